@@ -347,6 +347,57 @@ def cli_leg(vs, regions, w):
     return out
 
 
+DUMP_SAMPLE_REGIONS = 64          # regions of the batch whose rows are written in full by --dump-outputs (a fixed, seeded sample)
+DUMP_MAX_CARRIERS = 3_000_000     # (16 bytes each: the sample stops growing past this many carriers, well inside 64 MB in all)
+
+
+def dump_outputs(outdir, vs, res, regions, seed=2024):
+    """--dump-outputs: what the caller of the timed path receives from its last step, as float64 / float32 .npy files in `outdir`.
+    Every region: its variant count and flags (`var_count`, `region_flags`) and the batch's totals.  A fixed, seeded sample of the
+    regions: every row of their answer text (`region_text`, the reference's `-o` file) as numbers -- position, REF / ALT lengths and
+    bases (character codes), carrier count -- and every carrier as (sample id, allele 1, allele 2, phased).  None of it depends on
+    how the result lies in memory, so two builds of the project compare output for output."""
+    import numpy as np
+    if not os.path.isdir(outdir):
+        os.makedirs(outdir)
+        with open(os.path.join(outdir, ".gitignore"), "w") as f:   # (a directory of outputs made here stays out of git status)
+            f.write("*\n")
+    n = len(regions)
+    raw = res.raw(with_carriers=False)
+    per_region = {"var_count": raw["var_count"].astype(np.float64), "region_flags": raw["region_flags"].astype(np.float64)}
+    del raw
+    sample = np.sort(np.random.default_rng(seed).choice(n, size=min(DUMP_SAMPLE_REGIONS, n), replace=False))
+    ids, picked, rows, refs, alts, cars = {}, [], [], [], [], []
+    for k, q in enumerate(sample):
+        if len(cars) > DUMP_MAX_CARRIERS:
+            break
+        picked.append((q, regions[q, 0], regions[q, 1]))
+        for line in res.region_text(int(q)).split("\n")[1:]:
+            if not line:
+                continue
+            p, ref, alt, smp = line.split("\t")
+            toks = smp.split()
+            rows.append((k, int(p), len(ref), len(alt), len(toks)))
+            refs += [ord(c) for c in ref]
+            alts += [ord(c) for c in alt]
+            for tok in toks:
+                name, gt = tok[:-1].rsplit("(", 1)
+                if name not in ids:
+                    ids[name] = vs.sample_id(name)
+                al = [-1 if a == "." else int(a) for a in gt.replace("/", "|").split("|")]
+                cars.append((ids[name], al[0], al[1] if len(al) > 1 else -1, 1 if "|" in gt else (0 if "/" in gt else -1)))
+    out = dict(per_region,
+               totals=np.array(res.totals(), dtype=np.float64),
+               sample_regions=np.array(picked, dtype=np.float64).reshape(-1, 3),      # (region index, start, end)
+               sample_rows=np.array(rows, dtype=np.float64).reshape(-1, 5),           # (sample k, pos, ref len, alt len, carriers)
+               sample_ref_bases=np.array(refs, dtype=np.float64),
+               sample_alt_bases=np.array(alts, dtype=np.float64),
+               sample_carriers=np.array(cars, dtype=np.float32).reshape(-1, 4))       # (sample id, allele 1, allele 2, phased)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def git_blob_hash(path):
     """`git hash-object` of a file without needing git: sha1("blob <len>\0" + content)."""
     import hashlib
@@ -720,21 +771,30 @@ def main():
     ap.add_argument("--emulate-shard", default="", metavar="K/N",
                     help="with --scaling strong on ONE GPU: run rank K's shard of the N-way split of the strong batch (what one of N GPUs would "
                          "run, without the collective) and print the N-GPU value it predicts: total regions / this shard's step time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--latency-samples", type=int, default=200)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the bench measures and checks: the box's streaming ceilings, roofline and phase "
+                         "times, the untimed legs (--extras), latency, the N > 1 collective checks, the CPU baseline and its parity stamp.  "
+                         "Without it a run sets up, warms up, times the steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64 / float32; a fixed, "
+                         "seeded sample of the regions in full, per-region counts of all of them): two builds can be compared output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baseline")
+    ap.add_argument("--latency-samples", type=int, default=200, help="(--full) single-region latency samples")
     ap.add_argument("--extras", default=os.environ.get("VS_BENCH_EXTRAS", "all"),
-                    help="comma list of the untimed legs to run: t4,points,sc,delivery,resident,cli,pipelined | all (= all but cli and pipelined, "
-                         "which run by name only) | none")
+                    help="(--full) comma list of the untimed legs to run: t4,points,sc,delivery,resident,cli,pipelined | all (= all but cli and "
+                         "pipelined, which run by name only) | none")
     ap.add_argument("--skip-extras", action="store_true", help="same as --extras none")
     ap.add_argument("--types", default="", metavar="LIST",
-                    help="mixed-type leg (BASELINE configs[4]: types 3 / 6 / 7 over N GPUs; src/commands.cc:150-193 dispatches all seven): comma list "
-                         "out of 2,3,4,5,6,7 -- every rank answers its shard with each type's entry point and, at N > 1, the per-region "
+                    help="(--full) mixed-type leg (BASELINE configs[4]: types 3 / 6 / 7 over N GPUs; src/commands.cc:150-193 dispatches all seven): "
+                         "comma list out of 2,3,4,5,6,7 -- every rank answers its shard with each type's entry point and, at N > 1, the per-region "
                          "summary records are all-gathered through vs_comm_*; per-type whole-job regions/s under `mixed_types`")
     ap.add_argument("--async-fill", action="store_true",
                     help="headline loop with the engine's pipelined expansion (option async_fill): step k's carrier expansion runs beside step "
                          "k + 1's bounds, scans and rows.  Off by default: the expansion kernel then shares the machine and its own duration -- "
                          "the roofline figure -- no longer describes the kernel; `--extras pipelined` measures the throughput beside the default loop")
     args = ap.parse_args()
+    if args.types and not args.full:
+        raise SystemExit("bench.py: --types is a leg of --full")
     if args.skip_extras or os.environ.get("VS_BENCH_SKIP_T4") == "1":
         args.extras = "none"
     # ("cli" saves and reloads the index through the on-disk format -- minutes for the 5 M-site cohort: only when asked for by name)
@@ -758,7 +818,7 @@ def main():
     import torch
     import torch.distributed as dist
 
-    ceil = box_ceilings() if int(os.environ.get("RANK", "0")) == 0 and int(os.environ.get("WORLD_SIZE", "1")) == 1 else None
+    ceil = box_ceilings() if args.full and int(os.environ.get("RANK", "0")) == 0 and int(os.environ.get("WORLD_SIZE", "1")) == 1 else None
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # VS_BENCH_SAME_DEVICE=1 (a REHEARSAL of the N > 1 code on a one-GPU box, not a measurement): every rank uses GPU 0, torch.distributed runs
@@ -932,6 +992,54 @@ def main():
     res = old   # (the last step's result stays alive: the figures below are read from it)
     if vs.info().t6_refused != refused_before:   # (a refused batch does its work only when its result is read: a timed loop must not hold one)
         raise SystemExit("bench.py: a batch of the timed loop was refused on the device (speculative sizes): the warm-up did not settle the handle's expectation")
+    dumped = dump_outputs(args.dump_outputs, vs, res, regions) if args.dump_outputs and rank == 0 else None
+
+    shard_note = (f"one sorted batch of {total_regions} regions cut into {world} contiguous shard(s)" if strong
+                  else f"{nreg} random {w['region_len']} bp regions per GPU")
+    workload_desc = (f"{args.workload}: {w['ref_length']} bp, {w['num_variants']} sites, {w['num_samples']} samples, {shard_note}, "
+                     "query type 6 (get_var_in_ref), index + regions resident in HBM, results left in HBM"
+                     + (" [regions handed over as a host array in every step]" if host_regions else ""))
+    sharding = f"regions x{world}, index replicated" + ((", RCCL all-gatherv of hit lists (per-region site ranges) through "
+                                                         + ("torch.distributed" if torch_collective else "the C ABI (vs_comm_allgather_regions)"))
+                                                        if use_dist else "")
+    index_info = {"vertices": info.num_vertices, "csr_edges": info.num_edges_csr, "sites": info.num_sites, "classes": info.num_classes,
+                  "carrier_records": info.num_carriers, "hbm_image_bytes": info.device_bytes, "build_s": round(t_build, 1)}
+    emulated = ({"shard": emu[0], "of": emu[1], "regions_in_shard": nreg, "batch_regions": (args.regions or 1_000_000),
+                 "ms_per_step": elapsed / args.steps * 1e3,
+                 "predicted_value_at_n_gpus": (args.regions or 1_000_000) * args.steps / elapsed,
+                 "note": "one GPU running rank K's shard of the strong batch, no collective; the N-GPU step is the slowest shard's"}
+                if emu is not None else None)
+    head = {
+        "metric": "region-queries/sec (batch, query-type 6)",
+        "value": total_regions * args.steps / elapsed,
+        "unit": "queries/s",
+        "n_gpus": world,
+        **({"rehearsal_same_device": True, "rehearsal_note": "every rank on GPU 0 through tests/native/fake_rccl.cpp and gloo: the N > 1 code paths, not a measurement"}
+           if same_device else {}),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic",
+    }
+    if not args.full:
+        # a plain run: the headline and what describes it; everything else the bench measures and checks is --full's
+        if rank == 0:
+            out = dict(head, config={"workload": workload_desc, "pipelined_expansion": pipelined, "regions_per_gpu": nreg,
+                                     "regions_total": total_regions, "region_len": w["region_len"], "sharding": sharding, "index": index_info},
+                       emulated_shard=emulated, result_digest=f"{res.digest():016x}", dumped_outputs=dumped)
+            print(json.dumps(out), file=real_stdout, flush=True)
+        res.close()
+        if comm is not None:
+            comm.close()
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     if fill_steps == 0:   # (a form without per-result events: private rows -- the handle's events of one more batch)
         res2, _g = step()
         fill_ms, fill_steps = vs.last_timing().ms_fill * args.steps, args.steps
@@ -1322,28 +1430,10 @@ def main():
             vs.set_option("resident_lists", 0)
 
     if rank == 0:
-        shard_note = (f"one sorted batch of {total_regions} regions cut into {world} contiguous shard(s)" if strong
-                      else f"{nreg} random {w['region_len']} bp regions per GPU")
         out = {
-            "metric": "region-queries/sec (batch, query-type 6)",
-            "value": total_regions * args.steps / elapsed,
-            "unit": "queries/s",
-            "n_gpus": world,
-            **({"rehearsal_same_device": True, "rehearsal_note": "every rank on GPU 0 through tests/native/fake_rccl.cpp and gloo: the N > 1 code paths, not a measurement"}
-               if same_device else {}),
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "u32",
-            "data": "synthetic",
+            **head,
             "config": {
-                "workload": f"{args.workload}: {w['ref_length']} bp, {w['num_variants']} sites, "
-                            f"{w['num_samples']} samples, {shard_note}, "
-                            "query type 6 (get_var_in_ref), index + regions resident in HBM, results left in HBM"
-                            + (" [regions handed over as a host array in every step]" if host_regions else ""),
+                "workload": workload_desc,
                 "pipelined_expansion": pipelined,   # step k's carrier expansion runs beside step k + 1's bounds, scans and rows (engine option async_fill)
                 "regions_per_gpu": nreg, "regions_total": total_regions, "region_len": w["region_len"],
                 "variants_per_region": nvar / max(nq, 1), "carriers_per_variant": ncar / max(nvar, 1),
@@ -1353,12 +1443,8 @@ def main():
                                           "site refers to them (its rows are a range of the shared table), as REF/ALT refer to the sequence "
                                           "pool" if lists_shared else None,
                                   "private_rows_and_lists_for_comparison": private},
-                "sharding": f"regions x{world}, index replicated" + ((", RCCL all-gatherv of hit lists (per-region site ranges) through "
-                                                                        + ("torch.distributed" if torch_collective else "the C ABI (vs_comm_allgather_regions)"))
-                                                                       if use_dist else ""),
-                "index": {"vertices": info.num_vertices, "csr_edges": info.num_edges_csr, "sites": info.num_sites,
-                          "classes": info.num_classes, "carrier_records": info.num_carriers,
-                          "hbm_image_bytes": info.device_bytes, "build_s": round(t_build, 1)},
+                "sharding": sharding,
+                "index": index_info,
             },
             # achieved = bytes that crossed the HBM pins per launch of the dominant kernel (rocprofv3 --pmc passes of this
             # command on THESE kernels, profiles/traffic_<workload>.json; FETCH_SIZE corrected per MI355X_MICROARCH.md) /
@@ -1418,11 +1504,7 @@ def main():
             "strong": (dist_info or {}).pop("strong", None) if dist_info else None,
             "distributed": dist_info,
             "mixed_types": mixed_info,
-            "emulated_shard": ({"shard": emu[0], "of": emu[1], "regions_in_shard": nreg, "batch_regions": (args.regions or 1_000_000),
-                                "ms_per_step": elapsed / args.steps * 1e3,
-                                "predicted_value_at_n_gpus": (args.regions or 1_000_000) * args.steps / elapsed,
-                                "note": "one GPU running rank K's shard of the strong batch, no collective; the N-GPU step is the slowest shard's"}
-                               if emu is not None else None),
+            "emulated_shard": emulated,
             "p50_latency_us": p50,
             "p50_latency_paced_1ms_us": p50_paced,
             "type4": t4,
@@ -1430,6 +1512,7 @@ def main():
             "sample_coordinate_queries": tsc,
             "delivery": delivery, "resident_lists": resident, "unsorted_batch": unsorted, "pipelined": pipe,
             "result_digest": f"{digest:016x}",
+            "dumped_outputs": dumped,
             # type-6 batches of this process submitted without a host wait (table and arena sized from the batch before, totals read on the
             # device) and how many of those the device refused and the host reran (none inside a timed loop: the loops check)
             "speculative_batches": {"submitted": int(vs.info().t6_speculated), "refused_and_redone": int(vs.info().t6_refused),

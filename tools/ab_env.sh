@@ -2,6 +2,7 @@
 # Same-box A/B of an environment switch of the engine on the default bench:   tools/ab_env.sh VAR "v1 v2 ..." [rounds] [extra bench args]
 # (box to box -- and run to run on one box -- the headline moves by several per cent: settings alternate, several rounds)
 var=$1; vals=$2; rounds=${3:-2}; shift 3
+set -- --full "$@"   # (the roofline figures printed below are measured by --full)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $R
 mkdir -p gpurun_out/ab_env

@@ -12,7 +12,7 @@ for _ in range(2):
         env = dict(os.environ, VS_BENCH_SKIP_T4="1")
         if lib:
             env["VS_ENGINE_LIB"] = lib
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "2", "--no-cpu-baseline",
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "10", "--warmup", "2", "--no-cpu-baseline",
                               "--latency-samples", "50"], env=env, capture_output=True, text=True)
         try:
             d = json.loads(out.stdout.strip().splitlines()[-1])

