@@ -259,6 +259,69 @@ def test_type6_batches_that_outgrow_the_previous_batch_are_redone(tmp_path):
     vs.close()
 
 
+def test_every_accessor_redoes_a_refused_type6_batch_first(tmp_path):
+    """Every accessor of a result passes the same gate (engine.hip: result_enter): a speculative type-6 batch that was refused on the
+    device is redone with the exact sizes whichever accessor touches it first -- the view, the raw copy, one region's text, the layout,
+    the digest, the fill time, the two pack calls or the totals -- and then answers like the same batch with t6_speculate off."""
+    import torch
+    vs = VariantStore.synthetic(device=0, ref_length=2_000_000, num_variants=20_000, num_samples=200, seed=21,
+                                first_pos=500, frac_ins=0.05, frac_del=0.05, frac_multi=0.02, max_indel=6, af_exponent=3.0)
+    plain = os.path.join(tmp_path, "p.bin")
+    vs.export_plain(plain)
+    orc = Oracle(plain)
+    rng = np.random.default_rng(9)
+    n = 1500
+    starts = np.sort(rng.integers(1, 1_980_000, size=n))
+    short = np.stack([starts, starts + 300], axis=1).astype(np.uint64)
+    long_ = np.stack([starts, starts + 9000], axis=1).astype(np.uint64)
+
+    vs.set_option("t6_speculate", 0)
+    r = vs.get_var_in_ref(long_)
+    want = (r.totals(), r.digest(), r.layout())
+    slots = want[2][0]
+    regs = torch.zeros((n, 4), dtype=torch.int64, device="cuda")
+    hdrs = torch.zeros((slots, 4), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+
+    def packs(res):                         # (the records of the whole batch, region_base 3)
+        assert res.pack_regions_into(regs.data_ptr(), n, region_base=3) == n
+        assert res.pack_headers_into(hdrs.data_ptr(), slots, region_base=3) == slots
+        return regs.cpu().numpy(), hdrs.cpu().numpy()
+
+    want_packs = packs(r)
+    r.close()
+    vs.set_option("t6_speculate", 1)
+    first_touch = {
+        "view": lambda res: res.view(),
+        "raw": lambda res: res.raw(),
+        "region_text": lambda res: res.region_text(n // 2),
+        "layout": lambda res: res.layout(),
+        "digest": lambda res: res.digest(),
+        "fill_ms": lambda res: res.fill_ms(),
+        "pack_regions": lambda res: res.pack_regions_into(regs.data_ptr(), n),
+        "pack_headers": lambda res: res.pack_headers_into(hdrs.data_ptr(), slots),
+        "totals": lambda res: res.totals(),
+    }
+    for name, touch in first_touch.items():
+        for _ in range(9):                  # nine short batches, unread: the handle expects short batches again
+            vs.get_var_in_ref(short).close()
+        s0 = vs.info()
+        c = vs.get_var_in_ref(long_)        # as many regions, thirty times the rows: refused on the device, redone at first use
+        assert vs.info().t6_speculated == s0.t6_speculated + 1, name
+        assert vs.info().t6_refused == s0.t6_refused, name
+        touch(c)
+        assert vs.info().t6_refused == s0.t6_refused + 1, name
+        assert (c.totals(), c.digest(), c.layout()) == want, name
+        got = packs(c)
+        assert np.array_equal(got[0], want_packs[0]) and np.array_equal(got[1], want_packs[1]), name
+        for q in range(0, n, 97):
+            cnt, _, text = orc.get_var_in_ref(int(long_[q, 0]), int(long_[q, 1]))
+            if cnt >= 0:
+                assert c.region_text(q) == text, (name, q)
+        c.close()
+    vs.close()
+
+
 @pytest.mark.parametrize("shape", ["wide", "explicit"])
 def test_many_short_scattered_regions_wide_and_explicit_cohorts(shape, tmp_path):
     """The many-runs shape of a shared batch (test_many_short_scattered_regions_many_runs) through the OTHER instantiation of

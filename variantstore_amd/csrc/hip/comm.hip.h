@@ -152,14 +152,19 @@ int vs_comm_info(vs_comm* c, int* rank, int* world, int* rccl_ranks) {
   return VS_OK;
 }
 
-int vs_comm_allgather_regions(vs_comm* c, vs_result* r, uint64_t region_base, uint64_t max_count, void* device_dst, int async_op) {
-  if (!c || !r || !device_dst) return fail(VS_ERR_ARG, "null argument");
+// The communicator's checks, then the result's gate (result_enter): from here on the handle's device is current.
+static int comm_enter(vs_comm* c, vs_result* r, const void* dst) {
+  if (!c || !r || !dst) return fail(VS_ERR_ARG, "null argument");
   if (r->idx != c->idx) return fail(VS_ERR_ARG, "the result belongs to another index handle than the communicator");
+  return result_enter(r, Want::Any, true);   // (a refused batch is redone before its records travel)
+}
+
+int vs_comm_allgather_regions(vs_comm* c, vs_result* r, uint64_t region_base, uint64_t max_count, void* device_dst, int async_op) {
+  VS_TRY(comm_enter(c, r, device_dst));
   if (r->d.Q > max_count) return fail(VS_ERR_ARG, "this rank holds %llu regions, max_count is %llu", (unsigned long long)r->d.Q, (unsigned long long)max_count);
   RcclApi* api = rccl_api();
   if (!api) return rccl_missing();
   vs_index* idx = c->idx;
-  HIP_TRY(hipSetDevice(idx->device));
   VS_TRY(vs_comm_wait(c));   // (the send buffer is reused)
   const size_t bytes = std::max<uint64_t>(max_count, 1) * 32;
   if (c->send_cap < bytes) {
@@ -188,8 +193,7 @@ int vs_comm_allgather_regions(vs_comm* c, vs_result* r, uint64_t region_base, ui
 }
 
 int vs_comm_allgather_regions_host(vs_comm* c, vs_result* r, uint64_t region_base, uint64_t max_count, void* host_dst) {
-  if (!c || !host_dst) return fail(VS_ERR_ARG, "null argument");
-  HIP_TRY(hipSetDevice(c->idx->device));
+  VS_TRY(comm_enter(c, r, host_dst));
   VS_TRY(vs_comm_wait(c));
   const size_t bytes = (size_t)c->world * std::max<uint64_t>(max_count, 1) * 32;
   if (c->recv_cap < bytes) {

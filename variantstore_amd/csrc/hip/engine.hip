@@ -217,6 +217,7 @@ struct vs_result {
   float fill_ms = -1.0f;
   // a SPECULATIVE type-6 batch: d.A / d.S hold what was ALLOCATED until somebody asks for the result's sizes (result_sizes)
   bool sizes_pending = false, totals_captured = false;
+  int redo_rc = VS_OK;                // the redo of a refused batch failed with this code: the result is torn, every accessor returns it (result_enter)
   int plan_slot = -1;
   uint64_t plan_seq = 0, cap_rows = 0, cap_arena = 0;
   PlanTotals plan_copy{};
@@ -238,9 +239,6 @@ struct vs_result {
   std::vector<uint64_t> h_byte_begin;
   std::vector<uint8_t> h_chars;
 };
-
-#define VS_NOT_SEQ(r) \
-  if ((r)->kind == 2 || (r)->kind == 3) return fail(VS_ERR_ARG, "a sequence result (query types 2/3) has no variant table; use vs_result_get_sequences")
 
 // ------------------------------------------------------------------ helpers
 static int server_stop(vs_index* idx);   // the resident latency server must be gone before anything that synchronises the
@@ -412,6 +410,7 @@ struct ScratchBufs {
   ScratchBufs(const ScratchBufs&) = delete;
   ScratchBufs& operator=(const ScratchBufs&) = delete;
   void release() { release_bufs(idx, bufs); }
+  void hand_to(std::vector<DevBuf>& owner) { owner.insert(owner.end(), bufs.begin(), bufs.end()); bufs.clear(); }   // (a result that outlives the call)
   ~ScratchBufs() {
     if (bufs.empty()) return;
     if (idx->plan_stream) (void)hipStreamSynchronize(idx->plan_stream);
@@ -860,6 +859,29 @@ static int result_ready(vs_result* r) {
   return VS_OK;
 }
 
+// Every throughput batch starts here: a throughput batch does not share the GPU with a polling server, and the handle's timing
+// state is this batch's from now on (an earlier lean batch's event pair is not).
+static int begin_batch(vs_index* idx) {
+  if (idx->srv_alive) VS_TRY(server_stop(idx));
+  idx->timing_pending = false; idx->timing_owner = nullptr; idx->timing_total_only = false;
+  return VS_OK;
+}
+// A batch that returns ENQUEUED (async_submit): everything that reads the result is ordered behind it on the handle's stream, and
+// the call's temporaries stay with the result until its completion event (vs_result_free, result_ready) -- a buffer in the pool is
+// never referenced by work in flight, whatever stream takes it next.  record_done = false: the caller's last event is the batch's
+// completion already (a lean type-6 batch's last kernel is its expansion: the result's own event behind that is it).
+static int batch_enqueued(vs_result* r, ScratchBufs& scratch, bool record_done = true) {
+  vs_index* idx = r->idx;
+  if (record_done) {
+    VS_TRY(pooled_event(idx, &r->ev_done));
+    HIP_TRY(hipEventRecord(r->ev_done, idx->stream));
+  }
+  r->pending = true;
+  idx->batch_in_flight = true;
+  scratch.hand_to(r->bufs);
+  return VS_OK;
+}
+
 // The carrier expansion of one result (or of the resident arena): one launch over n_fill rows.
 static int fill_lists(vs_index* idx, const DevResult& d, bool share, const uint32_t* u_site, uint64_t n_fill, hipStream_t on = nullptr) {
   if (n_fill) {
@@ -1054,13 +1076,11 @@ static int capture_totals(vs_result* r) {
   else { idx->sort_hint = true; idx->sort_probe_in = 32; }   // (as after a batch that was sorted on the device: the next ones sort first -- also when nobody reads this one)
   return VS_OK;
 }
-static int result_ready(vs_result* r);
-static void release_bufs(vs_index* idx, std::vector<DevBuf>& bufs);
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
                             bool allow_async, bool may_speculate);
-// Every accessor of a result calls this first: a speculative batch's sizes become the plan's totals here -- or, when the plan refused the
-// batch on the device (more rows or arena entries than were allocated, or regions that were not sorted), the batch is run again from the
-// result's own copy of the regions, with the exact sizes, before anything is read.
+// A speculative batch's sizes become the plan's totals here -- or, when the plan refused the batch on the device (more rows or arena
+// entries than were allocated, or regions that were not sorted), the batch is run again from the result's own copy of the regions,
+// with the exact sizes, before anything is read.  A redo that fails leaves the result torn: its code sticks (vs_result::redo_rc).
 static int result_sizes(vs_result* r) {
   if (!r->sizes_pending) return VS_OK;
   vs_index* idx = r->idx;
@@ -1073,16 +1093,35 @@ static int result_sizes(vs_result* r) {
     return VS_OK;
   }
   idx->t6_refused++;
-  VS_TRY(result_ready(r));                         // (its kernels returned at once; nothing was written behind the plan)
-  if (idx->timing_owner == r) { idx->timing_owner = nullptr; idx->timing_pending = false; }
-  std::vector<DevBuf> old;
-  old.swap(r->bufs);                               // (the result's copy of the regions lives in there: released when the redo has read it)
-  const uint64_t n = r->d.Q;
-  const vs_region* dreg = reinterpret_cast<const vs_region*>(r->d.regions);
-  r->d = DevResult{};
-  const int rc = run_type6_shared(idx, dreg, n, r, /*regions_on_device=*/true, nullptr, /*allow_async=*/false, /*may_speculate=*/false);
-  release_bufs(idx, old);
+  int rc = result_ready(r);                        // (its kernels returned at once; nothing was written behind the plan)
+  if (rc == VS_OK) {
+    if (idx->timing_owner == r) { idx->timing_owner = nullptr; idx->timing_pending = false; }
+    std::vector<DevBuf> old;
+    old.swap(r->bufs);                             // (the result's copy of the regions lives in there: released when the redo has read it)
+    const uint64_t n = r->d.Q;
+    const vs_region* dreg = reinterpret_cast<const vs_region*>(r->d.regions);
+    r->d = DevResult{};
+    rc = run_type6_shared(idx, dreg, n, r, /*regions_on_device=*/true, nullptr, /*allow_async=*/false, /*may_speculate=*/false);
+    release_bufs(idx, old);
+  }
+  r->redo_rc = rc;
   return rc;
+}
+
+// THE entry of every exported accessor of a result, in this order: the result exists and is of the kind asked for, no redo of it has
+// failed (vs_result::redo_rc), its handle's device is current -- and, with `sizes`, a speculative batch's sizes are known (result_sizes:
+// a refused batch is redone here, on its own handle's device).  The helpers below that take a result (fetch_*, raw_copy_begin,
+// launch_pack_regions) assume that the caller has passed this gate; they neither set the device nor resolve sizes.
+enum class Want { Variants, Sequences, Any };
+static hipError_t result_device(const vs_result* r) { return hipSetDevice(r->idx->device); }   // (vs_result_free's too: it tears down any state)
+static int result_enter(vs_result* r, Want want, bool sizes) {
+  if (!r) return fail(VS_ERR_ARG, "null argument");
+  const bool seq = r->kind == 2 || r->kind == 3;
+  if (want == Want::Variants && seq) return fail(VS_ERR_ARG, "a sequence result (query types 2/3) has no variant table; use vs_result_get_sequences");
+  if (want == Want::Sequences && !seq) return fail(VS_ERR_ARG, "not a sequence result");
+  if (r->redo_rc != VS_OK) return fail(r->redo_rc, "the batch was refused on the device and its redo failed (%s): the result holds nothing; free it", vs_strerror(r->redo_rc));
+  HIP_TRY(result_device(r));
+  return sizes ? result_sizes(r) : VS_OK;
 }
 
 // The expansion of a shared batch that writes the shared rows as well (k_fill_sites2).  mode 2 (tuning builds): split -- rows +
@@ -1131,8 +1170,7 @@ static void launch_fill2(vs_index* idx, const DevResult& d, const RunRec* runs, 
 //   done   k_post_done: a word in mapped host memory, the host spins on it
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
                             bool allow_async, bool may_speculate = true) {
-  if (idx->srv_alive) VS_TRY(server_stop(idx));   // a throughput batch does not share the GPU with a polling server
-  idx->timing_pending = false; idx->timing_owner = nullptr; idx->timing_total_only = false;   // (an earlier lean batch's event pair is not this batch's)
+  VS_TRY(begin_batch(idx));
   DevResult& d = r->d;
   d.Q = n;
   uint64_t* dreg = nullptr;
@@ -1419,32 +1457,18 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   }
   idx->timing_pending = true;
   idx->timing_fill_launches = n_fill ? 1 : 0;   // (async_fill: ms_fill is what the first stream saw of it, ~0; vs_result_fill_ms has the kernel's time)
-  // async_submit: the batch is enqueued, its sizes are known (the plan's totals; a speculative batch: result_sizes) and its buffers are the result's -- the call
-  // returns here.  Whatever reads the result (copies, digests, packs, the next batch's kernels that reuse the temporaries
-  // released below) is ordered behind the batch on the handle's stream; the timing events are read when asked for.
-  if (!async_submit) {
-    uint64_t* done = idx->pinned + vs_index::kPinDone;
-    const uint64_t seq = ++idx->done_seq;
-    hipLaunchKernelGGL(k_post_done, dim3(1), dim3(1), 0, idx->stream, done, seq);
-    HIP_TRY(hipGetLastError());
-    VS_TRY(wait_posted(idx, done, seq, 2000));
-    idx->batch_in_flight = false;
-  }
-  if (async_submit) {
-    // the batch's completion event (a lean batch's last kernel is its expansion: the result's own event behind that is it);
-    // the call's temporaries stay with the result until it has happened (vs_result_free, result_ready): a buffer in the
-    // pool is never referenced by work in flight, whatever stream takes it next
-    if (!lean) {
-      VS_TRY(pooled_event(idx, &r->ev_done));
-      HIP_TRY(hipEventRecord(r->ev_done, idx->stream));
-    }
-    r->pending = true;
-    idx->batch_in_flight = true;
-  }
-  if (async_fill || async_submit) { r->bufs.insert(r->bufs.end(), scratch.bufs.begin(), scratch.bufs.end()); scratch.bufs.clear(); }
+  // async_submit: the batch is enqueued, its sizes are known (the plan's totals; a speculative batch: result_sizes) and its buffers are the
+  // result's -- the call returns here; the timing events are read when asked for
+  if (async_submit) return batch_enqueued(r, scratch, /*record_done=*/!lean);
+  uint64_t* done = idx->pinned + vs_index::kPinDone;
+  const uint64_t seq = ++idx->done_seq;
+  hipLaunchKernelGGL(k_post_done, dim3(1), dim3(1), 0, idx->stream, done, seq);
+  HIP_TRY(hipGetLastError());
+  VS_TRY(wait_posted(idx, done, seq, 2000));
+  idx->batch_in_flight = false;
+  if (async_fill) scratch.hand_to(r->bufs);
   scratch.release();
-  if (!async_submit) VS_TRY(collect_timing(idx));
-  return VS_OK;
+  return collect_timing(idx);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1507,8 +1531,7 @@ static int batch_setup(BatchCtx& c, const vs_region* regions, bool regions_on_de
   vs_index* idx = c.idx;
   vs_result* r = c.r;
   const uint64_t n = c.n;
-  if (idx->srv_alive) VS_TRY(server_stop(idx));   // a throughput batch does not share the GPU with a polling server
-  idx->timing_pending = false; idx->timing_owner = nullptr; idx->timing_total_only = false;
+  VS_TRY(begin_batch(idx));
   DevResult& d = r->d;
   d.Q = n;
   uint64_t* dreg = nullptr;
@@ -1610,27 +1633,20 @@ static int batch_fill(BatchCtx& c, bool allow_async) {
   return VS_OK;
 }
 
-// enqueued: the batch returns when its last kernel is launched (the walking query types under async_submit): its temporaries stay
-// with the result until the completion event recorded here, everything that reads the result is ordered behind it on the
-// handle's stream, and the phase times are read from the handle's events when somebody asks (vs_index_last_timing)
+// enqueued: the batch returns when its last kernel is launched (the walking query types under async_submit: batch_enqueued), and the
+// phase times are read from the handle's events when somebody asks (vs_index_last_timing)
 static int batch_finish(BatchCtx& c, bool enqueued = false) {
   vs_index* idx = c.idx;
   HIP_TRY(hipEventRecord(idx->ev[4], idx->stream));
   if (c.lean_events) idx->timing_total_only = true;
   if (enqueued) {
-    vs_result* r = c.r;
-    VS_TRY(pooled_event(idx, &r->ev_done));
-    HIP_TRY(hipEventRecord(r->ev_done, idx->stream));
-    r->pending = true;
-    idx->batch_in_flight = true;
-    r->bufs.insert(r->bufs.end(), c.scratch.bufs.begin(), c.scratch.bufs.end());
-    c.scratch.bufs.clear();
+    VS_TRY(batch_enqueued(c.r, c.scratch));
     idx->timing_pending = true;
     return VS_OK;
   }
   HIP_TRY(hipStreamSynchronize(idx->stream));
   idx->batch_in_flight = false;
-  if (c.async_fill) { c.r->bufs.insert(c.r->bufs.end(), c.scratch.bufs.begin(), c.scratch.bufs.end()); c.scratch.bufs.clear(); }
+  if (c.async_fill) c.scratch.hand_to(c.r->bufs);
   c.scratch.release();
   idx->timing_pending = true;
   return collect_timing(idx);
@@ -1718,16 +1734,14 @@ static void launch_sample_seq(vs_index* idx, const DevSeqResult& q, uint64_t n) 
 //          (cooperative, serial with jumps, or literal: option t4_walk); a region that outgrows its capacity -- not seen
 //          in practice; option force_fallbacks -- sends the batch down the count-then-emit pair of walks
 //   claims one carrier list per reported VERTEX, shared by the rows that report it (k_t4_claim)
-static int run_walk_batch_once(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, uint32_t sample_id, const uint32_t* sample_ids, int walk_mode,
-                               bool speculate, bool* refused);
 // ONE host wait per batch (round 5): the recording walk's scratch is sized from the handle's previous batch of the kind; a batch
-// that does not fit is refused on the device (WalkAdmit: the walk's first look) and redone here with the exact size -- the first batch of a handle
-// and a batch 12 % bigger than any before it pay the second wait, a steady stream of batches never does.
-static int run_walk_batch(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, uint32_t sample_id, const uint32_t* sample_ids, int walk_mode) {
+// that does not fit is refused on the device (WalkAdmit: the walk's first look) and redone with the exact size (run_with_redo) -- the
+// first batch of a handle and a batch 12 % bigger than any before it pay the second wait, a steady stream of batches never does.
+template <typename Once>   // once(bool speculate, bool* refused)
+static int run_with_redo(Once&& once) {
   bool refused = false;
-  VS_TRY(run_walk_batch_once(idx, regions, n, r, sample_id, sample_ids, walk_mode, true, &refused));
-  if (!refused) return VS_OK;
-  return run_walk_batch_once(idx, regions, n, r, sample_id, sample_ids, walk_mode, false, &refused);
+  VS_TRY(once(true, &refused));
+  return refused ? once(false, &refused) : VS_OK;
 }
 static int run_walk_batch_once(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, uint32_t sample_id, const uint32_t* sample_ids, int walk_mode,
                                bool speculate, bool* refused) {
@@ -1900,6 +1914,9 @@ static int run_walk_batch_once(vs_index* idx, const vs_region* regions, uint64_t
   if (claim_tab >= 0 && enqueued) idx->t4_claim_done[claim_tab] = r->ev_done;   // (not enqueued: the stream has been synchronised)
   return VS_OK;
 }
+static int run_walk_batch(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, uint32_t sample_id, const uint32_t* sample_ids, int walk_mode) {
+  return run_with_redo([&](bool speculate, bool* refused) { return run_walk_batch_once(idx, regions, n, r, sample_id, sample_ids, walk_mode, speculate, refused); });
+}
 
 template <typename T>
 static int fetch(vs_index* idx, std::vector<T>& h, const T* dptr, size_t n) {
@@ -1908,9 +1925,9 @@ static int fetch(vs_index* idx, std::vector<T>& h, const T* dptr, size_t n) {
   return VS_OK;
 }
 
+// The host copies of a result.  The caller has passed the gate (result_enter): the handle's device is current and the sizes are known.
 // carriers [first, first + n) of the arena as 32-bit words (id | gt << 29), whatever the arena's width
 static int fetch_carriers(vs_result* r, uint64_t first, uint64_t n, std::vector<uint32_t>& out) {
-  VS_TRY(result_sizes(r));
   vs_index* idx = r->idx;
   VS_TRY(result_ready(r));
   out.resize(n);
@@ -1933,10 +1950,8 @@ static int fetch_carriers(vs_result* r, uint64_t first, uint64_t n, std::vector<
 
 // the per-region arrays (Q-sized: a few MB for the largest batches)
 static int fetch_region_meta(vs_result* r) {
-  VS_TRY(result_sizes(r));
   if (r->have_meta) return VS_OK;
   vs_index* idx = r->idx;
-  HIP_TRY(hipSetDevice(idx->device));
   const DevResult& d = r->d;
   VS_TRY(fetch(idx, r->h_flags, (const uint8_t*)d.q_flags, d.Q));
   VS_TRY(fetch(idx, r->h_var_begin, (const uint64_t*)d.var_begin, d.Q + 1));
@@ -1957,7 +1972,6 @@ static int fetch_region_meta(vs_result* r) {
 // The whole variant table on the host, and the VIEW built from it: every region's rows expanded back to back (shared
 // rows once per region that reports them) as the structure-of-arrays vs_result_view promises.
 static int fetch_headers(vs_result* r) {
-  VS_TRY(result_sizes(r));
   if (r->have_headers) return VS_OK;
   vs_index* idx = r->idx;
   VS_TRY(fetch_region_meta(r));
@@ -1988,22 +2002,14 @@ static int fetch_headers(vs_result* r) {
 }
 
 // Query types 2 and 3: count pieces and bytes per region, scan, emit the piece list, decode it.  ONE host wait per batch
-// (the byte total): the piece list is sized from the handle's previous batch of the type, as the walking types' scratch is.
-static int run_sample_seq_once(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, int mode, vs_result* r, bool speculate, bool* refused);
-static int run_sample_seq(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, int mode, vs_result* r) {
-  bool refused = false;
-  VS_TRY(run_sample_seq_once(idx, regions, n, sample_ids, mode, r, true, &refused));
-  if (!refused) return VS_OK;
-  return run_sample_seq_once(idx, regions, n, sample_ids, mode, r, false, &refused);
-}
+// (the byte total): the piece list is sized from the handle's previous batch of the type, as the walking types' scratch is (run_with_redo).
 static int run_sample_seq_once(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, int mode, vs_result* r, bool speculate, bool* refused) {
   DevSeqResult& q = r->sq;
   // everything in front of the host wait on the handle's second stream, beside the previous batch's k_copy_segments (PreStream)
   const bool aside = idx->opts.async_submit && speculate && n > 0 && !idx->opts.force_fallbacks && !idx->opts.lat_debug;
   if (aside) VS_TRY(ensure_plan_stream(idx));
   PreStream pre(idx, aside ? idx->plan_stream : nullptr);
-  if (idx->srv_alive) VS_TRY(server_stop(idx));
-  idx->timing_pending = false; idx->timing_owner = nullptr; idx->timing_total_only = false;
+  VS_TRY(begin_batch(idx));
   q.Q = n;
   r->d.Q = n;
   uint64_t* dreg = nullptr;
@@ -2107,13 +2113,8 @@ static int run_sample_seq_once(vs_index* idx, const vs_region* regions, uint64_t
     }
   }
   HIP_TRY(hipEventRecord(idx->ev[4], idx->stream));
-  if (idx->opts.async_submit && single_walk) {   // the batch is enqueued: return; its temporaries stay with the result until its completion event
-    VS_TRY(pooled_event(idx, &r->ev_done));
-    HIP_TRY(hipEventRecord(r->ev_done, idx->stream));
-    r->pending = true;
-    idx->batch_in_flight = true;
-    r->bufs.insert(r->bufs.end(), scratch.bufs.begin(), scratch.bufs.end());
-    scratch.bufs.clear();
+  if (idx->opts.async_submit && single_walk) {   // the batch is enqueued: return
+    VS_TRY(batch_enqueued(r, scratch));
     idx->timing_pending = true; idx->timing_total_only = true;
     return VS_OK;
   }
@@ -2125,11 +2126,13 @@ static int run_sample_seq_once(vs_index* idx, const vs_region* regions, uint64_t
   t.fill_launches = 0;
   return VS_OK;
 }
+static int run_sample_seq(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, int mode, vs_result* r) {
+  return run_with_redo([&](bool speculate, bool* refused) { return run_sample_seq_once(idx, regions, n, sample_ids, mode, r, speculate, refused); });
+}
 
 // the per-region records of any result on the handle's stream: site ranges + counts (k_pack_regions: query types 6, 4, 5, 1, 7)
-// or pieces + bytes (k_pack_seq_regions: types 2, 3)
+// or pieces + bytes (k_pack_seq_regions: types 2, 3).  The caller has passed the gate (result_enter).
 static int launch_pack_regions(vs_result* r, uint64_t* dst, uint64_t region_base) {
-  VS_TRY(result_sizes(r));
   vs_index* idx = r->idx;
   const uint64_t n = r->d.Q;
   if (!n) return VS_OK;
@@ -2139,10 +2142,9 @@ static int launch_pack_regions(vs_result* r, uint64_t* dst, uint64_t region_base
   return VS_OK;
 }
 
-static int fetch_sequences(vs_result* r) {
+static int fetch_sequences(vs_result* r) {   // (the caller has passed the gate)
   if (r->have_seq) return VS_OK;
   vs_index* idx = r->idx;
-  HIP_TRY(hipSetDevice(idx->device));
   VS_TRY(fetch(idx, r->h_flags, (const uint8_t*)r->sq.q_flags, r->sq.Q));
   VS_TRY(fetch(idx, r->h_byte_begin, (const uint64_t*)r->sq.byte_begin, r->sq.Q + 1));
   VS_TRY(fetch(idx, r->h_chars, (const uint8_t*)r->sq.chars, r->seq_bytes));
@@ -2389,6 +2391,33 @@ static int drop_result(vs_result* r, int rc) {
   if (r->idx && r->idx->stream) (void)hipStreamSynchronize(r->idx->stream);
   vs_result_free(r);
   return rc;
+}
+
+// The handle of a query: present and opened with a device.
+static int query_handle(const vs_index* idx) {
+  if (!idx) return fail(VS_ERR_ARG, "null argument");
+  if (idx->device < 0) return fail(VS_ERR_NO_DEVICE, "index handle was opened without a device; queries run on the GPU only");
+  return VS_OK;
+}
+static vs_result* new_result(vs_index* idx, int kind) {
+  vs_result* r = new vs_result();
+  r->idx = idx;
+  r->kind = kind;
+  idx->live_results++;
+  return r;
+}
+// THE way a query makes its result (after its own argument checks): the handle's device is current, a live result of `kind` is
+// handed to run(r); a failed run drops it (drop_result), a successful one goes to the caller.
+template <typename Run>
+static int make_result(vs_index* idx, int kind, vs_result** out, Run&& run) {
+  VS_TRY(query_handle(idx));
+  if (!out) return fail(VS_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(idx->device));
+  vs_result* r = new_result(idx, kind);
+  const int rc = run(r);
+  if (rc != VS_OK) return drop_result(r, rc);
+  *out = r;
+  return VS_OK;
 }
 
 extern "C" {
@@ -2638,7 +2667,7 @@ int vs_index_last_timing(const vs_index* cidx, vs_timing* t) {
 void vs_result_free(vs_result* r) {
   if (!r) return;
   if (r->idx) {
-    (void)hipSetDevice(r->idx->device);
+    (void)result_device(r);
     (void)result_ready(r);
     if (r->sizes_pending) {   // a speculative batch nobody asked anything of: its totals still feed the handle's hints, its mailbox goes back
       (void)capture_totals(r);
@@ -2669,95 +2698,63 @@ static int check_host_ids(vs_index* idx, const uint32_t* sample_ids, uint64_t n)
 }
 
 int vs_query_var_in_ref(vs_index* idx, const vs_region* regions, uint64_t n, vs_result** out) {
-  if (!idx || !out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
-  if (idx->device < 0) return fail(VS_ERR_NO_DEVICE, "index handle was opened without a device; queries run on the GPU only");
-  HIP_TRY(hipSetDevice(idx->device));
-  vs_result* r = new vs_result();
-  r->idx = idx;
-  idx->live_results++;
-  int rc = 1;
-  if (n > 0 && n <= 64) {
-    rc = run_small_type6(idx, regions, n, r);
-    if (rc == 1) {  // the device asked for more than the host had sized (host and device disagree: should not happen)
-      release_bufs(idx, r->bufs);
+  if (n && !regions) return fail(VS_ERR_ARG, "null argument");
+  return make_result(idx, 0, out, [&](vs_result* r) {
+    if (n > 0 && n <= 64) {
+      const int rc = run_small_type6(idx, regions, n, r);
+      if (rc != 1) return rc;
+      release_bufs(idx, r->bufs);   // the device asked for more than the host had sized (host and device disagree: should not happen)
       r->d = DevResult{};
     }
-  }
-  if (rc == 1) rc = run_type6(idx, regions, n, r, false, nullptr, /*allow_async=*/true);
-  if (rc != VS_OK) return drop_result(r, rc);
-  *out = r;
-  return VS_OK;
+    return run_type6(idx, regions, n, r, false, nullptr, /*allow_async=*/true);
+  });
 }
 
 int vs_query_var_in_ref_device(vs_index* idx, const vs_region* device_regions, uint64_t n, vs_result** out) {
-  if (!idx || !out || (n && !device_regions)) return fail(VS_ERR_ARG, "null argument");
-  if (idx->device < 0) return fail(VS_ERR_NO_DEVICE, "index handle was opened without a device; queries run on the GPU only");
-  HIP_TRY(hipSetDevice(idx->device));
-  vs_result* r = new vs_result();
-  r->idx = idx;
-  idx->live_results++;
-  const int rc = run_type6(idx, device_regions, n, r, /*regions_on_device=*/true, nullptr, /*allow_async=*/true);
-  if (rc != VS_OK) return drop_result(r, rc);
-  *out = r;
-  return VS_OK;
+  if (n && !device_regions) return fail(VS_ERR_ARG, "null argument");
+  return make_result(idx, 0, out, [&](vs_result* r) {
+    return run_type6(idx, device_regions, n, r, /*regions_on_device=*/true, nullptr, /*allow_async=*/true);
+  });
 }
 
 int vs_query_expand_site_ranges(vs_index* idx, const void* device_records, uint64_t n, vs_result** out) {
-  if (!idx || !out || (n && !device_records)) return fail(VS_ERR_ARG, "null argument");
-  if (idx->device < 0) return fail(VS_ERR_NO_DEVICE, "index handle was opened without a device; queries run on the GPU only");
-  HIP_TRY(hipSetDevice(idx->device));
-  vs_result* r = new vs_result();
-  r->idx = idx;
-  idx->live_results++;
-  const int rc = run_type6(idx, nullptr, n, r, false, (const uint64_t*)device_records, /*allow_async=*/false);
-  if (rc != VS_OK) return drop_result(r, rc);
-  *out = r;
-  return VS_OK;
+  if (n && !device_records) return fail(VS_ERR_ARG, "null argument");
+  return make_result(idx, 0, out, [&](vs_result* r) {
+    return run_type6(idx, nullptr, n, r, false, (const uint64_t*)device_records, /*allow_async=*/false);
+  });
 }
 
 int vs_query_sample_var_in_ref(vs_index* idx, const vs_region* regions, uint64_t n, uint32_t sample_id, vs_result** out) {
-  if (!idx || !out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
-  if (idx->device < 0) return fail(VS_ERR_NO_DEVICE, "index handle was opened without a device; queries run on the GPU only");
+  if (!out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
+  VS_TRY(query_handle(idx));
   if (sample_id >= idx->g.num_samples) return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u out of range (%u samples)", sample_id, idx->g.num_samples);
-  HIP_TRY(hipSetDevice(idx->device));
-  vs_result* r = new vs_result();
-  r->idx = idx;
-  idx->live_results++;
-  int rc = run_walk_batch(idx, regions, n, r, sample_id, nullptr, 4);
-  if (rc != VS_OK) return drop_result(r, rc);
-  *out = r;
+  return make_result(idx, 0, out, [&](vs_result* r) { return run_walk_batch(idx, regions, n, r, sample_id, nullptr, 4); });
+}
+
+// the argument checks of a batch with one sample per region
+static int check_sample_batch(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, vs_result** out,
+                              bool need_index) {
+  if (!out || (n && (!regions || !sample_ids))) return fail(VS_ERR_ARG, "null argument");
+  VS_TRY(query_handle(idx));
+  VS_TRY(check_host_ids(idx, sample_ids, n));
+  if (need_index && !idx->d.has_car_index)
+    return fail(VS_ERR_ARG, "this index holds no sample coordinates (built without them); query types 2, 3 and 5 need them");
   return VS_OK;
 }
 
 int vs_query_samples_var_in_ref(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids,
                                 vs_result** out) {
-  if (!idx || !out || (n && (!regions || !sample_ids))) return fail(VS_ERR_ARG, "null argument");
-  if (idx->device < 0) return fail(VS_ERR_NO_DEVICE, "index handle was opened without a device; queries run on the GPU only");
-  HIP_TRY(hipSetDevice(idx->device));
-  VS_TRY(check_host_ids(idx, sample_ids, n));
-  vs_result* r = new vs_result();
-  r->idx = idx;
-  idx->live_results++;
-  int rc = run_walk_batch(idx, regions, n, r, kNone, sample_ids, 4);
-  if (rc != VS_OK) return drop_result(r, rc);
-  *out = r;
-  return VS_OK;
+  VS_TRY(check_sample_batch(idx, regions, n, sample_ids, out, false));
+  return make_result(idx, 0, out, [&](vs_result* r) { return run_walk_batch(idx, regions, n, r, kNone, sample_ids, 4); });
 }
 
 static int run_point_batch(vs_index* idx, const uint64_t* positions, uint64_t n, uint32_t mode, const PointStrings* strings,
                            vs_result** out) {
-  if (idx->device < 0) return fail(VS_ERR_NO_DEVICE, "index handle was opened without a device; queries run on the GPU only");
-  HIP_TRY(hipSetDevice(idx->device));
-  std::vector<vs_region> regions(n);
-  for (uint64_t i = 0; i < n; ++i) regions[i] = vs_region{positions[i], 0};
-  vs_result* r = new vs_result();
-  r->idx = idx;
-  r->kind = mode == 7 ? 7 : 0;
-  idx->live_results++;
-  int rc = run_private_batch(idx, regions.data(), n, r, false, nullptr, mode, strings, false);
-  if (rc != VS_OK) return drop_result(r, rc);
-  *out = r;
-  return VS_OK;
+  return make_result(idx, mode == 7 ? 7 : 0, out, [&](vs_result* r) {
+    std::vector<vs_region> regions(n);
+    for (uint64_t i = 0; i < n; ++i) regions[i] = vs_region{positions[i], 0};
+    return run_private_batch(idx, regions.data(), n, r, false, nullptr, mode, strings, false);
+  });
 }
 
 int vs_query_closest_var(vs_index* idx, const uint64_t* positions, uint64_t n, vs_result** out) {
@@ -2782,48 +2779,22 @@ int vs_query_samples_has_var(vs_index* idx, const uint64_t* positions, const cha
   return run_point_batch(idx, positions, n, 7, &ps, out);
 }
 
-static int check_sample_batch(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, vs_result** out,
-                              bool need_index) {
-  if (!idx || !out || (n && (!regions || !sample_ids))) return fail(VS_ERR_ARG, "null argument");
-  if (idx->device < 0) return fail(VS_ERR_NO_DEVICE, "index handle was opened without a device; queries run on the GPU only");
-  HIP_TRY(hipSetDevice(idx->device));
-  VS_TRY(check_host_ids(idx, sample_ids, n));
-  if (need_index && !idx->d.has_car_index)
-    return fail(VS_ERR_ARG, "this index holds no sample coordinates (built without them); query types 2, 3 and 5 need them");
-  return VS_OK;
-}
-
 int vs_query_sample_seq(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, int sample_coordinates,
                         vs_result** out) {
   VS_TRY(check_sample_batch(idx, regions, n, sample_ids, out, true));
-  HIP_TRY(hipSetDevice(idx->device));
-  vs_result* r = new vs_result();
-  r->idx = idx;
-  r->kind = sample_coordinates ? 3 : 2;
-  idx->live_results++;
-  int rc = run_sample_seq(idx, regions, n, sample_ids, r->kind, r);
-  if (rc != VS_OK) return drop_result(r, rc);
-  *out = r;
-  return VS_OK;
+  const int kind = sample_coordinates ? 3 : 2;
+  return make_result(idx, kind, out, [&](vs_result* r) { return run_sample_seq(idx, regions, n, sample_ids, kind, r); });
 }
 
 int vs_query_sample_var_in_sample(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, vs_result** out) {
   VS_TRY(check_sample_batch(idx, regions, n, sample_ids, out, true));
-  HIP_TRY(hipSetDevice(idx->device));
-  vs_result* r = new vs_result();
-  r->idx = idx;
-  idx->live_results++;
   static const uint32_t none = 0;
-  int rc = run_walk_batch(idx, regions, n, r, kNone, n ? sample_ids : &none, 5);
-  if (rc != VS_OK) return drop_result(r, rc);
-  *out = r;
-  return VS_OK;
+  return make_result(idx, 0, out, [&](vs_result* r) { return run_walk_batch(idx, regions, n, r, kNone, n ? sample_ids : &none, 5); });
 }
 
 int vs_result_get_sequences(vs_result* r, uint64_t* n_regions, const uint8_t** region_flags, const uint64_t** seq_begin,
                             const char** chars) {
-  if (!r) return fail(VS_ERR_ARG, "null argument");
-  if (r->kind != 2 && r->kind != 3) return fail(VS_ERR_ARG, "not a sequence result");
+  VS_TRY(result_enter(r, Want::Sequences, true));
   VS_TRY(fetch_sequences(r));
   if (n_regions) *n_regions = r->sq.Q;
   if (region_flags) *region_flags = r->h_flags.data();
@@ -2871,9 +2842,9 @@ int vs_index_find(vs_index* idx, const uint64_t* pos, uint64_t n, uint32_t* vert
 }
 
 // ---------------------------------------------------------------- result access
-// Start (stream) the raw copy of a result: rows and -- on request -- the arena go into one page-locked block.
+// Start (stream) the raw copy of a result: rows and -- on request -- the arena go into one page-locked block.  (The caller has passed
+// the gate.)
 static int raw_copy_begin(vs_result* r, bool with_carriers, hipStream_t stream) {
-  VS_TRY(result_sizes(r));
   vs_index* idx = r->idx;
   const DevResult& d = r->d;
   const size_t row_bytes = (size_t)d.A * sizeof(VariantRow), arena_bytes = with_carriers && !r->resident ? (size_t)d.S * d.car_width : 0;
@@ -2909,11 +2880,10 @@ static void fill_raw(vs_result* r, vs_result_raw* raw) {
 }
 
 int vs_result_get_raw(vs_result* r, int with_carriers, vs_result_raw* raw) {
-  if (r) { VS_NOT_SEQ(r); }
-  if (!r || !raw) return fail(VS_ERR_ARG, "null argument");
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!raw) return fail(VS_ERR_ARG, "null argument");
   static_assert(sizeof(vs_variant_row) == sizeof(VariantRow), "row layout of the ABI");
   vs_index* idx = r->idx;
-  HIP_TRY(hipSetDevice(idx->device));
   VS_TRY(raw_copy_begin(r, with_carriers != 0, idx->stream));
   VS_TRY(fetch_region_meta(r));   // (synchronises the stream)
   HIP_TRY(hipStreamSynchronize(idx->stream));
@@ -2927,8 +2897,8 @@ int vs_result_get_raw(vs_result* r, int with_carriers, vs_result_raw* raw) {
 // chunks to share rows and lists (each chunk is a batch of its own).
 int vs_query_var_in_ref_stream(vs_index* idx, const vs_region* regions, uint64_t n, uint64_t chunk_regions, int with_carriers,
                                vs_chunk_fn fn, void* user) {
-  if (!idx || (n && !regions) || !fn) return fail(VS_ERR_ARG, "null argument");
-  if (idx->device < 0) return fail(VS_ERR_NO_DEVICE, "index handle was opened without a device; queries run on the GPU only");
+  if ((n && !regions) || !fn) return fail(VS_ERR_ARG, "null argument");
+  VS_TRY(query_handle(idx));
   if (chunk_regions == 0) return fail(VS_ERR_ARG, "chunk_regions must be positive");
   HIP_TRY(hipSetDevice(idx->device));
   if (!idx->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&idx->copy_stream, hipStreamNonBlocking));
@@ -2950,9 +2920,7 @@ int vs_query_var_in_ref_stream(vs_index* idx, const vs_region* regions, uint64_t
   };
   for (uint64_t first = 0; first < n && rc == VS_OK; first += chunk_regions) {
     const uint64_t cn = std::min<uint64_t>(chunk_regions, n - first);
-    vs_result* r = new vs_result();
-    r->idx = idx;
-    idx->live_results++;
+    vs_result* r = new_result(idx, 0);   // (never speculative, and on the handle's device: the chunk's helpers below need no gate)
     rc = run_type6(idx, regions + first, cn, r, false, nullptr, /*allow_async=*/false);   // (returns with the chunk's kernels complete; the previous chunk's copy ran beside them)
     if (rc == VS_OK) rc = fetch_region_meta(r);
     if (rc != VS_OK) { drop_result(r, rc); break; }
@@ -2968,15 +2936,14 @@ int vs_query_var_in_ref_stream(vs_index* idx, const vs_region* regions, uint64_t
 }
 
 int vs_result_get_view(vs_result* r, int with_carriers, vs_result_view* view) {
-  if (r) { VS_NOT_SEQ(r); }
-  if (!r || !view) return fail(VS_ERR_ARG, "null argument");
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!view) return fail(VS_ERR_ARG, "null argument");
   VS_TRY(fetch_headers(r));
   if (with_carriers && !r->have_carriers) {
     // the arena pads every variant's range; the view packs the lists back to back
     r->h_carriers.resize(r->n_view_carriers);
     const uint64_t ns = r->h_view_begin[r->d.Q];
     if (r->resident) {   // from the handle's mirror of the resident arena
-      HIP_TRY(hipSetDevice(r->idx->device));
       VS_TRY(ensure_resident_mirror(r->idx));
       const uint16_t* m16 = (const uint16_t*)r->idx->res_mirror;
       const uint32_t* m32 = (const uint32_t*)r->idx->res_mirror;
@@ -3014,7 +2981,7 @@ int vs_result_get_view(vs_result* r, int with_carriers, vs_result_view* view) {
 
 int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_variants, uint64_t* n_carriers, uint64_t* n_bases) {
   vs_result* r = const_cast<vs_result*>(cr);
-  if (!r) return fail(VS_ERR_ARG, "null argument");
+  VS_TRY(result_enter(r, Want::Any, true));
   if (r->kind == 2 || r->kind == 3) {  // sequences: only regions and bases
     if (n_regions) *n_regions = r->sq.Q;
     if (n_variants) *n_variants = 0;
@@ -3024,8 +2991,6 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
   }
   if (!r->have_totals) {   // reduced on the device: nothing but three words crosses PCIe
     vs_index* idx = r->idx;
-    HIP_TRY(hipSetDevice(idx->device));
-    VS_TRY(result_sizes(r));
     ScratchBufs tmp(idx);
     void* dt = nullptr;
     VS_TRY(dev_alloc(idx, 24, &dt, &tmp.bufs));
@@ -3048,8 +3013,8 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
 }
 
 int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_t* len) {
-  if (!r || !text) return fail(VS_ERR_ARG, "null argument");
-  VS_TRY(result_sizes(r));
+  VS_TRY(result_enter(r, Want::Any, true));
+  if (!text) return fail(VS_ERR_ARG, "null argument");
   if (r->kind == 2 || r->kind == 3) {  // `out << seq << std::endl`, query.h:182-187 / :252-257
     VS_TRY(fetch_sequences(r));
     if (q >= r->sq.Q) return fail(VS_ERR_ARG, "region %llu out of range", (unsigned long long)q);
@@ -3070,7 +3035,6 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
   const uint32_t* car = nullptr;
   const bool from_view = r->have_carriers;
   if (!from_view && r->scattered_lists && !(r->raw_rows && r->raw_arena)) {   // lists all over the arena: bring it over once
-    HIP_TRY(hipSetDevice(idx->device));
     VS_TRY(raw_copy_begin(r, true, idx->stream));
     HIP_TRY(hipStreamSynchronize(idx->stream));
   }
@@ -3158,18 +3122,15 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
 /* Duration of the result's carrier expansion by HIP events on the stream it ran on, when it ran asynchronously (option
  * "async_fill"; waits for it); -1 otherwise (vs_index_last_timing().ms_fill has it then). */
 int vs_result_fill_ms(vs_result* r, float* ms) {
-  if (!r || !ms) return fail(VS_ERR_ARG, "null argument");
-  if (r->idx && r->idx->device >= 0) HIP_TRY(hipSetDevice(r->idx->device));
-  VS_TRY(result_sizes(r));   // (a refused speculative batch is run now: the time asked for is that of the expansion that produced the result)
+  VS_TRY(result_enter(r, Want::Any, true));   // (a refused speculative batch is run now: the time asked for is that of the expansion that produced the result)
+  if (!ms) return fail(VS_ERR_ARG, "null argument");
   VS_TRY(result_ready(r));
   *ms = r->fill_ms;
   return VS_OK;
 }
 
 int vs_result_layout(const vs_result* r, uint64_t* n_slots, uint64_t* table_rows, uint64_t* arena_entries, uint64_t* lists_expanded, int* shared) {
-  if (!r) return fail(VS_ERR_ARG, "null argument");
-  VS_NOT_SEQ(r);
-  if (r->sizes_pending) { if (r->idx && r->idx->device >= 0) HIP_TRY(hipSetDevice(r->idx->device)); VS_TRY(result_sizes(const_cast<vs_result*>(r))); }
+  VS_TRY(result_enter(const_cast<vs_result*>(r), Want::Variants, true));
   if (n_slots) *n_slots = r->n_rows_reported;
   if (table_rows) *table_rows = r->d.A;
   if (arena_entries) *arena_entries = r->resident ? 0 : r->d.S;   // (a result over resident lists owns no arena)
@@ -3179,11 +3140,9 @@ int vs_result_layout(const vs_result* r, uint64_t* n_slots, uint64_t* table_rows
 }
 
 int vs_result_digest(vs_result* r, uint64_t* digest) {
-  if (!r || !digest) return fail(VS_ERR_ARG, "null argument");
-  VS_NOT_SEQ(r);
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!digest) return fail(VS_ERR_ARG, "null argument");
   vs_index* idx = r->idx;
-  HIP_TRY(hipSetDevice(idx->device));
-  VS_TRY(result_sizes(r));
   VS_TRY(result_ready(r));
   ScratchBufs tmp(idx);
   void* dd = nullptr;
@@ -3205,15 +3164,12 @@ int vs_result_digest(vs_result* r, uint64_t* digest) {
 
 int vs_result_pack_headers(vs_result* r, void* device_dst, uint64_t capacity_records, uint64_t region_base,
                            uint64_t* n_records) {
-  if (!r) return fail(VS_ERR_ARG, "null argument");
-  VS_NOT_SEQ(r);
-  if (r->sizes_pending) { HIP_TRY(hipSetDevice(r->idx->device)); VS_TRY(result_sizes(r)); }
+  VS_TRY(result_enter(r, Want::Variants, true));
   if (n_records) *n_records = r->n_rows_reported;   // rows over all regions (a shared row once per region reporting it)
   if (!device_dst) return VS_OK;  // size query
   if (capacity_records < r->n_rows_reported) return fail(VS_ERR_ARG, "destination holds %llu records, %llu needed",
                                                         (unsigned long long)capacity_records, (unsigned long long)r->n_rows_reported);
   vs_index* idx = r->idx;
-  HIP_TRY(hipSetDevice(idx->device));
   if (r->d.Q) {
     ScratchBufs tmp(idx);
     uint64_t* slot_begin = nullptr;
@@ -3231,14 +3187,13 @@ int vs_result_pack_headers(vs_result* r, void* device_dst, uint64_t capacity_rec
 
 int vs_result_pack_regions(vs_result* r, void* device_dst, uint64_t capacity_records, uint64_t region_base,
                            uint64_t* n_records) {
-  if (!r) return fail(VS_ERR_ARG, "null argument");
+  // (a size query: the region count is known -- a refused batch is redone before its records travel, not before)
+  VS_TRY(result_enter(r, Want::Any, /*sizes=*/device_dst != nullptr));
   if (n_records) *n_records = r->d.Q;
   if (!device_dst) return VS_OK;
-  if (r->sizes_pending) { HIP_TRY(hipSetDevice(r->idx->device)); VS_TRY(result_sizes(r)); }   // (a refused batch is redone before its records travel)
   if (capacity_records < r->d.Q) return fail(VS_ERR_ARG, "destination holds %llu records, %llu needed",
                                              (unsigned long long)capacity_records, (unsigned long long)r->d.Q);
   vs_index* idx = r->idx;
-  HIP_TRY(hipSetDevice(idx->device));
   VS_TRY(launch_pack_regions(r, (uint64_t*)device_dst, region_base));
   HIP_TRY(hipStreamSynchronize(idx->stream));
   return VS_OK;
