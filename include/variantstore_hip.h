@@ -170,6 +170,34 @@ int vs_query_sample_seq(vs_index* idx, const vs_region* regions, uint64_t n, con
  * of sample_ids[i] over regions[i] in the SAMPLE's coordinates; an ordinary variant-table result.  var_pos follows the
  * reference: the sample-coordinate index for substitutions and deletions, the reference index for insertions. */
 int vs_query_sample_var_in_sample(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, vs_result** out);
+/* Allele counts over regions, optionally for a subset S of the samples (no reference counterpart: what a caller of type 6
+ * would count on the host from the carrier lists).  Each region reports the rows type 6 reports -- same positions, REF / ALT,
+ * order, duplicate rule (dropped rows flagged as in vs_result_raw) and region flags -- and each row carries, instead of a
+ * carrier list, four counts over its carriers c that lie in S.  They come from the genotype bits the index stores per carrier
+ * (VS_CARRIER_GT: bit 0 phase, bit 1 gt_1, bit 2 gt_2), not from the VCF's allele indices: the constructor sets gt_1 / gt_2 for
+ * ANY allele > 0, so a `1|2` call counts 2 alternate alleles on both of its ALT rows, and a haploid `1` counts as gt_1 alone.
+ *   carriers    = |{c in S}|
+ *   alt_alleles = sum over c in S of gt_1 + gt_2
+ *   hom_alt     = |{c in S : gt_1 && gt_2}|
+ *   phased      = |{c in S : phase}|
+ * A dropped row counts 0. */
+typedef struct { uint32_t carriers, alt_alleles, hom_alt, phased; } vs_allele_counts;
+/* `regions` may lie in host memory or in DEVICE memory of the handle's GPU (the engine asks the runtime which); n >= 1.
+ * sample_ids == NULL: the whole cohort (every sample but "ref"); else a HOST array of n_ids >= 1 index sample ids, taken as a set
+ * (duplicates count once) -- id 0 ("ref") or an id >= num_samples fails with VS_ERR_UNKNOWN_SAMPLE, n_ids == 0 with VS_ERR_ARG.
+ * Every batch size takes the batch pipeline: the type-6 plan and shared rows, then one counting kernel instead of the carrier
+ * expansion (never speculative; the handle's type-6 state -- vs_index_info.t6_speculated / t6_refused, size and sort hints -- is
+ * left as it was).  The result has the variant table of type 6 and no carrier arena: vs_result_get_raw / vs_result_get_view
+ * with with_carriers = 0, vs_result_totals (n_carriers = the sum of `carriers` over the reported rows), vs_result_layout (arena
+ * and lists 0), vs_result_fill_ms (the counting kernel) and vs_result_format_region
+ * ("Pos\tRef\tAlt\tCarriers\tAC\tHomAlt\tPhased\n", then one line per reported row) work; with_carriers = 1, vs_result_digest,
+ * vs_result_pack_headers / _pack_regions and vs_comm_allgather_regions* fail with VS_ERR_UNSUPPORTED. */
+int vs_query_allele_counts(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids,
+                           vs_result** out);
+/* The counts of an allele-count result, copied into page-locked memory owned by the result: counts[i] belongs to
+ * vs_result_raw.rows[i] (table order), so region q's are counts[row_begin[q] .. row_begin[q] + row_count[q]). */
+int vs_result_get_allele_counts(vs_result* r, uint64_t* n_rows, const vs_allele_counts** counts);
+
 /* host view of a sequence result: region i is chars[seq_begin[i] .. seq_begin[i+1]) */
 int vs_result_get_sequences(vs_result* r, uint64_t* n_regions, const uint8_t** region_flags, const uint64_t** seq_begin,
                             const char** chars);

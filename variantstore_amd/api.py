@@ -72,6 +72,7 @@ class QueryResult:
         self._store = store
         self._h = handle
         self._lib = store._lib
+        self.subset_size = 0   # allele-count results: |S|, the samples the counts are over (region_counts' af)
 
     def close(self):
         if self._h:
@@ -204,6 +205,36 @@ class QueryResult:
         n = C.c_uint64()
         _check(self._lib.vs_result_format_region(self._h, q, C.byref(txt), C.byref(n)), "vs_result_format_region")
         return C.string_at(txt, n.value).decode("latin-1")
+
+    COUNT_DTYPE = np.dtype([("carriers", "<u4"), ("alt_alleles", "<u4"), ("hom_alt", "<u4"), ("phased", "<u4")])
+
+    def allele_counts(self):
+        """An allele-count result (VariantStore.allele_counts) as numpy arrays: the variant table's `rows` and their `counts`
+        (structured: carriers, alt_alleles, hom_alt, phased; counts[i] belongs to rows[i]), and per region `row_begin`,
+        `row_count` and `flags` -- region q reports rows[row_begin[q] : row_begin[q] + row_count[q]].  Copies, valid after
+        the result is closed."""
+        raw = self.raw(with_carriers=False)
+        n = C.c_uint64()
+        p = C.POINTER(_lib.AlleleCounts)()
+        _check(self._lib.vs_result_get_allele_counts(self._h, C.byref(n), C.byref(p)), "vs_result_get_allele_counts")
+        a = int(n.value)
+        counts = (np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(a * 16,)).view(self.COUNT_DTYPE).copy()
+                  if a else np.zeros(0, self.COUNT_DTYPE))
+        return {"rows": raw["rows"].copy(), "counts": counts, "row_begin": raw["row_begin"].copy(),
+                "row_count": raw["row_count"].copy(), "flags": raw["region_flags"].copy()}
+
+    def region_counts(self, q):
+        """The rows region q reports (dropped ones left out) with their counts: a list of dicts with pos, ref, alt, carriers,
+        alt_alleles, hom_alt, phased and af = alt_alleles / (2 |S|), S the subset the query was made for."""
+        out = []
+        for line in self.region_text(q).split("\n")[1:]:
+            if not line:
+                continue
+            pos, ref, alt, car, ac, hom, ph = line.split("\t")
+            ac = int(ac)
+            out.append({"pos": int(pos), "ref": ref, "alt": alt, "carriers": int(car), "alt_alleles": ac, "hom_alt": int(hom),
+                        "phased": int(ph), "af": ac / (2.0 * self.subset_size) if self.subset_size else 0.0})
+        return out
 
     def region_variants(self, q) -> List[Variant]:
         out = []
@@ -413,6 +444,31 @@ class VariantStore:
         _check(self._lib.vs_query_expand_site_ranges(self._h, C.c_void_p(int(device_ptr)), int(n), C.byref(h)),
                "vs_query_expand_site_ranges")
         return QueryResult(self, h)
+
+    def allele_counts(self, regions, samples=None) -> QueryResult:
+        """Allele counts over regions (vs_query_allele_counts): the rows type 6 reports, each with carriers, alt_alleles,
+        hom_alt and phased over the samples in `samples` (names or ids, taken as a set; None: the whole cohort).  `regions`:
+        (pos_x, pos_y) pairs as a list or an array, or a DeviceArray of them in this GPU's memory.  Read the result with
+        QueryResult.allele_counts / region_counts / region_text."""
+        arr, ptr, n = _regions_array(regions)
+        h = C.c_void_p()
+        if samples is None:
+            ids, ids_ptr, n_ids = None, None, 0
+            if getattr(self, "_cohort", None) is None:   # (vs_index_get_info asks the device for its free memory: once per handle)
+                self._cohort = self.info().num_samples - 1
+            subset = self._cohort
+        else:
+            if isinstance(samples, (str, bytes)):
+                samples = [samples]
+            ids = np.ascontiguousarray([self.sample_id(x) if isinstance(x, str) else int(x) for x in samples], dtype=np.uint32)
+            ids_ptr, n_ids = ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.shape[0]
+            if n_ids == 0:   # (the C ABI's NULL-or-non-empty rule: an empty list is not the whole cohort)
+                ids_ptr = (C.c_uint32 * 1)()
+            subset = len(set(ids.tolist()))
+        _check(self._lib.vs_query_allele_counts(self._h, ptr, n, ids_ptr, n_ids, C.byref(h)), "vs_query_allele_counts")
+        res = QueryResult(self, h)
+        res.subset_size = subset
+        return res
 
     def get_sample_var_in_ref(self, regions, sample) -> QueryResult:
         """Query type 4 for one sample over a batch of regions (query.h:618-729)."""

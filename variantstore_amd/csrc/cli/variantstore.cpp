@@ -110,7 +110,7 @@ bool dir_exists(const std::string& p) {
 }
 
 struct Args {
-  std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out;
+  std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out, samples_file;
   uint32_t type = 0, mode = 0;
   uint64_t hops = 0;
   bool have_hops = false;
@@ -673,6 +673,61 @@ int query_main(const Args& a) {
   return EXIT_SUCCESS;
 }
 
+// `variantstore counts`: allele counts over the regions (vs_query_allele_counts), for the whole cohort or the samples named in
+// the -S file (one name per line).  Every region's text ("Pos Ref Alt Carriers AC HomAlt Phased") goes to -o (stdout without it),
+// with a "#region <i> <x>:<y>" line before it, as --batch-out writes type 6.
+int counts_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore counts -p <output-prefix> -r <region> [-S <sample-name-file>] [-o <outfile>] [--device <n>]\n\n"
+               "        Allele counts (carriers, alternate alleles, homozygous-alternate and phased carriers) of the variants\n"
+               "        query type 6 reports in each region, over the whole cohort or over the samples named in the file.\n";
+  return EXIT_FAILURE;
+}
+
+int counts_main(const Args& a) {
+  vs_index* idx = nullptr;
+  int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
+  if (rc != VS_OK) die(rc, "load");
+  std::vector<uint32_t> ids;
+  if (!a.samples_file.empty()) {
+    std::ifstream in(a.samples_file);
+    if (!in) { error("cannot open sample file " + a.samples_file); vs_index_close(idx); return EXIT_FAILURE; }
+    std::string line;
+    while (std::getline(in, line)) {
+      if (!line.empty() && line.back() == '\r') line.pop_back();
+      if (line.empty()) continue;
+      uint32_t sid = 0;
+      if (vs_index_sample_id(idx, line.c_str(), &sid) != VS_OK || sid == 0) {
+        error("Sample not found: " + line);
+        vs_index_close(idx);
+        return EXIT_FAILURE;
+      }
+      ids.push_back(sid);
+    }
+    if (ids.empty()) { error("no sample names in " + a.samples_file); vs_index_close(idx); return EXIT_FAILURE; }
+  }
+  std::vector<vs_region> batch;
+  for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
+  vs_result* res = nullptr;
+  rc = vs_query_allele_counts(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
+  if (rc != VS_OK) die(rc, "counts");
+  std::ofstream file;
+  if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
+  std::ostream& out = a.outfile.empty() ? std::cout : file;
+  for (size_t i = 0; i < batch.size(); ++i) {
+    const char* text = nullptr;
+    uint64_t len = 0;
+    rc = vs_result_format_region(res, i, &text, &len);
+    if (rc != VS_OK) die(rc, "result");
+    out << "#region " << i << " " << batch[i].x << ":" << batch[i].y << "\n";
+    out.write(text, len);
+  }
+  out.flush();
+  vs_result_free(res);
+  vs_index_close(idx);
+  return EXIT_SUCCESS;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -713,7 +768,18 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
+    } else if (a.cmd == "counts") {
+      if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
+      else if (f == "-r" || f == "--region") a.region = need(i);
+      else if (f == "-S" || f == "--samples") a.samples_file = need(i);
+      else if (f == "-o" || f == "--output_file") a.outfile = need(i);
+      else if (f == "--device") a.device = atoi(need(i).c_str());
+      else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
     }
+  }
+  if (a.cmd == "counts") {
+    if (a.prefix.empty() || a.region.empty()) return counts_usage();
+    return counts_main(a);
   }
   if (a.cmd == "construct") {
     if (a.ref.empty() || a.vcf.empty() || a.prefix.empty()) return usage();

@@ -231,7 +231,10 @@ struct vs_result {
   std::vector<DevBuf> old_pins;   // earlier raw copies of this result (rows only, then rows + carriers): pointers handed out stay valid until it is freed
   const VariantRow* raw_rows = nullptr;
   const uint8_t* raw_arena = nullptr;   // NULL: carriers not copied
-  int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences
+  int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts
+  // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
+  uint4* d_counts = nullptr;
+  DevBuf counts_pin{nullptr, 0};
   // sequence results (query types 2 and 3)
   DevSeqResult sq{};
   uint64_t seq_bytes = 0;
@@ -239,6 +242,11 @@ struct vs_result {
   std::vector<uint64_t> h_byte_begin;
   std::vector<uint8_t> h_chars;
 };
+
+constexpr int kKindCounts = 8;   // vs_result::kind of an allele-count result: the rows of type 6, counts instead of carrier lists
+static int refuse_counts(const char* what) {
+  return fail(VS_ERR_UNSUPPORTED, "%s: an allele-count result holds counts per row, no carrier lists (vs_result_get_allele_counts)", what);
+}
 
 // ------------------------------------------------------------------ helpers
 static int server_stop(vs_index* idx);   // the resident latency server must be gone before anything that synchronises the
@@ -1076,8 +1084,9 @@ static int capture_totals(vs_result* r) {
   else { idx->sort_hint = true; idx->sort_probe_in = 32; }   // (as after a batch that was sorted on the device: the next ones sort first -- also when nobody reads this one)
   return VS_OK;
 }
+struct CountReq { const uint64_t* mask; uint32_t words; };   // an allele-count batch: the subset's bit mask in host memory (NULL: the whole cohort)
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
-                            bool allow_async, bool may_speculate);
+                            bool allow_async, bool may_speculate = true, const CountReq* counting = nullptr);
 // A speculative batch's sizes become the plan's totals here -- or, when the plan refused the batch on the device (more rows or arena
 // entries than were allocated, or regions that were not sorted), the batch is run again from the result's own copy of the regions,
 // with the exact sizes, before anything is read.  A redo that fails leaves the result torn: its code sticks (vs_result::redo_rc).
@@ -1168,18 +1177,24 @@ static void launch_fill2(vs_index* idx, const DevResult& d, const RunRec* runs, 
 //   fill   k_fill_sites2: the shared rows AND their carrier lists, one launch; with resident lists k_share_rows2 alone;
 //          with async_fill k_share_rows2 here and k_fill_sites on the second stream
 //   done   k_post_done: a word in mapped host memory, the host spins on it
+//   counts (an allele-count batch, `counting`: vs_query_allele_counts) instead of the expansion: k_share_rows2 with the site of every
+//          row, k_count_slow_sites for the private rows, k_allele_counts.  Never speculative, no arena, and it leaves the handle's
+//          type-6 state (size hints, sort hint) as it found it: count batches interleaved with type-6 batches change none of theirs
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
-                            bool allow_async, bool may_speculate = true) {
+                            bool allow_async, bool may_speculate, const CountReq* counting) {
   VS_TRY(begin_batch(idx));
   DevResult& d = r->d;
   d.Q = n;
   uint64_t* dreg = nullptr;
+  uint64_t* d_mask = nullptr;   // (an allele-count batch over a subset: its bit mask, copied with the regions)
   {   // the per-region arrays of the result: one buffer
     Slab sl;
     const size_t o_reg = sl.add(2 * n * 8), o_fl = sl.add(n * sizeof(*d.q_flags)), o_g0 = sl.add(n * sizeof(*d.q_g0)), o_nv = sl.add(n * sizeof(*d.q_nvar)),
                  o_nc = sl.add(n * sizeof(*d.q_ncar)), o_vb = sl.add((n + 1) * sizeof(*d.var_begin)), o_cb = sl.add((n + 1) * sizeof(*d.car_base)),
-                 o_vc = sl.add(n * sizeof(*d.var_count)), o_cl = sl.add(n * sizeof(*d.q_car_len));
+                 o_vc = sl.add(n * sizeof(*d.var_count)), o_cl = sl.add(n * sizeof(*d.q_car_len)),
+                 o_mk = sl.add(counting && counting->mask ? (size_t)counting->words * 8 : 0);
     VS_TRY(ralloc(r, sl.bytes, &sl.base));
+    if (counting && counting->mask) d_mask = sl.at<uint64_t>(o_mk);
     dreg = sl.at<uint64_t>(o_reg);
     d.q_flags = sl.at<std::remove_pointer_t<decltype(d.q_flags)>>(o_fl); d.q_g0 = sl.at<std::remove_pointer_t<decltype(d.q_g0)>>(o_g0);
     d.q_nvar = sl.at<std::remove_pointer_t<decltype(d.q_nvar)>>(o_nv); d.q_ncar = sl.at<std::remove_pointer_t<decltype(d.q_ncar)>>(o_nc);
@@ -1194,7 +1209,8 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   // rest of the batch (rows, expansion) goes to the handle's stream behind an event.  Not for a handle that sorts first,
   // not with async_fill (whose second stream plays the opposite game).
   const bool async_submit = allow_async && idx->opts.async_submit && !idx->opts.async_fill && !idx->opts.lat_debug;
-  bool plan_aside = async_submit && !(idx->sort_hint && idx->sort_probe_in > 0);
+  const bool sort_first = !counting && idx->sort_hint && idx->sort_probe_in > 0;
+  bool plan_aside = async_submit && !sort_first;
   if (plan_aside) VS_TRY(ensure_plan_stream(idx));
   hipStream_t ps = plan_aside ? idx->plan_stream : idx->stream;
   // (regions already in device memory are copied by the kernel that reads them first: k_t6_bounds)
@@ -1203,9 +1219,10 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   if (regions_dev) {}
   else if (regions) HIP_TRY(hipMemcpyAsync(dreg, regions, n * 16, regions_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ps));
   else HIP_TRY(hipMemsetAsync(dreg, 0, n * 16, ps));
+  if (d_mask) HIP_TRY(hipMemcpyAsync(d_mask, counting->mask, (size_t)counting->words * 8, hipMemcpyHostToDevice, ps));
   HIP_TRY(hipEventRecord(idx->ev[0], ps));
   ScratchBufs scratch(idx);
-  const bool resident = idx->opts.resident_lists && idx->res_arena;
+  const bool resident = !counting && idx->opts.resident_lists && idx->res_arena;
   // ---- plan ----
   uint32_t items = (uint32_t)((n + (uint64_t)kPlanBlock * kPlanMaxTiles - 1) / ((uint64_t)kPlanBlock * kPlanMaxTiles));
   if (n >= 65536 && items < idx->opts.plan_items) items = idx->opts.plan_items;   // (regions per thread of the plan's kernels: see EngineOpts::plan_items)
@@ -1233,7 +1250,7 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   // batch (+ 1/8), k_t6_totals leaves the totals and its verdict in device memory for the kernels behind it (PlanDev) and in this batch's
   // own mailbox for the host, which reads it when the result is first asked for anything (result_sizes) -- and redoes a refused batch.
   const uint64_t want_rows = idx->t6_hint_rows, want_arena = idx->t6_hint_arena;
-  const bool spec = may_speculate && idx->opts.t6_speculate && plan_aside && regions && !site_records && !resident && idx->opts.fill_fused && !idx->opts.fill_mode &&
+  const bool spec = may_speculate && !counting && idx->opts.t6_speculate && plan_aside && regions && !site_records && !resident && idx->opts.fill_fused && !idx->opts.fill_mode &&
                     !idx->opts.fill_stats && !idx->opts.lat_debug && want_rows > 0 && idx->t6_hint_n > 0 && n * 4 <= idx->t6_hint_n * 5 && n * 5 >= idx->t6_hint_n * 4;
   int slot = -1;
   if (spec) {
@@ -1317,7 +1334,7 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   };
   const int src = site_records ? 1 : 0;
   // (a handle whose last batch needed sorting sorts first; it looks at the order as given again every 32nd batch)
-  if (idx->sort_hint && idx->sort_probe_in > 0) {
+  if (sort_first) {
     --idx->sort_probe_in;
     launch_bounds(src);
     VS_TRY(sort_batch());
@@ -1333,25 +1350,28 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
       }
       VS_TRY(sort_batch());
       VS_TRY(plan(2));
-      idx->sort_hint = true; idx->sort_probe_in = 32;
-    } else idx->sort_hint = false;
+      if (!counting) { idx->sort_hint = true; idx->sort_probe_in = 32; }
+    } else if (!counting) idx->sort_hint = false;
   }
   if (!spec && pt->not_sorted) return fail(VS_ERR_INTERNAL, "the batch is not sorted by first site after the device-side sort");
   if (!plan_end_enqueued) HIP_TRY(hipEventRecord(idx->ev[1], ps));   // (a plan on the handle's own stream: the phase boundary only)
   // (speculative: every size below is what was ALLOCATED -- an upper bound the launches are made for; the kernels take the real ones from PlanDev)
   const uint64_t U = spec ? want_rows : pt->shared_rows, n_slow = spec ? 0 : pt->n_slow, n_runs = spec ? 0 : pt->n_runs;
-  if (!spec) { d.A = pt->rows; d.S = pt->arena; }
+  if (!spec) { d.A = pt->rows; d.S = counting ? 0 : pt->arena; }
   r->n_rows_reported = spec ? 0 : pt->reported;
   if (spec) {
     r->sizes_pending = true; r->totals_captured = false; r->plan_slot = slot; r->plan_seq = plan_seq; r->cap_rows = want_rows; r->cap_arena = want_arena;
     idx->plan_slot_owner[slot] = r;
     idx->t6_speculated++;
-  } else t6_hint_update(idx, n, pt->rows, pt->arena);
+  } else if (!counting) t6_hint_update(idx, n, pt->rows, pt->arena);
   r->shared_lists = true;
   r->resident = resident;
   r->scattered_lists = false;
-  r->n_unique_sites = resident ? 0 : U;
-  if (!spec) {
+  r->n_unique_sites = resident || counting ? 0 : U;
+  if (counting) {
+    VS_TRY(ralloc(r, d.A, &d.rows));
+    VS_TRY(ralloc(r, d.A, &r->d_counts));
+  } else if (!spec) {
     VS_TRY(ralloc(r, d.A, &d.rows));
     if (resident) d.carriers = idx->res_arena;
     else {
@@ -1361,9 +1381,9 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
     }
   }
   // ---- shared rows + carrier lists: which form ----
-  const uint64_t n_fill = resident ? 0 : U;
+  const uint64_t n_fill = resident || counting ? 0 : U;
   const bool async_fill = allow_async && idx->opts.async_fill && n_fill > 0;
-  const bool fused = idx->opts.fill_fused && !resident && !async_fill;
+  const bool fused = idx->opts.fill_fused && !resident && !async_fill && !counting;
   // Every event on a stream is a packet the GPU works through (~3 us each): the default batch -- async_submit, rows and lists in one
   // launch, no permutation -- records TWO on the handle's stream, the result's own pair around the expansion, and its phase
   // times are read from those (round 3 recorded five per batch, and this round's completion event would have made it eight).
@@ -1377,11 +1397,29 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   // ---- shared rows + carrier lists ----
   uint32_t* u_site = nullptr;
   if (U && !fused) {
-    if (!resident) VS_TRY(dev_alloc(idx, U * 4 + 8, (void**)&u_site, &scratch.bufs));
+    if (!resident) VS_TRY(dev_alloc(idx, (counting ? d.A : U) * 4 + 8, (void**)&u_site, &scratch.bufs));   // (counts: the private rows' sites too)
     hipLaunchKernelGGL(k_share_rows2, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, idx->stream, idx->d, d, (const RunRec*)runs, (const uint32_t*)coarse, n_runs, U, u_site);
   }
   HIP_TRY(hipGetLastError());
   if (!lean) HIP_TRY(hipEventRecord(idx->ev[3], idx->stream));
+  if (counting && d.A) {
+    // the counts: the private rows' sites behind the shared ones, then one launch over the whole table between the result's own pair
+    // of events (vs_result_fill_ms)
+    if (n_slow) {
+      const uint64_t waves = std::min<uint64_t>(n_slow, 16384);
+      hipLaunchKernelGGL(k_count_slow_sites, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, idx->stream, d, (const uint32_t*)slow_list, n_slow, u_site);
+    }
+    VS_TRY(result_events(r));
+    HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
+    const unsigned blocks = (unsigned)((d.A + 4 * kCountRows - 1) / (4 * kCountRows));
+    if (d_mask) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_allele_counts<true>), dim3(blocks), dim3(256), (size_t)counting->words * 8, idx->stream, idx->d,
+                                   (const VariantRow*)d.rows, (const uint32_t*)u_site, d.A, U, (const uint64_t*)d_mask, counting->words, r->d_counts);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_allele_counts<false>), dim3(blocks), dim3(256), 0, idx->stream, idx->d,
+                            (const VariantRow*)d.rows, (const uint32_t*)u_site, d.A, U, (const uint64_t*)nullptr, 0u, r->d_counts);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
+    r->pending = true;
+  }
   if (async_fill) {
     // the expansion goes to the handle's second stream behind an event and the call returns once the FIRST stream is done
     // (rows, per-region arrays); the next batch's plan and rows then run beside it.  The call's temporaries (the site
@@ -1456,7 +1494,7 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
     idx->timing_owner = r;
   }
   idx->timing_pending = true;
-  idx->timing_fill_launches = n_fill ? 1 : 0;   // (async_fill: ms_fill is what the first stream saw of it, ~0; vs_result_fill_ms has the kernel's time)
+  idx->timing_fill_launches = (n_fill || (counting && d.A)) ? 1 : 0;   // (async_fill: ms_fill is what the first stream saw of it, ~0; vs_result_fill_ms has the kernel's time)
   // async_submit: the batch is enqueued, its sizes are known (the plan's totals; a speculative batch: result_sizes) and its buffers are the
   // result's -- the call returns here; the timing events are read when asked for
   if (async_submit) return batch_enqueued(r, scratch, /*record_done=*/!lean);
@@ -1702,6 +1740,14 @@ static int run_private_batch(vs_index* idx, const vs_region* regions, uint64_t n
 static int run_type6(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records, bool allow_async) {
   if (idx->opts.share_lists && n > 64) return run_type6_shared(idx, regions, n, r, regions_on_device, site_records, allow_async);
   return run_private_batch(idx, regions, n, r, regions_on_device, site_records, 0, nullptr, allow_async);
+}
+
+// Allele counts (vs_query_allele_counts): the plan and the shared rows of type 6, then k_allele_counts over the rows instead of the
+// expansion -- every batch size, never speculative, no arena (run_type6_shared: `counting`).  mask: a bit per sample of the subset,
+// empty for the whole cohort.
+static int run_counts_batch(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const std::vector<uint64_t>& mask) {
+  const CountReq cq{mask.empty() ? nullptr : mask.data(), (uint32_t)mask.size()};
+  return run_type6_shared(idx, regions, n, r, regions_on_device, nullptr, /*allow_async=*/true, /*may_speculate=*/false, &cq);
 }
 
 // lanes per region of the one-chain walks of query types 2, 3 and 5 (k_sample_walk_sc, k_sample_seq): 1, or kScGroup running the same chain
@@ -2679,6 +2725,7 @@ void vs_result_free(vs_result* r) {
     if (r->ev_done) { r->idx->ev_pool.push_back(r->ev_done); r->ev_done = nullptr; }
     release_bufs(r->idx, r->bufs);
     pin_release(r->idx, r->raw_pin);
+    pin_release(r->idx, r->counts_pin);
     for (auto& b : r->old_pins) pin_release(r->idx, b);
     r->idx->live_results--;
     if (r->idx->close_pending && r->idx->live_results == 0 && r->idx->live_comms == 0) vs_index_close(r->idx);
@@ -2721,6 +2768,27 @@ int vs_query_expand_site_ranges(vs_index* idx, const void* device_records, uint6
   if (n && !device_records) return fail(VS_ERR_ARG, "null argument");
   return make_result(idx, 0, out, [&](vs_result* r) {
     return run_type6(idx, nullptr, n, r, false, (const uint64_t*)device_records, /*allow_async=*/false);
+  });
+}
+
+int vs_query_allele_counts(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, vs_result** out) {
+  // (the arguments first: they are checked on the host, also on a handle opened without a device)
+  if (!idx || !out || (n && !regions) || (!sample_ids && n_ids)) return fail(VS_ERR_ARG, "null argument");
+  if (n == 0) return fail(VS_ERR_ARG, "an allele-count batch needs at least one region");
+  std::vector<uint64_t> mask;   // the subset as a bit per sample (id 0, "ref", is never a carrier)
+  if (sample_ids) {
+    if (n_ids == 0) return fail(VS_ERR_ARG, "an empty sample subset (pass NULL for the whole cohort)");
+    const uint32_t ns = idx->g.num_samples;
+    mask.assign((ns + 63) / 64, 0);
+    for (uint64_t i = 0; i < n_ids; ++i) {
+      const uint32_t id = sample_ids[i];
+      if (id == 0 || id >= ns) return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u is not a sample of the cohort (1 .. %u)", id, ns - 1);
+      mask[id >> 6] |= 1ull << (id & 63);
+    }
+    if (mask.size() * 8 > kCountMaskMaxBytes) return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the counting kernel's LDS", ns);
+  }
+  return make_result(idx, kKindCounts, out, [&](vs_result* r) {
+    return run_counts_batch(idx, regions, n, r, is_device_ptr(regions), mask);
   });
 }
 
@@ -2842,6 +2910,21 @@ int vs_index_find(vs_index* idx, const uint64_t* pos, uint64_t n, uint32_t* vert
 }
 
 // ---------------------------------------------------------------- result access
+// An allele-count result's counts in page-locked memory owned by the result (the caller has passed the gate).
+static int counts_to_host(vs_result* r) {
+  if (r->counts_pin.p) return VS_OK;
+  vs_index* idx = r->idx;
+  VS_TRY(result_ready(r));
+  DevBuf b{nullptr, 0};
+  VS_TRY(pin_alloc(idx, (size_t)r->d.A * sizeof(uint4) + 16, &b));
+  if (r->d.A) {
+    const hipError_t e = hipMemcpyAsync(b.p, r->d_counts, (size_t)r->d.A * sizeof(uint4), hipMemcpyDeviceToHost, idx->stream);
+    const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(idx->stream) : e;
+    if (e2 != hipSuccess) { pin_release(idx, b); return fail(VS_ERR_HIP, "copy of the allele counts failed: %s", hipGetErrorString(e2)); }
+  }
+  r->counts_pin = b;
+  return VS_OK;
+}
 // Start (stream) the raw copy of a result: rows and -- on request -- the arena go into one page-locked block.  (The caller has passed
 // the gate.)
 static int raw_copy_begin(vs_result* r, bool with_carriers, hipStream_t stream) {
@@ -2882,6 +2965,7 @@ static void fill_raw(vs_result* r, vs_result_raw* raw) {
 int vs_result_get_raw(vs_result* r, int with_carriers, vs_result_raw* raw) {
   VS_TRY(result_enter(r, Want::Variants, true));
   if (!raw) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind == kKindCounts && with_carriers) return refuse_counts("vs_result_get_raw with carriers");
   static_assert(sizeof(vs_variant_row) == sizeof(VariantRow), "row layout of the ABI");
   vs_index* idx = r->idx;
   VS_TRY(raw_copy_begin(r, with_carriers != 0, idx->stream));
@@ -2938,6 +3022,7 @@ int vs_query_var_in_ref_stream(vs_index* idx, const vs_region* regions, uint64_t
 int vs_result_get_view(vs_result* r, int with_carriers, vs_result_view* view) {
   VS_TRY(result_enter(r, Want::Variants, true));
   if (!view) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind == kKindCounts && with_carriers) return refuse_counts("vs_result_get_view with carriers");
   VS_TRY(fetch_headers(r));
   if (with_carriers && !r->have_carriers) {
     // the arena pads every variant's range; the view packs the lists back to back
@@ -3003,7 +3088,17 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
     HIP_TRY(hipMemcpyAsync(h, dt, 24, hipMemcpyDeviceToHost, idx->stream));
     HIP_TRY(hipStreamSynchronize(idx->stream));
     tmp.release();
-    r->n_variants = h[0]; r->n_carriers_kept = h[1]; r->n_bases = h[2]; r->have_totals = true;
+    r->n_variants = h[0]; r->n_carriers_kept = h[1]; r->n_bases = h[2];
+    if (r->kind == kKindCounts) {   // the carriers that lie in the subset: the counts of the rows every region reports (dropped rows count 0)
+      VS_TRY(fetch_region_meta(r));
+      VS_TRY(counts_to_host(r));
+      const uint4* c = (const uint4*)r->counts_pin.p;
+      uint64_t nc = 0;
+      for (uint64_t q = 0; q < r->d.Q; ++q)
+        for (uint64_t a = r->h_var_begin[q], e = a + r->h_nvar[q]; a < e; ++a) nc += c[a].x;
+      r->n_carriers_kept = nc;
+    }
+    r->have_totals = true;
   }
   if (n_regions) *n_regions = r->d.Q;
   if (n_variants) *n_variants = r->n_variants;
@@ -3031,6 +3126,34 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
   if (q >= r->d.Q) return fail(VS_ERR_ARG, "region %llu out of range", (unsigned long long)q);
   vs_index* idx = r->idx;
   const uint64_t a0 = r->h_var_begin[q], a1 = a0 + r->h_nvar[q];
+  if (r->kind == kKindCounts) {   // the region's reported rows with their counts
+    VS_TRY(counts_to_host(r));
+    const VariantRow* rows;
+    if (r->have_headers) rows = r->h_rows.data() + a0;
+    else if (r->raw_rows) rows = r->raw_rows + a0;
+    else {
+      VS_TRY(fetch(idx, r->sl_rows, (const VariantRow*)r->d.rows + a0, (size_t)(a1 - a0)));
+      HIP_TRY(hipStreamSynchronize(idx->stream));
+      rows = r->sl_rows.data();
+    }
+    const uint4* c = (const uint4*)r->counts_pin.p;
+    std::string& out = r->text;
+    out = "Pos\tRef\tAlt\tCarriers\tAC\tHomAlt\tPhased\n";
+    for (uint64_t a = a0; a < a1; ++a) {
+      const VariantRow& v = rows[a - a0];
+      if (v.count_flags & kRowDropped) continue;
+      out += std::to_string(v.pos);
+      out += '\t';
+      out.append(idx->seq_chars, v.ref_off, v.ref_len);
+      out += '\t';
+      out.append(idx->seq_chars, v.alt_off, v.alt_len);
+      for (uint32_t f : {c[a].x, c[a].y, c[a].z, c[a].w}) { out += '\t'; out += std::to_string(f); }
+      out += '\n';
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
   const uint64_t c0 = r->h_car_base[q], c1 = c0 + r->h_car_len[q];
   const uint32_t* car = nullptr;
   const bool from_view = r->have_carriers;
@@ -3121,6 +3244,17 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
 
 /* Duration of the result's carrier expansion by HIP events on the stream it ran on, when it ran asynchronously (option
  * "async_fill"; waits for it); -1 otherwise (vs_index_last_timing().ms_fill has it then). */
+int vs_result_get_allele_counts(vs_result* r, uint64_t* n_rows, const vs_allele_counts** counts) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!counts) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindCounts) return fail(VS_ERR_ARG, "not an allele-count result (vs_query_allele_counts)");
+  static_assert(sizeof(vs_allele_counts) == sizeof(uint4), "count layout of the ABI");
+  VS_TRY(counts_to_host(r));
+  *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (n_rows) *n_rows = r->d.A;
+  return VS_OK;
+}
+
 int vs_result_fill_ms(vs_result* r, float* ms) {
   VS_TRY(result_enter(r, Want::Any, true));   // (a refused speculative batch is run now: the time asked for is that of the expansion that produced the result)
   if (!ms) return fail(VS_ERR_ARG, "null argument");
@@ -3141,6 +3275,7 @@ int vs_result_layout(const vs_result* r, uint64_t* n_slots, uint64_t* table_rows
 
 int vs_result_digest(vs_result* r, uint64_t* digest) {
   VS_TRY(result_enter(r, Want::Variants, true));
+  if (r->kind == kKindCounts) return refuse_counts("vs_result_digest");
   if (!digest) return fail(VS_ERR_ARG, "null argument");
   vs_index* idx = r->idx;
   VS_TRY(result_ready(r));
@@ -3165,6 +3300,7 @@ int vs_result_digest(vs_result* r, uint64_t* digest) {
 int vs_result_pack_headers(vs_result* r, void* device_dst, uint64_t capacity_records, uint64_t region_base,
                            uint64_t* n_records) {
   VS_TRY(result_enter(r, Want::Variants, true));
+  if (r->kind == kKindCounts) return refuse_counts("vs_result_pack_headers");
   if (n_records) *n_records = r->n_rows_reported;   // rows over all regions (a shared row once per region reporting it)
   if (!device_dst) return VS_OK;  // size query
   if (capacity_records < r->n_rows_reported) return fail(VS_ERR_ARG, "destination holds %llu records, %llu needed",
@@ -3189,6 +3325,7 @@ int vs_result_pack_regions(vs_result* r, void* device_dst, uint64_t capacity_rec
                            uint64_t* n_records) {
   // (a size query: the region count is known -- a refused batch is redone before its records travel, not before)
   VS_TRY(result_enter(r, Want::Any, /*sizes=*/device_dst != nullptr));
+  if (r->kind == kKindCounts) return refuse_counts("vs_result_pack_regions");
   if (n_records) *n_records = r->d.Q;
   if (!device_dst) return VS_OK;
   if (capacity_records < r->d.Q) return fail(VS_ERR_ARG, "destination holds %llu records, %llu needed",

@@ -51,6 +51,8 @@
 //  k_pack_seq_regions    flags per region): site range + counts, or pieces + bytes of a sequence; k_bounds_from_records: the
 //                       receiving side (vs_query_expand_site_ranges)
 // k_find                Index::find batched
+// k_allele_counts       allele counts per row of a type-6 plan over a sample subset (vs_query_allele_counts: no reference
+//  k_count_slow_sites    counterpart; what a caller of type 6 would count on the host from the carrier lists)
 #pragma once
 #include "k_image.hip.h"
 #include "k_sites.hip.h"
@@ -62,3 +64,4 @@
 #include "k_points.hip.h"
 #include "k_sample_coords.hip.h"
 #include "k_digest.hip.h"
+#include "k_counts.hip.h"
