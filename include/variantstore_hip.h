@@ -197,6 +197,45 @@ int vs_query_allele_counts(vs_index* idx, const vs_region* regions, uint64_t n, 
 /* The counts of an allele-count result, copied into page-locked memory owned by the result: counts[i] belongs to
  * vs_result_raw.rows[i] (table order), so region q's are counts[row_begin[q] .. row_begin[q] + row_count[q]). */
 int vs_result_get_allele_counts(vs_result* r, uint64_t* n_rows, const vs_allele_counts** counts);
+/* Per-sample burden over regions: the counts above along the other axis -- a regions x samples matrix, the input of gene-burden
+ * and collapsing tests and of per-sample QC counts (no reference counterpart: what a caller of type 6 would reduce on the host
+ * from every carrier list).  Let R(q) be the rows type 6 reports for region q (same order, duplicate rule and region flags; a
+ * dropped row is not in R(q)) and ac_S(row) the alt_alleles vs_query_allele_counts reports for the row over the same S.  A row
+ * COUNTS iff min_ac <= ac_S(row) <= max_ac (0 and UINT32_MAX: every reported row counts).  Cell (q, c), over the counting rows
+ * of R(q) of which column c's sample is a carrier (genotype bits as for vs_allele_counts: a `1|2` call gives 2 on both of its
+ * ALT rows, a haploid `1` is gt_1 alone):
+ *   variants    = number of such rows
+ *   alt_alleles = sum of gt_1 + gt_2
+ *   hom_alt     = number with gt_1 && gt_2
+ *   phased      = number with the phase bit */
+typedef struct { uint32_t variants, alt_alleles, hom_alt, phased; } vs_sample_burden;   /* 16 bytes, one cell */
+/* `regions` as for vs_query_allele_counts (host or device memory, n >= 1); `sample_ids` NULL (the whole cohort) or a HOST array of
+ * n_ids >= 1 ids.  The COLUMNS are the distinct ids of S in ascending id order (duplicates collapse); with S == NULL they are the
+ * ids 1 .. num_samples - 1 ("ref", id 0, is never a column).  The matrix's rows are the regions in the caller's order, whether or
+ * not the device sorted the batch.  Checked on the host, in this order, before the handle's device is asked for (a handle opened
+ * without a device reports them first and VS_ERR_NO_DEVICE otherwise): n == 0, sample_ids == NULL with n_ids != 0, non-NULL
+ * sample_ids with n_ids == 0, min_ac > max_ac -> VS_ERR_ARG; id 0 or id >= num_samples -> VS_ERR_UNKNOWN_SAMPLE; a matrix of more
+ * than 2^31 cells (n x columns; 32 GiB) -> VS_ERR_ARG: a condition of this interface, callers split larger batches.  An
+ * allocation failure below that limit is VS_ERR_HIP.
+ * Every batch size takes the batch pipeline, as count batches do; a burden batch is never speculative and leaves the handle's
+ * type-6 state as it was.  The result holds the type-6 per-region arrays and variant table, no carrier arena, and the matrix:
+ * vs_result_get_raw / vs_result_get_view with with_carriers = 0, vs_result_layout (arena and lists 0), vs_result_fill_ms (the
+ * burden kernels, the window's count kernel included), vs_result_totals (n_regions, n_var as for type 6; n_carriers = the sum
+ * of `variants` over the matrix, reduced on the device: with the default window the count result's n_carriers for the same S)
+ * and vs_result_format_region ("Sample\tVariants\tAC\tHomAlt\tPhased\n", then one line per column with variants > 0, in column
+ * order, by sample name) work; with_carriers = 1, vs_result_digest, vs_result_pack_headers / _pack_regions and
+ * vs_comm_allgather_regions* fail with VS_ERR_UNSUPPORTED, vs_result_get_allele_counts with VS_ERR_ARG.
+ * Option "burden_chunk" (vs_index_set_option; 0 = default, 64..65536): the rows of a region one workgroup walks before the region
+ * is split between several. */
+int vs_query_sample_burden(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids,
+                           uint32_t min_ac, uint32_t max_ac, vs_result** out);
+/* The matrix of a burden result copied into page-locked memory owned by the result: cells[q * n_cols + c], col_ids[c] the sample
+ * id of column c.  VS_ERR_ARG on any other result. */
+int vs_result_get_sample_burden(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, const uint32_t** col_ids,
+                                const vs_sample_burden** cells);
+/* The matrix as it lies in HBM: n_regions x n_cols cells of 16 bytes, row-major, valid until vs_result_free.  The engine has
+ * synchronised its stream when this returns: the caller needs no event. */
+int vs_result_sample_burden_device(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, const void** dev_cells);
 
 /* host view of a sequence result: region i is chars[seq_begin[i] .. seq_begin[i+1]) */
 int vs_result_get_sequences(vs_result* r, uint64_t* n_regions, const uint8_t** region_flags, const uint64_t** seq_begin,
@@ -395,6 +434,8 @@ void vs_comm_destroy(vs_comm* c);
  *                     every event is a packet between two kernels of a string of dependent launches (~3 us each)
  *   "force_fallbacks" 1 = query types 2 - 5 take the count-then-emit pair of walks they fall back to when a region outgrows
  *                     the capacity of its recording walk (tests of that path)
+ *   "burden_chunk"    rows of a region one workgroup of the burden kernel walks (vs_query_sample_burden): a region with more is
+ *                     split between several, which add to its cells with atomics.  0 (default): 4096; else 64..65536
  * Tuning builds (VS_BUILD_TUNING=1 python -m variantstore_amd.build --force) add "lat_debug", "fill_fused", "fill_chunk",
  * "fill_stats", "walk_stats", "fill_ablate", "fill_lds_pad"; VS_ERR_UNSUPPORTED in the production library, whose kernels
  * do not carry the code. */

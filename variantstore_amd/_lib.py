@@ -42,6 +42,10 @@ class AlleleCounts(C.Structure):   # vs_allele_counts
     _fields_ = [("carriers", C.c_uint32), ("alt_alleles", C.c_uint32), ("hom_alt", C.c_uint32), ("phased", C.c_uint32)]
 
 
+class SampleBurden(C.Structure):   # vs_sample_burden
+    _fields_ = [("variants", C.c_uint32), ("alt_alleles", C.c_uint32), ("hom_alt", C.c_uint32), ("phased", C.c_uint32)]
+
+
 class ResultView(C.Structure):
     _fields_ = [("n_regions", C.c_uint64), ("region_flags", C.POINTER(C.c_uint8)),
                 ("var_begin", C.POINTER(C.c_uint64)), ("var_count", C.POINTER(C.c_uint64)),
@@ -94,6 +98,11 @@ SYMBOLS = {
     "vs_query_var_in_ref_device": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P)]),
     "vs_query_allele_counts": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(_P)]),
     "vs_result_get_allele_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(AlleleCounts))]),
+    "vs_query_sample_burden": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32,
+                                         C.POINTER(_P)]),
+    "vs_result_get_sample_burden": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint32)),
+                                              C.POINTER(C.POINTER(SampleBurden))]),
+    "vs_result_sample_burden_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)]),
     "vs_query_expand_site_ranges": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P)]),
     "vs_query_sample_var_in_ref": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.c_uint32, C.POINTER(_P)]),
     "vs_query_samples_var_in_ref": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(_P)]),

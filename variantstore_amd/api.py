@@ -236,6 +236,32 @@ class QueryResult:
                         "phased": int(ph), "af": ac / (2.0 * self.subset_size) if self.subset_size else 0.0})
         return out
 
+    BURDEN_DTYPE = np.dtype([("variants", "<u4"), ("alt_alleles", "<u4"), ("hom_alt", "<u4"), ("phased", "<u4")])
+
+    def sample_burden(self):
+        """A burden result (VariantStore.sample_burden) as numpy arrays: `columns` (uint32[C], the sample id of each column,
+        ascending), `cells` (structured (Q, C): variants, alt_alleles, hom_alt, phased; row q is region q of the batch as it
+        was given) and per region `flags`.  Copies, valid after the result is closed."""
+        q, c = C.c_uint64(), C.c_uint64()
+        cols = C.POINTER(C.c_uint32)()
+        p = C.POINTER(_lib.SampleBurden)()
+        _check(self._lib.vs_result_get_sample_burden(self._h, C.byref(q), C.byref(c), C.byref(cols), C.byref(p)),
+               "vs_result_get_sample_burden")
+        nq, nc = int(q.value), int(c.value)
+        cells = (np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(nq * nc * 16,)).view(self.BURDEN_DTYPE)
+                 .reshape(nq, nc).copy())
+        return {"columns": np.ctypeslib.as_array(cols, shape=(nc,)).copy(), "cells": cells,
+                "flags": self.raw(with_carriers=False)["region_flags"].copy()}
+
+    def sample_burden_device(self):
+        """(address, Q, C) of a burden result's matrix as it lies in this GPU's memory: Q x C cells of four uint32, row-major,
+        complete when this returns and valid until the result is closed."""
+        q, c = C.c_uint64(), C.c_uint64()
+        p = C.c_void_p()
+        _check(self._lib.vs_result_sample_burden_device(self._h, C.byref(q), C.byref(c), C.byref(p)),
+               "vs_result_sample_burden_device")
+        return int(p.value or 0), int(q.value), int(c.value)
+
     def region_variants(self, q) -> List[Variant]:
         out = []
         for line in self.region_text(q).split("\n")[1:]:
@@ -469,6 +495,27 @@ class VariantStore:
         res = QueryResult(self, h)
         res.subset_size = subset
         return res
+
+    def sample_burden(self, regions, samples=None, min_ac=0, max_ac=None) -> QueryResult:
+        """Per-sample burden over regions (vs_query_sample_burden): a regions x samples matrix -- for every region and every
+        sample of `samples` (names or ids, taken as a set; None: the whole cohort) the variants of the region the sample
+        carries, with alt_alleles, hom_alt and phased.  Only the rows whose alternate-allele count over the same samples lies
+        in [min_ac, max_ac] count (max_ac None: no upper limit).  `regions` as for allele_counts.  Read the result with
+        QueryResult.sample_burden / sample_burden_device / region_text."""
+        arr, ptr, n = _regions_array(regions)
+        h = C.c_void_p()
+        if samples is None:
+            ids, ids_ptr, n_ids = None, None, 0
+        else:
+            if isinstance(samples, (str, bytes)):
+                samples = [samples]
+            ids = np.ascontiguousarray([self.sample_id(x) if isinstance(x, str) else int(x) for x in samples], dtype=np.uint32)
+            ids_ptr, n_ids = ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.shape[0]
+            if n_ids == 0:   # (the C ABI's NULL-or-non-empty rule: an empty list is not the whole cohort)
+                ids_ptr = (C.c_uint32 * 1)()
+        _check(self._lib.vs_query_sample_burden(self._h, ptr, n, ids_ptr, n_ids, int(min_ac),
+                                                0xFFFFFFFF if max_ac is None else int(max_ac), C.byref(h)), "vs_query_sample_burden")
+        return QueryResult(self, h)
 
     def get_sample_var_in_ref(self, regions, sample) -> QueryResult:
         """Query type 4 for one sample over a batch of regions (query.h:618-729)."""

@@ -111,6 +111,7 @@ bool dir_exists(const std::string& p) {
 
 struct Args {
   std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out, samples_file;
+  uint32_t min_ac = 0, max_ac = UINT32_MAX;   // `burden`: the alternate-allele-count window of the rows that count
   uint32_t type = 0, mode = 0;
   uint64_t hops = 0;
   bool have_hops = false;
@@ -684,7 +685,20 @@ int counts_usage() {
   return EXIT_FAILURE;
 }
 
-int counts_main(const Args& a) {
+// `variantstore burden`: the per-sample burden of the regions (vs_query_sample_burden) over the same samples, restricted to the
+// rows whose alternate-allele count lies in [--min-ac, --max-ac].  Output as `counts`: "#region <i> <x>:<y>", then the region's
+// text ("Sample Variants AC HomAlt Phased", one line per sample that carries a counting variant of the region).
+int burden_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore burden -p <output-prefix> -r <region> [-S <sample-name-file>] [--min-ac <n>] [--max-ac <n>]\n"
+               "                            [-o <outfile>] [--device <n>]\n\n"
+               "        For every region and every sample (of the whole cohort or of those named in the file): the variants of the\n"
+               "        region the sample carries, their alternate alleles, homozygous-alternate and phased calls.  Only variants whose\n"
+               "        alternate-allele count over those samples lies within --min-ac .. --max-ac count (rare-variant burden).\n";
+  return EXIT_FAILURE;
+}
+
+int counts_main(const Args& a, bool burden = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
   if (rc != VS_OK) die(rc, "load");
@@ -709,8 +723,9 @@ int counts_main(const Args& a) {
   std::vector<vs_region> batch;
   for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
   vs_result* res = nullptr;
-  rc = vs_query_allele_counts(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
-  if (rc != VS_OK) die(rc, "counts");
+  if (burden) rc = vs_query_sample_burden(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.min_ac, a.max_ac, &res);
+  else rc = vs_query_allele_counts(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
+  if (rc != VS_OK) die(rc, burden ? "burden" : "counts");
   std::ofstream file;
   if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
   std::ostream& out = a.outfile.empty() ? std::cout : file;
@@ -768,8 +783,10 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts") {
+    } else if (a.cmd == "counts" || a.cmd == "burden") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
+      else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (f == "-r" || f == "--region") a.region = need(i);
       else if (f == "-S" || f == "--samples") a.samples_file = need(i);
       else if (f == "-o" || f == "--output_file") a.outfile = need(i);
@@ -780,6 +797,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "counts") {
     if (a.prefix.empty() || a.region.empty()) return counts_usage();
     return counts_main(a);
+  }
+  if (a.cmd == "burden") {
+    if (a.prefix.empty() || a.region.empty()) return burden_usage();
+    return counts_main(a, /*burden=*/true);
   }
   if (a.cmd == "construct") {
     if (a.ref.empty() || a.vcf.empty() || a.prefix.empty()) return usage();

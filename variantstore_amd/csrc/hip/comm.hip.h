@@ -156,7 +156,7 @@ int vs_comm_info(vs_comm* c, int* rank, int* world, int* rccl_ranks) {
 static int comm_enter(vs_comm* c, vs_result* r, const void* dst) {
   if (!c || !r || !dst) return fail(VS_ERR_ARG, "null argument");
   if (r->idx != c->idx) return fail(VS_ERR_ARG, "the result belongs to another index handle than the communicator");
-  if (r->kind == kKindCounts) return refuse_counts("vs_comm_allgather_regions");
+  if (no_lists(r)) return refuse_no_lists(r, "vs_comm_allgather_regions");
   return result_enter(r, Want::Any, true);   // (a refused batch is redone before its records travel)
 }
 

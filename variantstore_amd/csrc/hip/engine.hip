@@ -86,6 +86,7 @@ struct EngineOpts {
   bool lat_debug = false;       // device-clock stamps of the latency kernels on stderr
   bool fill_fused = true;       // shared batches: the expansion writes the shared rows as well (k_fill_sites2); false: k_share_rows2 + k_fill_sites
   uint32_t fill_chunk = 0;      // rows per task of the expansion: 0 = by the batch's shape, else 8 / 16 / 32 / 64
+  uint32_t burden_chunk = 0;    // rows one workgroup of the burden kernel walks before a region is split: 0 = kBurdenChunkRows
   int fill_mode = 0;            // shared expansion: 0 one launch, 2 split (lists + rows, then the dense sites: what a profiler wants to see apart)
   uint32_t fill_dense_k = 16;   // dense sites per wave of k_fill_dense: 8 / 16 / 32 / 64
   bool fill_stats = false;      // device-clock ticks per phase of the expansion's tasks (k_fill_sites2)
@@ -231,10 +232,18 @@ struct vs_result {
   std::vector<DevBuf> old_pins;   // earlier raw copies of this result (rows only, then rows + carriers): pointers handed out stay valid until it is freed
   const VariantRow* raw_rows = nullptr;
   const uint8_t* raw_arena = nullptr;   // NULL: carriers not copied
-  int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts
+  int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts;
+                 // kKindBurden: per-sample burden
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
+  // burden results (vs_query_sample_burden): the regions x columns matrix in HBM (16 bytes per cell, row-major), the sum of its
+  // `variants` (a device word the kernels add to), the column ids, and the matrix's page-locked host copy
+  uint4* d_cells = nullptr;
+  unsigned long long* d_cell_total = nullptr;
+  std::vector<uint32_t> h_cols;
+  DevBuf cells_pin{nullptr, 0};
+  std::vector<uint4> sl_cells;   // the cells of ONE region, fetched when the matrix is not on the host (vs_result_format_region)
   // sequence results (query types 2 and 3)
   DevSeqResult sq{};
   uint64_t seq_bytes = 0;
@@ -246,6 +255,12 @@ struct vs_result {
 constexpr int kKindCounts = 8;   // vs_result::kind of an allele-count result: the rows of type 6, counts instead of carrier lists
 static int refuse_counts(const char* what) {
   return fail(VS_ERR_UNSUPPORTED, "%s: an allele-count result holds counts per row, no carrier lists (vs_result_get_allele_counts)", what);
+}
+constexpr int kKindBurden = 9;   // ... of a burden result: the rows of type 6, a regions x samples matrix instead of carrier lists
+static bool no_lists(const vs_result* r) { return r->kind == kKindCounts || r->kind == kKindBurden; }
+static int refuse_no_lists(const vs_result* r, const char* what) {
+  if (r->kind == kKindCounts) return refuse_counts(what);
+  return fail(VS_ERR_UNSUPPORTED, "%s: a burden result holds a regions x samples matrix, no carrier lists (vs_result_get_sample_burden)", what);
 }
 
 // ------------------------------------------------------------------ helpers
@@ -1084,7 +1099,10 @@ static int capture_totals(vs_result* r) {
   else { idx->sort_hint = true; idx->sort_probe_in = 32; }   // (as after a batch that was sorted on the device: the next ones sort first -- also when nobody reads this one)
   return VS_OK;
 }
-struct CountReq { const uint64_t* mask; uint32_t words; };   // an allele-count batch: the subset's bit mask in host memory (NULL: the whole cohort)
+// a burden batch (vs_query_sample_burden) is a count batch with a second consumer: the columns in front of each word of the mask
+// (NULL with the mask), their number, the window (0 .. UINT32_MAX: every reported row counts, k_allele_counts is not run)
+struct BurdenReq { const uint32_t* rank; uint32_t n_cols, min_ac, max_ac; };
+struct CountReq { const uint64_t* mask; uint32_t words; const BurdenReq* burden; };   // an allele-count batch: the subset's bit mask in host memory (NULL: the whole cohort)
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
                             bool allow_async, bool may_speculate = true, const CountReq* counting = nullptr);
 // A speculative batch's sizes become the plan's totals here -- or, when the plan refused the batch on the device (more rows or arena
@@ -1168,6 +1186,65 @@ static void launch_fill2(vs_index* idx, const DevResult& d, const RunRec* runs, 
   }
 }
 
+// k_allele_counts over the whole table of a count batch (u_site: the site of every row; d_mask NULL: the whole cohort)
+static void launch_allele_counts(vs_index* idx, const DevResult& d, const uint32_t* u_site, uint64_t U, const uint64_t* d_mask, uint32_t words, uint4* out) {
+  const unsigned blocks = (unsigned)((d.A + 4 * kCountRows - 1) / (4 * kCountRows));
+  if (d_mask) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_allele_counts<true>), dim3(blocks), dim3(256), (size_t)words * 8, idx->stream, idx->d,
+                                 (const VariantRow*)d.rows, u_site, d.A, U, d_mask, words, out);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_allele_counts<false>), dim3(blocks), dim3(256), 0, idx->stream, idx->d,
+                          (const VariantRow*)d.rows, u_site, d.A, U, (const uint64_t*)nullptr, 0u, out);
+}
+
+// The burden matrix of a count batch whose per-region arrays are in the caller's order: one workgroup per (region, column tile), and
+// -- only when the rows all regions report could hold a region longer than a chunk -- the device-built list of such regions' chunks
+// and the launch that adds them (its workgroups beyond the list return at once).
+template <bool SUBSET, bool WINDOW>
+static int launch_burden_kernels(vs_index* idx, const BurdenArgs& a, uint64_t Q, uint32_t cap, size_t lds) {
+  auto big_lds = [&](const void* fn) -> int {   // (more than 64 KiB of dynamic LDS is asked for per kernel)
+    if (lds > (64 << 10)) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return VS_OK;
+  };
+  VS_TRY(big_lds(reinterpret_cast<const void*>(&k_sample_burden<SUBSET, WINDOW, false>)));
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sample_burden<SUBSET, WINDOW, false>), dim3((unsigned)(Q * a.n_tiles)), dim3(256), lds, idx->stream, idx->d, a);
+  if (cap) {
+    VS_TRY(big_lds(reinterpret_cast<const void*>(&k_sample_burden<SUBSET, WINDOW, true>)));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sample_burden<SUBSET, WINDOW, true>), dim3((unsigned)((uint64_t)cap * a.n_tiles)), dim3(256), lds, idx->stream, idx->d, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+static int launch_burden(vs_index* idx, vs_result* r, const uint32_t* u_site, uint64_t U, const uint64_t* d_mask, const uint32_t* d_rank, uint32_t words,
+                         const BurdenReq& bq, ScratchBufs& scratch) {
+  const DevResult& d = r->d;
+  BurdenArgs a{};
+  a.rows = d.rows; a.u_site = u_site; a.U = U; a.var_begin = d.var_begin; a.q_nvar = d.q_nvar;
+  a.S = d_mask; a.S_rank = d_rank; a.s_words = d_mask ? words : 0;
+  a.ac = r->d_counts; a.min_ac = bq.min_ac; a.max_ac = bq.max_ac;
+  a.n_cols = bq.n_cols;
+  a.tile_cols = std::min<uint32_t>(bq.n_cols, kBurdenTileCols);
+  a.n_tiles = (bq.n_cols + a.tile_cols - 1) / a.tile_cols;
+  a.chunk_rows = idx->opts.burden_chunk ? idx->opts.burden_chunk : kBurdenChunkRows;
+  a.cells = r->d_cells; a.total = r->d_cell_total;
+  uint32_t* n_work = reinterpret_cast<uint32_t*>(r->d_cell_total + 1);
+  a.n_work = n_work;
+  if (d.Q * a.n_tiles > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu regions x %u column tiles)", (unsigned long long)d.Q, a.n_tiles);
+  HIP_TRY(hipMemsetAsync(r->d_cell_total, 0, 16, idx->stream));
+  // every split region has more than chunk_rows rows, so its chunks number less than twice its rows / chunk_rows
+  const uint64_t cap64 = r->n_rows_reported > a.chunk_rows ? 2 * r->n_rows_reported / a.chunk_rows : 0;
+  if (cap64 * a.n_tiles > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu row chunks x %u column tiles)", (unsigned long long)cap64, a.n_tiles);
+  const uint32_t cap = (uint32_t)cap64;
+  if (cap) {
+    uint2* work = nullptr;
+    VS_TRY(dev_alloc(idx, (size_t)cap * sizeof(uint2), (void**)&work, &scratch.bufs));
+    a.work = work;
+    hipLaunchKernelGGL(k_burden_split_plan, dim3((unsigned)((d.Q + 255) / 256)), dim3(256), 0, idx->stream, (const uint64_t*)d.q_nvar, d.Q, a.chunk_rows, work, n_work, cap);
+  }
+  const size_t lds = (size_t)a.tile_cols * 16 + (size_t)a.s_words * 12;
+  const bool window = r->d_counts != nullptr;
+  if (d_mask) return window ? launch_burden_kernels<true, true>(idx, a, d.Q, cap, lds) : launch_burden_kernels<true, false>(idx, a, d.Q, cap, lds);
+  return window ? launch_burden_kernels<false, true>(idx, a, d.Q, cap, lds) : launch_burden_kernels<false, false>(idx, a, d.Q, cap, lds);
+}
+
 // Query type 6 over a batch whose regions SHARE rows and carrier lists (every batch of more than 64 regions unless
 // option share_lists is 0).  Stages, each reading only what the stage before it left:
 //   plan   k_t6_bounds / _mid / _apply: bounds, E_prev, the per-region arrays, the row deltas, the slow-region list;
@@ -1180,6 +1257,9 @@ static void launch_fill2(vs_index* idx, const DevResult& d, const RunRec* runs, 
 //   counts (an allele-count batch, `counting`: vs_query_allele_counts) instead of the expansion: k_share_rows2 with the site of every
 //          row, k_count_slow_sites for the private rows, k_allele_counts.  Never speculative, no arena, and it leaves the handle's
 //          type-6 state (size hints, sort hint) as it found it: count batches interleaved with type-6 batches change none of theirs
+//   burden (a count batch with CountReq::burden: vs_query_sample_burden) the same, then -- behind the permutation of an unsorted batch,
+//          the matrix's rows are the regions in the caller's order -- k_allele_counts only under a window, k_sample_burden over
+//          (region, column tile) pairs, and for regions longer than a chunk k_burden_split_plan + the SPLIT launch
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
                             bool allow_async, bool may_speculate, const CountReq* counting) {
   VS_TRY(begin_batch(idx));
@@ -1187,14 +1267,18 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   d.Q = n;
   uint64_t* dreg = nullptr;
   uint64_t* d_mask = nullptr;   // (an allele-count batch over a subset: its bit mask, copied with the regions)
+  uint32_t* d_rank = nullptr;   // (a burden batch over a subset: the columns in front of each mask word)
+  const BurdenReq* burden = counting ? counting->burden : nullptr;
   {   // the per-region arrays of the result: one buffer
     Slab sl;
     const size_t o_reg = sl.add(2 * n * 8), o_fl = sl.add(n * sizeof(*d.q_flags)), o_g0 = sl.add(n * sizeof(*d.q_g0)), o_nv = sl.add(n * sizeof(*d.q_nvar)),
                  o_nc = sl.add(n * sizeof(*d.q_ncar)), o_vb = sl.add((n + 1) * sizeof(*d.var_begin)), o_cb = sl.add((n + 1) * sizeof(*d.car_base)),
                  o_vc = sl.add(n * sizeof(*d.var_count)), o_cl = sl.add(n * sizeof(*d.q_car_len)),
-                 o_mk = sl.add(counting && counting->mask ? (size_t)counting->words * 8 : 0);
+                 o_mk = sl.add(counting && counting->mask ? (size_t)counting->words * 8 : 0),
+                 o_rk = sl.add(burden && burden->rank ? (size_t)counting->words * 4 : 0);
     VS_TRY(ralloc(r, sl.bytes, &sl.base));
     if (counting && counting->mask) d_mask = sl.at<uint64_t>(o_mk);
+    if (burden && burden->rank) d_rank = sl.at<uint32_t>(o_rk);
     dreg = sl.at<uint64_t>(o_reg);
     d.q_flags = sl.at<std::remove_pointer_t<decltype(d.q_flags)>>(o_fl); d.q_g0 = sl.at<std::remove_pointer_t<decltype(d.q_g0)>>(o_g0);
     d.q_nvar = sl.at<std::remove_pointer_t<decltype(d.q_nvar)>>(o_nv); d.q_ncar = sl.at<std::remove_pointer_t<decltype(d.q_ncar)>>(o_nc);
@@ -1220,6 +1304,7 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   else if (regions) HIP_TRY(hipMemcpyAsync(dreg, regions, n * 16, regions_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ps));
   else HIP_TRY(hipMemsetAsync(dreg, 0, n * 16, ps));
   if (d_mask) HIP_TRY(hipMemcpyAsync(d_mask, counting->mask, (size_t)counting->words * 8, hipMemcpyHostToDevice, ps));
+  if (d_rank) HIP_TRY(hipMemcpyAsync(d_rank, burden->rank, (size_t)counting->words * 4, hipMemcpyHostToDevice, ps));
   HIP_TRY(hipEventRecord(idx->ev[0], ps));
   ScratchBufs scratch(idx);
   const bool resident = !counting && idx->opts.resident_lists && idx->res_arena;
@@ -1370,7 +1455,12 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   r->n_unique_sites = resident || counting ? 0 : U;
   if (counting) {
     VS_TRY(ralloc(r, d.A, &d.rows));
-    VS_TRY(ralloc(r, d.A, &r->d_counts));
+    const bool window = burden && (burden->min_ac != 0 || burden->max_ac != UINT32_MAX);
+    if (!burden || window) VS_TRY(ralloc(r, d.A, &r->d_counts));   // (a burden batch: the filter's input, made only under a window)
+    if (burden) {
+      VS_TRY(ralloc(r, (size_t)n * burden->n_cols, &r->d_cells));
+      VS_TRY(ralloc(r, 2, &r->d_cell_total));   // (+ the number of chunks of the split regions)
+    }
   } else if (!spec) {
     VS_TRY(ralloc(r, d.A, &d.rows));
     if (resident) d.carriers = idx->res_arena;
@@ -1396,8 +1486,9 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   }
   // ---- shared rows + carrier lists ----
   uint32_t* u_site = nullptr;
+  if (counting && d.A) VS_TRY(dev_alloc(idx, d.A * 4 + 8, (void**)&u_site, &scratch.bufs));   // (counts: the private rows' sites too)
   if (U && !fused) {
-    if (!resident) VS_TRY(dev_alloc(idx, (counting ? d.A : U) * 4 + 8, (void**)&u_site, &scratch.bufs));   // (counts: the private rows' sites too)
+    if (!resident && !counting) VS_TRY(dev_alloc(idx, U * 4 + 8, (void**)&u_site, &scratch.bufs));
     hipLaunchKernelGGL(k_share_rows2, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, idx->stream, idx->d, d, (const RunRec*)runs, (const uint32_t*)coarse, n_runs, U, u_site);
   }
   HIP_TRY(hipGetLastError());
@@ -1409,16 +1500,14 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
       const uint64_t waves = std::min<uint64_t>(n_slow, 16384);
       hipLaunchKernelGGL(k_count_slow_sites, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, idx->stream, d, (const uint32_t*)slow_list, n_slow, u_site);
     }
-    VS_TRY(result_events(r));
-    HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
-    const unsigned blocks = (unsigned)((d.A + 4 * kCountRows - 1) / (4 * kCountRows));
-    if (d_mask) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_allele_counts<true>), dim3(blocks), dim3(256), (size_t)counting->words * 8, idx->stream, idx->d,
-                                   (const VariantRow*)d.rows, (const uint32_t*)u_site, d.A, U, (const uint64_t*)d_mask, counting->words, r->d_counts);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_allele_counts<false>), dim3(blocks), dim3(256), 0, idx->stream, idx->d,
-                            (const VariantRow*)d.rows, (const uint32_t*)u_site, d.A, U, (const uint64_t*)nullptr, 0u, r->d_counts);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
-    r->pending = true;
+    if (!burden) {
+      VS_TRY(result_events(r));
+      HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
+      launch_allele_counts(idx, d, u_site, U, d_mask, counting->words, r->d_counts);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
+      r->pending = true;
+    }
   }
   if (async_fill) {
     // the expansion goes to the handle's second stream behind an event and the call returns once the FIRST stream is done
@@ -1488,13 +1577,21 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
     hipLaunchKernelGGL(k_permute_out, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, idx->stream, ds, d, (const uint32_t*)perm);
     HIP_TRY(hipGetLastError());
   }
+  if (burden) {   // the matrix, between the result's own pair of events (vs_result_fill_ms): the filter's counts are inside the pair
+    VS_TRY(result_events(r));
+    HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
+    if (r->d_counts && d.A) launch_allele_counts(idx, d, u_site, U, d_mask, counting->words, r->d_counts);
+    VS_TRY(launch_burden(idx, r, u_site, U, d_mask, d_rank, counting->words, *burden, scratch));
+    HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
+    r->pending = true;
+  }
   if (!lean) HIP_TRY(hipEventRecord(idx->ev[4], idx->stream));
   else {   // plan: the handle's two events on the plan stream; the rest: the result's pair (no separate rows kernel: ms_emit = 0)
     idx->tev[0] = idx->ev[0]; idx->tev[1] = idx->ev[1]; idx->tev[2] = r->ev_fill[0]; idx->tev[3] = r->ev_fill[0]; idx->tev[4] = r->ev_fill[1];
     idx->timing_owner = r;
   }
   idx->timing_pending = true;
-  idx->timing_fill_launches = (n_fill || (counting && d.A)) ? 1 : 0;   // (async_fill: ms_fill is what the first stream saw of it, ~0; vs_result_fill_ms has the kernel's time)
+  idx->timing_fill_launches = (n_fill || (counting && d.A) || burden) ? 1 : 0;   // (async_fill: ms_fill is what the first stream saw of it, ~0; vs_result_fill_ms has the kernel's time)
   // async_submit: the batch is enqueued, its sizes are known (the plan's totals; a speculative batch: result_sizes) and its buffers are the
   // result's -- the call returns here; the timing events are read when asked for
   if (async_submit) return batch_enqueued(r, scratch, /*record_done=*/!lean);
@@ -1745,8 +1842,9 @@ static int run_type6(vs_index* idx, const vs_region* regions, uint64_t n, vs_res
 // Allele counts (vs_query_allele_counts): the plan and the shared rows of type 6, then k_allele_counts over the rows instead of the
 // expansion -- every batch size, never speculative, no arena (run_type6_shared: `counting`).  mask: a bit per sample of the subset,
 // empty for the whole cohort.
-static int run_counts_batch(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const std::vector<uint64_t>& mask) {
-  const CountReq cq{mask.empty() ? nullptr : mask.data(), (uint32_t)mask.size()};
+static int run_counts_batch(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const std::vector<uint64_t>& mask,
+                            const BurdenReq* burden = nullptr) {
+  const CountReq cq{mask.empty() ? nullptr : mask.data(), (uint32_t)mask.size(), burden};
   return run_type6_shared(idx, regions, n, r, regions_on_device, nullptr, /*allow_async=*/true, /*may_speculate=*/false, &cq);
 }
 
@@ -2674,6 +2772,10 @@ int vs_index_set_option(vs_index* idx, const char* key, int64_t value) {
   } else if (k == "phase_events") o.phase_events = value != 0;
   else if (k == "force_fallbacks") o.force_fallbacks = value != 0;
   else if (k == "t6_speculate") o.t6_speculate = value != 0;
+  else if (k == "burden_chunk") {
+    if (value != 0 && (value < 64 || value > 65536)) return fail(VS_ERR_ARG, "burden_chunk takes 0 (default) or 64..65536 rows");
+    o.burden_chunk = (uint32_t)value;
+  }
   else if (k == "lat_debug" || k == "sc_group" || k == "fill_fused" || k == "fill_chunk" || k == "fill_mode" || k == "fill_dense_k" || k == "fill_stats" || k == "walk_stats" || k == "fill_ablate" ||
            k == "fill_lds_pad") {
 #ifdef VS_TUNING
@@ -2726,6 +2828,7 @@ void vs_result_free(vs_result* r) {
     release_bufs(r->idx, r->bufs);
     pin_release(r->idx, r->raw_pin);
     pin_release(r->idx, r->counts_pin);
+    pin_release(r->idx, r->cells_pin);
     for (auto& b : r->old_pins) pin_release(r->idx, b);
     r->idx->live_results--;
     if (r->idx->close_pending && r->idx->live_results == 0 && r->idx->live_comms == 0) vs_index_close(r->idx);
@@ -2789,6 +2892,46 @@ int vs_query_allele_counts(vs_index* idx, const vs_region* regions, uint64_t n, 
   }
   return make_result(idx, kKindCounts, out, [&](vs_result* r) {
     return run_counts_batch(idx, regions, n, r, is_device_ptr(regions), mask);
+  });
+}
+
+int vs_query_sample_burden(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t min_ac, uint32_t max_ac,
+                           vs_result** out) {
+  // (the arguments first, in the order of the count entry point: they are checked on the host, also on a handle opened without a device)
+  if (!idx || !out || (n && !regions) || (!sample_ids && n_ids)) return fail(VS_ERR_ARG, "null argument");
+  if (n == 0) return fail(VS_ERR_ARG, "a burden batch needs at least one region");
+  if (sample_ids && n_ids == 0) return fail(VS_ERR_ARG, "an empty sample subset (pass NULL for the whole cohort)");
+  if (min_ac > max_ac) return fail(VS_ERR_ARG, "an empty allele-count window [%u, %u]", min_ac, max_ac);
+  const uint32_t ns = idx->g.num_samples;
+  std::vector<uint64_t> mask;    // the subset as a bit per sample (id 0, "ref", is never a carrier)
+  std::vector<uint32_t> rank;    // the columns in front of each word of the mask
+  std::vector<uint32_t> cols;    // the distinct ids, ascending
+  if (sample_ids) {
+    mask.assign((ns + 63) / 64, 0);
+    for (uint64_t i = 0; i < n_ids; ++i) {
+      const uint32_t id = sample_ids[i];
+      if (id == 0 || id >= ns) return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u is not a sample of the cohort (1 .. %u)", id, ns - 1);
+      mask[id >> 6] |= 1ull << (id & 63);
+    }
+    rank.resize(mask.size());
+    for (size_t w = 0; w < mask.size(); ++w) {
+      rank[w] = (uint32_t)cols.size();
+      for (uint64_t m = mask[w]; m; m &= m - 1) cols.push_back((uint32_t)(w * 64 + __builtin_ctzll(m)));
+    }
+  } else {
+    if (ns < 2) return fail(VS_ERR_ARG, "the cohort has no samples");
+    cols.resize(ns - 1);
+    for (uint32_t i = 0; i + 1 < ns; ++i) cols[i] = i + 1;
+  }
+  const uint64_t n_cols = cols.size();
+  if (n > (1ull << 31) / n_cols)
+    return fail(VS_ERR_ARG, "a burden matrix of %llu regions x %llu columns exceeds 2^31 cells (%llu GiB at 16 bytes a cell): split the batch",
+                (unsigned long long)n, (unsigned long long)n_cols, (unsigned long long)((n >> 26) * n_cols));
+  if (mask.size() * 8 > kBurdenMaskMaxBytes) return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the burden kernel's LDS", ns);
+  const BurdenReq bq{rank.empty() ? nullptr : rank.data(), (uint32_t)n_cols, min_ac, max_ac};
+  return make_result(idx, kKindBurden, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    return run_counts_batch(idx, regions, n, r, is_device_ptr(regions), mask, &bq);
   });
 }
 
@@ -2925,6 +3068,20 @@ static int counts_to_host(vs_result* r) {
   r->counts_pin = b;
   return VS_OK;
 }
+// A burden result's matrix in page-locked memory owned by the result (the caller has passed the gate).
+static int cells_to_host(vs_result* r) {
+  if (r->cells_pin.p) return VS_OK;
+  vs_index* idx = r->idx;
+  VS_TRY(result_ready(r));
+  const size_t bytes = (size_t)r->d.Q * r->h_cols.size() * sizeof(uint4);
+  DevBuf b{nullptr, 0};
+  VS_TRY(pin_alloc(idx, bytes + 16, &b));
+  const hipError_t e = hipMemcpyAsync(b.p, r->d_cells, bytes, hipMemcpyDeviceToHost, idx->stream);
+  const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(idx->stream) : e;
+  if (e2 != hipSuccess) { pin_release(idx, b); return fail(VS_ERR_HIP, "copy of the burden matrix failed: %s", hipGetErrorString(e2)); }
+  r->cells_pin = b;
+  return VS_OK;
+}
 // Start (stream) the raw copy of a result: rows and -- on request -- the arena go into one page-locked block.  (The caller has passed
 // the gate.)
 static int raw_copy_begin(vs_result* r, bool with_carriers, hipStream_t stream) {
@@ -2965,7 +3122,7 @@ static void fill_raw(vs_result* r, vs_result_raw* raw) {
 int vs_result_get_raw(vs_result* r, int with_carriers, vs_result_raw* raw) {
   VS_TRY(result_enter(r, Want::Variants, true));
   if (!raw) return fail(VS_ERR_ARG, "null argument");
-  if (r->kind == kKindCounts && with_carriers) return refuse_counts("vs_result_get_raw with carriers");
+  if (no_lists(r) && with_carriers) return refuse_no_lists(r, "vs_result_get_raw with carriers");
   static_assert(sizeof(vs_variant_row) == sizeof(VariantRow), "row layout of the ABI");
   vs_index* idx = r->idx;
   VS_TRY(raw_copy_begin(r, with_carriers != 0, idx->stream));
@@ -3022,7 +3179,7 @@ int vs_query_var_in_ref_stream(vs_index* idx, const vs_region* regions, uint64_t
 int vs_result_get_view(vs_result* r, int with_carriers, vs_result_view* view) {
   VS_TRY(result_enter(r, Want::Variants, true));
   if (!view) return fail(VS_ERR_ARG, "null argument");
-  if (r->kind == kKindCounts && with_carriers) return refuse_counts("vs_result_get_view with carriers");
+  if (no_lists(r) && with_carriers) return refuse_no_lists(r, "vs_result_get_view with carriers");
   VS_TRY(fetch_headers(r));
   if (with_carriers && !r->have_carriers) {
     // the arena pads every variant's range; the view packs the lists back to back
@@ -3098,6 +3255,13 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
         for (uint64_t a = r->h_var_begin[q], e = a + r->h_nvar[q]; a < e; ++a) nc += c[a].x;
       r->n_carriers_kept = nc;
     }
+    if (r->kind == kKindBurden) {   // the sum of `variants` over the matrix: the burden kernels' own word
+      VS_TRY(result_ready(r));
+      uint64_t nc = 0;
+      HIP_TRY(hipMemcpyAsync(&nc, r->d_cell_total, 8, hipMemcpyDeviceToHost, idx->stream));
+      HIP_TRY(hipStreamSynchronize(idx->stream));
+      r->n_carriers_kept = nc;
+    }
     r->have_totals = true;
   }
   if (n_regions) *n_regions = r->d.Q;
@@ -3126,6 +3290,29 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
   if (q >= r->d.Q) return fail(VS_ERR_ARG, "region %llu out of range", (unsigned long long)q);
   vs_index* idx = r->idx;
   const uint64_t a0 = r->h_var_begin[q], a1 = a0 + r->h_nvar[q];
+  if (r->kind == kKindBurden) {   // the region's row of the matrix: the columns whose sample carries any counting row
+    const size_t nc = r->h_cols.size();
+    const uint4* c;
+    if (r->cells_pin.p) c = (const uint4*)r->cells_pin.p + q * nc;
+    else {
+      VS_TRY(result_ready(r));
+      VS_TRY(fetch(idx, r->sl_cells, (const uint4*)r->d_cells + q * nc, nc));
+      HIP_TRY(hipStreamSynchronize(idx->stream));
+      c = r->sl_cells.data();
+    }
+    std::string& out = r->text;
+    out = "Sample\tVariants\tAC\tHomAlt\tPhased\n";
+    for (size_t k = 0; k < nc; ++k) {
+      if (!c[k].x) continue;
+      const uint32_t id = r->h_cols[k];
+      out += id < idx->g.sample_names.size() ? idx->g.sample_names[id] : std::string("?");
+      for (uint32_t f : {c[k].x, c[k].y, c[k].z, c[k].w}) { out += '\t'; out += std::to_string(f); }
+      out += '\n';
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
   if (r->kind == kKindCounts) {   // the region's reported rows with their counts
     VS_TRY(counts_to_host(r));
     const VariantRow* rows;
@@ -3255,6 +3442,31 @@ int vs_result_get_allele_counts(vs_result* r, uint64_t* n_rows, const vs_allele_
   return VS_OK;
 }
 
+int vs_result_get_sample_burden(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, const uint32_t** col_ids, const vs_sample_burden** cells) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!cells) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindBurden) return fail(VS_ERR_ARG, "not a burden result (vs_query_sample_burden)");
+  static_assert(sizeof(vs_sample_burden) == sizeof(uint4), "cell layout of the ABI");
+  VS_TRY(cells_to_host(r));
+  *cells = (const vs_sample_burden*)r->cells_pin.p;
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (col_ids) *col_ids = r->h_cols.data();
+  return VS_OK;
+}
+
+int vs_result_sample_burden_device(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, const void** dev_cells) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!dev_cells) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindBurden) return fail(VS_ERR_ARG, "not a burden result (vs_query_sample_burden)");
+  VS_TRY(result_ready(r));
+  HIP_TRY(hipStreamSynchronize(r->idx->stream));   // the matrix is complete when the pointer is handed out: the caller needs no event
+  *dev_cells = r->d_cells;
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_cols) *n_cols = r->h_cols.size();
+  return VS_OK;
+}
+
 int vs_result_fill_ms(vs_result* r, float* ms) {
   VS_TRY(result_enter(r, Want::Any, true));   // (a refused speculative batch is run now: the time asked for is that of the expansion that produced the result)
   if (!ms) return fail(VS_ERR_ARG, "null argument");
@@ -3275,7 +3487,7 @@ int vs_result_layout(const vs_result* r, uint64_t* n_slots, uint64_t* table_rows
 
 int vs_result_digest(vs_result* r, uint64_t* digest) {
   VS_TRY(result_enter(r, Want::Variants, true));
-  if (r->kind == kKindCounts) return refuse_counts("vs_result_digest");
+  if (no_lists(r)) return refuse_no_lists(r, "vs_result_digest");
   if (!digest) return fail(VS_ERR_ARG, "null argument");
   vs_index* idx = r->idx;
   VS_TRY(result_ready(r));
@@ -3300,7 +3512,7 @@ int vs_result_digest(vs_result* r, uint64_t* digest) {
 int vs_result_pack_headers(vs_result* r, void* device_dst, uint64_t capacity_records, uint64_t region_base,
                            uint64_t* n_records) {
   VS_TRY(result_enter(r, Want::Variants, true));
-  if (r->kind == kKindCounts) return refuse_counts("vs_result_pack_headers");
+  if (no_lists(r)) return refuse_no_lists(r, "vs_result_pack_headers");
   if (n_records) *n_records = r->n_rows_reported;   // rows over all regions (a shared row once per region reporting it)
   if (!device_dst) return VS_OK;  // size query
   if (capacity_records < r->n_rows_reported) return fail(VS_ERR_ARG, "destination holds %llu records, %llu needed",
@@ -3325,7 +3537,7 @@ int vs_result_pack_regions(vs_result* r, void* device_dst, uint64_t capacity_rec
                            uint64_t* n_records) {
   // (a size query: the region count is known -- a refused batch is redone before its records travel, not before)
   VS_TRY(result_enter(r, Want::Any, /*sizes=*/device_dst != nullptr));
-  if (r->kind == kKindCounts) return refuse_counts("vs_result_pack_regions");
+  if (no_lists(r)) return refuse_no_lists(r, "vs_result_pack_regions");
   if (n_records) *n_records = r->d.Q;
   if (!device_dst) return VS_OK;
   if (capacity_records < r->d.Q) return fail(VS_ERR_ARG, "destination holds %llu records, %llu needed",
