@@ -236,6 +236,43 @@ int vs_result_get_sample_burden(vs_result* r, uint64_t* n_regions, uint64_t* n_c
 /* The matrix as it lies in HBM: n_regions x n_cols cells of 16 bytes, row-major, valid until vs_result_free.  The engine has
  * synchronised its stream when this returns: the caller needs no event. */
 int vs_result_sample_burden_device(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, const void** dev_cells);
+/* The genotype matrix over regions: the object the two queries above reduce -- for the variants of a set of regions every sample's
+ * call as a dense byte matrix, the input of LD / r^2, PCA / GRM and association tests (no reference counterpart: what a caller of
+ * type 6 would scatter on the host from every carrier list).  Let T be the variant table a type-6 batch over `regions` produces
+ * (the shared rows in site order, behind them the private rows of the regions under the duplicate rule; region q's rows are
+ * row_begin[q] .. row_begin[q] + row_count[q] of vs_result_get_raw).  The matrix has one ROW per row of T and one COLUMN per
+ * sample of S: the distinct ids of `sample_ids` in ascending order (a HOST array of n_ids >= 1 ids, duplicates collapse), or with
+ * sample_ids == NULL the ids 1 .. num_samples - 1 ("ref", id 0, is never a column).  Cell (i, c):
+ *   0           column c's sample is not a carrier of row i, or row i was dropped by the duplicate rule
+ *   0x08 | gt   it is a carrier; gt = the index's three genotype bits as type 6's arena holds them (bit 0 phase, bit 1 gt_1,
+ *               bit 2 gt_2: what vs_allele_counts and vs_sample_burden sum).  The dosage is popcount(cell & 6); a `1|2` call shows
+ *               on both of its ALT rows, a haploid `1` is gt_1 alone.
+ * The matrix is row-major, rows row_pitch bytes apart: the columns rounded up to a multiple of 16; padding bytes are 0.  A batch
+ * whose table is empty gives 0 rows and is no error.
+ * `regions` as for vs_query_allele_counts (host or device memory, n >= 1).  Checked on the host, in this order, before the handle's
+ * device is asked for (a handle opened without a device reports them first and VS_ERR_NO_DEVICE otherwise): n == 0, sample_ids ==
+ * NULL with n_ids != 0, non-NULL sample_ids with n_ids == 0 -> VS_ERR_ARG; id 0 or id >= num_samples -> VS_ERR_UNKNOWN_SAMPLE.
+ * A matrix (rows x row_pitch) of more than option "matrix_max_mib" MiB (default 32 GiB) is refused with VS_ERR_ARG once the plan
+ * has given the rows and before anything is allocated for it; the message names rows, columns and bytes.  An allocation failure
+ * below the limit is VS_ERR_HIP.
+ * Every batch size takes the batch pipeline, as count batches do; a matrix batch is never speculative and leaves the handle's
+ * type-6 state as it was.  The result holds the type-6 per-region arrays and variant table, no carrier arena, and the matrix:
+ * vs_result_get_raw / vs_result_get_view with with_carriers = 0, vs_result_layout (arena and lists 0), vs_result_fill_ms (the
+ * matrix kernel), vs_result_totals (n_regions, n_var as for type 6; n_carriers = the nonzero cells of the matrix, counted on the
+ * device: every table row once -- the count result's n_carriers for the same S when no two regions report the same row) and vs_result_format_region ("Pos\tRef\tAlt" and "\t<sample name>" per
+ * column, then per reported row of the region -- dropped rows left out -- Pos, Ref, Alt as type 6 prints them and per column `0`
+ * for a non-carrier, else gt_1, `|` under the phase bit or `/`, gt_2) work; with_carriers = 1, vs_result_digest,
+ * vs_result_pack_headers / _pack_regions and vs_comm_allgather_regions* fail with VS_ERR_UNSUPPORTED, vs_result_get_allele_counts
+ * and vs_result_get_sample_burden with VS_ERR_ARG. */
+int vs_query_genotype_matrix(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids,
+                             vs_result** out);
+/* The matrix of a genotype-matrix result copied into page-locked memory owned by the result: cells[i * row_pitch + c], col_ids[c]
+ * the sample id of column c.  VS_ERR_ARG on any other result. */
+int vs_result_get_genotype_matrix(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint64_t* row_pitch, const uint32_t** col_ids,
+                                  const uint8_t** cells);
+/* The matrix as it lies in HBM: n_rows rows of row_pitch bytes, valid until vs_result_free.  The engine has synchronised its
+ * stream when this returns: the caller needs no event. */
+int vs_result_genotype_matrix_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint64_t* row_pitch, const void** dev_cells);
 
 /* host view of a sequence result: region i is chars[seq_begin[i] .. seq_begin[i+1]) */
 int vs_result_get_sequences(vs_result* r, uint64_t* n_regions, const uint8_t** region_flags, const uint64_t** seq_begin,
@@ -436,6 +473,9 @@ void vs_comm_destroy(vs_comm* c);
  *                     the capacity of its recording walk (tests of that path)
  *   "burden_chunk"    rows of a region one workgroup of the burden kernel walks (vs_query_sample_burden): a region with more is
  *                     split between several, which add to its cells with atomics.  0 (default): 4096; else 64..65536
+ *   "matrix_max_mib"  the largest genotype matrix (vs_query_genotype_matrix), in MiB, a batch may ask for.  0 (default): 32 GiB
+ *   "matrix_tile_cols" columns of a workgroup's tile of the matrix kernel: 0 (default): 4096; else a multiple of 16 in 16..65536
+ *                     (small cohorts reach tile boundaries with it)
  * Tuning builds (VS_BUILD_TUNING=1 python -m variantstore_amd.build --force) add "lat_debug", "fill_fused", "fill_chunk",
  * "fill_stats", "walk_stats", "fill_ablate", "fill_lds_pad"; VS_ERR_UNSUPPORTED in the production library, whose kernels
  * do not carry the code. */

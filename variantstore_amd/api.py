@@ -262,6 +262,44 @@ class QueryResult:
                "vs_result_sample_burden_device")
         return int(p.value or 0), int(q.value), int(c.value)
 
+    def genotype_matrix(self):
+        """A genotype-matrix result (VariantStore.genotype_matrix) as numpy arrays: `columns` (uint32[C], the sample id of each
+        column, ascending), `cells` (uint8 (A, C): row i belongs to row i of the variant table, 0 = not a carrier, else
+        0x08 | genotype bits; a view of the pitched buffer: cells.strides[0] == row_pitch), `row_pitch`, the table's
+        `rows` and per region `row_begin`, `row_count` and `flags` -- region q's rows are
+        cells[row_begin[q] : row_begin[q] + row_count[q]].  Copies, valid after the result is closed."""
+        a, c, pitch = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        cols = C.POINTER(C.c_uint32)()
+        p = C.POINTER(C.c_uint8)()
+        _check(self._lib.vs_result_get_genotype_matrix(self._h, C.byref(a), C.byref(c), C.byref(pitch), C.byref(cols), C.byref(p)),
+               "vs_result_get_genotype_matrix")
+        na, nc, np_ = int(a.value), int(c.value), int(pitch.value)
+        buf = (np.ctypeslib.as_array(p, shape=(na * np_,)).copy() if na else np.zeros(0, np.uint8)).reshape(na, np_)
+        raw = self.raw(with_carriers=False)
+        return {"columns": np.ctypeslib.as_array(cols, shape=(nc,)).copy(), "cells": buf[:, :nc], "row_pitch": np_,
+                "rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "flags": raw["region_flags"].copy()}
+
+    def genotype_matrix_device(self):
+        """(address, n_rows, n_cols, row_pitch) of a genotype-matrix result's matrix as it lies in this GPU's memory: n_rows rows
+        of row_pitch bytes, complete when this returns and valid until the result is closed."""
+        a, c, pitch = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        p = C.c_void_p()
+        _check(self._lib.vs_result_genotype_matrix_device(self._h, C.byref(a), C.byref(c), C.byref(pitch), C.byref(p)),
+               "vs_result_genotype_matrix_device")
+        return int(p.value or 0), int(a.value), int(c.value), int(pitch.value)
+
+    def region_genotypes(self, q):
+        """The rows region q of a genotype-matrix result reports (dropped ones left out): a list of dicts with pos, ref, alt and
+        `calls`, per column `0` for a non-carrier or the call as type 6 prints it (`1|1`, `0/1`, ...)."""
+        out = []
+        for line in self.region_text(q).split("\n")[1:]:
+            if not line:
+                continue
+            pos, ref, alt, *calls = line.split("\t")
+            out.append({"pos": int(pos), "ref": ref, "alt": alt, "calls": calls})
+        return out
+
     def region_variants(self, q) -> List[Variant]:
         out = []
         for line in self.region_text(q).split("\n")[1:]:
@@ -515,6 +553,25 @@ class VariantStore:
                 ids_ptr = (C.c_uint32 * 1)()
         _check(self._lib.vs_query_sample_burden(self._h, ptr, n, ids_ptr, n_ids, int(min_ac),
                                                 0xFFFFFFFF if max_ac is None else int(max_ac), C.byref(h)), "vs_query_sample_burden")
+        return QueryResult(self, h)
+
+    def genotype_matrix(self, regions, samples=None) -> QueryResult:
+        """The genotype matrix over regions (vs_query_genotype_matrix): one row per row of the variant table a type-6 batch over
+        `regions` produces, one column per sample of `samples` (names or ids, taken as a set; None: the whole cohort), a byte
+        per call.  `regions` as for allele_counts.  Read the result with QueryResult.genotype_matrix /
+        genotype_matrix_device / region_genotypes / region_text."""
+        arr, ptr, n = _regions_array(regions)
+        h = C.c_void_p()
+        if samples is None:
+            ids, ids_ptr, n_ids = None, None, 0
+        else:
+            if isinstance(samples, (str, bytes)):
+                samples = [samples]
+            ids = np.ascontiguousarray([self.sample_id(x) if isinstance(x, str) else int(x) for x in samples], dtype=np.uint32)
+            ids_ptr, n_ids = ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.shape[0]
+            if n_ids == 0:   # (the C ABI's NULL-or-non-empty rule: an empty list is not the whole cohort)
+                ids_ptr = (C.c_uint32 * 1)()
+        _check(self._lib.vs_query_genotype_matrix(self._h, ptr, n, ids_ptr, n_ids, C.byref(h)), "vs_query_genotype_matrix")
         return QueryResult(self, h)
 
     def get_sample_var_in_ref(self, regions, sample) -> QueryResult:

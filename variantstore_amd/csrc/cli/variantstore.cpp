@@ -698,7 +698,17 @@ int burden_usage() {
   return EXIT_FAILURE;
 }
 
-int counts_main(const Args& a, bool burden = false) {
+// `variantstore genotypes`: the genotype matrix of the regions (vs_query_genotype_matrix) over the same samples.  Output as `counts`:
+// "#region <i> <x>:<y>", then the region's text ("Pos Ref Alt" and a column per sample; per reported row `0` or the call).
+int genotypes_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore genotypes -p <output-prefix> -r <region> [-S <sample-name-file>] [-o <outfile>] [--device <n>]\n\n"
+               "        For every variant query type 6 reports in each region, every sample's call (of the whole cohort or of the\n"
+               "        samples named in the file): 0 for a non-carrier, else the genotype as type 6 prints it (1|1, 0/1, ...).\n";
+  return EXIT_FAILURE;
+}
+
+int counts_main(const Args& a, bool burden = false, bool genotypes = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
   if (rc != VS_OK) die(rc, "load");
@@ -723,9 +733,10 @@ int counts_main(const Args& a, bool burden = false) {
   std::vector<vs_region> batch;
   for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
   vs_result* res = nullptr;
-  if (burden) rc = vs_query_sample_burden(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.min_ac, a.max_ac, &res);
+  if (genotypes) rc = vs_query_genotype_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
+  else if (burden) rc = vs_query_sample_burden(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.min_ac, a.max_ac, &res);
   else rc = vs_query_allele_counts(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
-  if (rc != VS_OK) die(rc, burden ? "burden" : "counts");
+  if (rc != VS_OK) die(rc, genotypes ? "genotypes" : burden ? "burden" : "counts");
   std::ofstream file;
   if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
   std::ostream& out = a.outfile.empty() ? std::cout : file;
@@ -783,7 +794,7 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
@@ -801,6 +812,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "burden") {
     if (a.prefix.empty() || a.region.empty()) return burden_usage();
     return counts_main(a, /*burden=*/true);
+  }
+  if (a.cmd == "genotypes") {
+    if (a.prefix.empty() || a.region.empty()) return genotypes_usage();
+    return counts_main(a, /*burden=*/false, /*genotypes=*/true);
   }
   if (a.cmd == "construct") {
     if (a.ref.empty() || a.vcf.empty() || a.prefix.empty()) return usage();

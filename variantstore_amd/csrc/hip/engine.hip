@@ -87,6 +87,8 @@ struct EngineOpts {
   bool fill_fused = true;       // shared batches: the expansion writes the shared rows as well (k_fill_sites2); false: k_share_rows2 + k_fill_sites
   uint32_t fill_chunk = 0;      // rows per task of the expansion: 0 = by the batch's shape, else 8 / 16 / 32 / 64
   uint32_t burden_chunk = 0;    // rows one workgroup of the burden kernel walks before a region is split: 0 = kBurdenChunkRows
+  uint32_t matrix_max_mib = 0;  // largest genotype matrix a batch may ask for, MiB: 0 = 32 GiB
+  uint32_t matrix_tile_cols = 0;   // column tile of the matrix kernel: 0 = kMatrixTileCols, else a multiple of 16 in 16..65536
   int fill_mode = 0;            // shared expansion: 0 one launch, 2 split (lists + rows, then the dense sites: what a profiler wants to see apart)
   uint32_t fill_dense_k = 16;   // dense sites per wave of k_fill_dense: 8 / 16 / 32 / 64
   bool fill_stats = false;      // device-clock ticks per phase of the expansion's tasks (k_fill_sites2)
@@ -233,7 +235,7 @@ struct vs_result {
   const VariantRow* raw_rows = nullptr;
   const uint8_t* raw_arena = nullptr;   // NULL: carriers not copied
   int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts;
-                 // kKindBurden: per-sample burden
+                 // kKindBurden: per-sample burden; kKindMatrix: genotype matrix
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -244,6 +246,11 @@ struct vs_result {
   std::vector<uint32_t> h_cols;
   DevBuf cells_pin{nullptr, 0};
   std::vector<uint4> sl_cells;   // the cells of ONE region, fetched when the matrix is not on the host (vs_result_format_region)
+  // genotype-matrix results (vs_query_genotype_matrix): table rows x columns bytes in HBM, rows mx_pitch bytes apart; the nonzero
+  // total is d_cell_total, the column ids h_cols and the page-locked host copy cells_pin, as for a burden result
+  uint8_t* d_matrix = nullptr;
+  uint64_t mx_pitch = 0;
+  std::vector<uint8_t> sl_matrix;   // the rows of ONE region, fetched when the matrix is not on the host (vs_result_format_region)
   // sequence results (query types 2 and 3)
   DevSeqResult sq{};
   uint64_t seq_bytes = 0;
@@ -257,9 +264,12 @@ static int refuse_counts(const char* what) {
   return fail(VS_ERR_UNSUPPORTED, "%s: an allele-count result holds counts per row, no carrier lists (vs_result_get_allele_counts)", what);
 }
 constexpr int kKindBurden = 9;   // ... of a burden result: the rows of type 6, a regions x samples matrix instead of carrier lists
-static bool no_lists(const vs_result* r) { return r->kind == kKindCounts || r->kind == kKindBurden; }
+constexpr int kKindMatrix = 10;  // ... of a genotype-matrix result: the rows of type 6, a table rows x samples byte matrix instead of carrier lists
+static bool no_lists(const vs_result* r) { return r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix; }
 static int refuse_no_lists(const vs_result* r, const char* what) {
   if (r->kind == kKindCounts) return refuse_counts(what);
+  if (r->kind == kKindMatrix)
+    return fail(VS_ERR_UNSUPPORTED, "%s: a genotype-matrix result holds a rows x samples matrix, no carrier lists (vs_result_get_genotype_matrix)", what);
   return fail(VS_ERR_UNSUPPORTED, "%s: a burden result holds a regions x samples matrix, no carrier lists (vs_result_get_sample_burden)", what);
 }
 
@@ -1102,7 +1112,9 @@ static int capture_totals(vs_result* r) {
 // a burden batch (vs_query_sample_burden) is a count batch with a second consumer: the columns in front of each word of the mask
 // (NULL with the mask), their number, the window (0 .. UINT32_MAX: every reported row counts, k_allele_counts is not run)
 struct BurdenReq { const uint32_t* rank; uint32_t n_cols, min_ac, max_ac; };
-struct CountReq { const uint64_t* mask; uint32_t words; const BurdenReq* burden; };   // an allele-count batch: the subset's bit mask in host memory (NULL: the whole cohort)
+// a matrix batch (vs_query_genotype_matrix) is a count batch with a third consumer: the ranks as above and the number of columns
+struct MatrixReq { const uint32_t* rank; uint32_t n_cols; };
+struct CountReq { const uint64_t* mask; uint32_t words; const BurdenReq* burden; const MatrixReq* matrix = nullptr; };   // an allele-count batch: the subset's bit mask in host memory (NULL: the whole cohort)
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
                             bool allow_async, bool may_speculate = true, const CountReq* counting = nullptr);
 // A speculative batch's sizes become the plan's totals here -- or, when the plan refused the batch on the device (more rows or arena
@@ -1245,6 +1257,33 @@ static int launch_burden(vs_index* idx, vs_result* r, const uint32_t* u_site, ui
   return window ? launch_burden_kernels<false, true>(idx, a, d.Q, cap, lds) : launch_burden_kernels<false, false>(idx, a, d.Q, cap, lds);
 }
 
+// The genotype matrix of a count batch: one workgroup per (block of table rows, column tile).  The tile is at most the pitch and
+// at most kMatrixTileBytes; a block takes as many rows as fit beside it, up to one per thread.
+static int launch_matrix(vs_index* idx, vs_result* r, const uint32_t* u_site, uint64_t U, const uint64_t* d_mask, const uint32_t* d_rank, uint32_t words,
+                         const MatrixReq& mq) {
+  const DevResult& d = r->d;
+  HIP_TRY(hipMemsetAsync(r->d_cell_total, 0, 16, idx->stream));
+  if (!d.A) return VS_OK;
+  MatrixArgs a{};
+  a.rows = d.rows; a.u_site = u_site; a.A = d.A; a.U = U;
+  a.S = d_mask; a.S_rank = d_rank; a.s_words = d_mask ? words : 0;
+  a.n_cols = mq.n_cols; a.pitch = (uint32_t)r->mx_pitch;
+  a.tile_cols = std::min<uint32_t>(a.pitch, idx->opts.matrix_tile_cols ? idx->opts.matrix_tile_cols : kMatrixTileCols);
+  a.n_tiles = (a.pitch + a.tile_cols - 1) / a.tile_cols;
+  a.rows_per_block = std::max<uint32_t>(1, std::min<uint32_t>(kMatrixMaxRows, kMatrixTileBytes / a.tile_cols));
+  a.cells = r->d_matrix; a.total = r->d_cell_total;
+  const uint64_t blocks = (d.A + a.rows_per_block - 1) / a.rows_per_block * a.n_tiles;
+  if (blocks > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu row blocks x %u column tiles)",
+                                           (unsigned long long)(blocks / a.n_tiles), a.n_tiles);
+  const size_t lds = (size_t)a.rows_per_block * a.tile_cols + (d_mask ? ((size_t)words * 8 + 15) / 16 * 16 + ((size_t)words * 4 + 15) / 16 * 16 : 0) + kMatrixParamBytes;
+  const void* fn = d_mask ? reinterpret_cast<const void*>(&k_genotype_matrix<true>) : reinterpret_cast<const void*>(&k_genotype_matrix<false>);
+  if (lds > (48 << 10)) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (d_mask) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_genotype_matrix<true>), dim3((unsigned)blocks), dim3(256), lds, idx->stream, idx->d, a);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_genotype_matrix<false>), dim3((unsigned)blocks), dim3(256), lds, idx->stream, idx->d, a);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+
 // Query type 6 over a batch whose regions SHARE rows and carrier lists (every batch of more than 64 regions unless
 // option share_lists is 0).  Stages, each reading only what the stage before it left:
 //   plan   k_t6_bounds / _mid / _apply: bounds, E_prev, the per-region arrays, the row deltas, the slow-region list;
@@ -1260,6 +1299,9 @@ static int launch_burden(vs_index* idx, vs_result* r, const uint32_t* u_site, ui
 //   burden (a count batch with CountReq::burden: vs_query_sample_burden) the same, then -- behind the permutation of an unsorted batch,
 //          the matrix's rows are the regions in the caller's order -- k_allele_counts only under a window, k_sample_burden over
 //          (region, column tile) pairs, and for regions longer than a chunk k_burden_split_plan + the SPLIT launch
+//   matrix (a count batch with CountReq::matrix: vs_query_genotype_matrix) the same without k_allele_counts: behind the permutation,
+//          k_genotype_matrix over (block of table rows, column tile) pairs.  The matrix is sized from the plan's rows and refused
+//          beyond option matrix_max_mib before anything is allocated for it
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
                             bool allow_async, bool may_speculate, const CountReq* counting) {
   VS_TRY(begin_batch(idx));
@@ -1269,16 +1311,18 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   uint64_t* d_mask = nullptr;   // (an allele-count batch over a subset: its bit mask, copied with the regions)
   uint32_t* d_rank = nullptr;   // (a burden batch over a subset: the columns in front of each mask word)
   const BurdenReq* burden = counting ? counting->burden : nullptr;
+  const MatrixReq* matrix = counting ? counting->matrix : nullptr;
+  const uint32_t* h_rank = burden ? burden->rank : matrix ? matrix->rank : nullptr;
   {   // the per-region arrays of the result: one buffer
     Slab sl;
     const size_t o_reg = sl.add(2 * n * 8), o_fl = sl.add(n * sizeof(*d.q_flags)), o_g0 = sl.add(n * sizeof(*d.q_g0)), o_nv = sl.add(n * sizeof(*d.q_nvar)),
                  o_nc = sl.add(n * sizeof(*d.q_ncar)), o_vb = sl.add((n + 1) * sizeof(*d.var_begin)), o_cb = sl.add((n + 1) * sizeof(*d.car_base)),
                  o_vc = sl.add(n * sizeof(*d.var_count)), o_cl = sl.add(n * sizeof(*d.q_car_len)),
                  o_mk = sl.add(counting && counting->mask ? (size_t)counting->words * 8 : 0),
-                 o_rk = sl.add(burden && burden->rank ? (size_t)counting->words * 4 : 0);
+                 o_rk = sl.add(h_rank ? (size_t)counting->words * 4 : 0);
     VS_TRY(ralloc(r, sl.bytes, &sl.base));
     if (counting && counting->mask) d_mask = sl.at<uint64_t>(o_mk);
-    if (burden && burden->rank) d_rank = sl.at<uint32_t>(o_rk);
+    if (h_rank) d_rank = sl.at<uint32_t>(o_rk);
     dreg = sl.at<uint64_t>(o_reg);
     d.q_flags = sl.at<std::remove_pointer_t<decltype(d.q_flags)>>(o_fl); d.q_g0 = sl.at<std::remove_pointer_t<decltype(d.q_g0)>>(o_g0);
     d.q_nvar = sl.at<std::remove_pointer_t<decltype(d.q_nvar)>>(o_nv); d.q_ncar = sl.at<std::remove_pointer_t<decltype(d.q_ncar)>>(o_nc);
@@ -1304,7 +1348,7 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   else if (regions) HIP_TRY(hipMemcpyAsync(dreg, regions, n * 16, regions_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ps));
   else HIP_TRY(hipMemsetAsync(dreg, 0, n * 16, ps));
   if (d_mask) HIP_TRY(hipMemcpyAsync(d_mask, counting->mask, (size_t)counting->words * 8, hipMemcpyHostToDevice, ps));
-  if (d_rank) HIP_TRY(hipMemcpyAsync(d_rank, burden->rank, (size_t)counting->words * 4, hipMemcpyHostToDevice, ps));
+  if (d_rank) HIP_TRY(hipMemcpyAsync(d_rank, h_rank, (size_t)counting->words * 4, hipMemcpyHostToDevice, ps));
   HIP_TRY(hipEventRecord(idx->ev[0], ps));
   ScratchBufs scratch(idx);
   const bool resident = !counting && idx->opts.resident_lists && idx->res_arena;
@@ -1454,9 +1498,23 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   r->scattered_lists = false;
   r->n_unique_sites = resident || counting ? 0 : U;
   if (counting) {
+    if (matrix) {   // (the plan's rows are known: the matrix is refused here, before it or the table is allocated)
+      const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+      r->mx_pitch = ((uint64_t)matrix->n_cols + 15) & ~15ull;
+      if (d.A > cap / r->mx_pitch) {
+        (void)hipStreamSynchronize(ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+        (void)hipStreamSynchronize(idx->stream);
+        return fail(VS_ERR_ARG, "a genotype matrix of %llu rows x %u columns takes %llu bytes (rows %llu bytes apart), more than the limit of %llu MiB "
+                    "(option matrix_max_mib): split the batch", (unsigned long long)d.A, matrix->n_cols, (unsigned long long)(d.A * r->mx_pitch),
+                    (unsigned long long)r->mx_pitch, (unsigned long long)(cap >> 20));
+      }
+    }
     VS_TRY(ralloc(r, d.A, &d.rows));
     const bool window = burden && (burden->min_ac != 0 || burden->max_ac != UINT32_MAX);
-    if (!burden || window) VS_TRY(ralloc(r, d.A, &r->d_counts));   // (a burden batch: the filter's input, made only under a window)
+    if (matrix) {
+      VS_TRY(ralloc(r, (size_t)(d.A * r->mx_pitch), &r->d_matrix));
+      VS_TRY(ralloc(r, 2, &r->d_cell_total));
+    } else if (!burden || window) VS_TRY(ralloc(r, d.A, &r->d_counts));   // (a burden batch: the filter's input, made only under a window)
     if (burden) {
       VS_TRY(ralloc(r, (size_t)n * burden->n_cols, &r->d_cells));
       VS_TRY(ralloc(r, 2, &r->d_cell_total));   // (+ the number of chunks of the split regions)
@@ -1500,7 +1558,7 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
       const uint64_t waves = std::min<uint64_t>(n_slow, 16384);
       hipLaunchKernelGGL(k_count_slow_sites, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, idx->stream, d, (const uint32_t*)slow_list, n_slow, u_site);
     }
-    if (!burden) {
+    if (!burden && !matrix) {
       VS_TRY(result_events(r));
       HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
       launch_allele_counts(idx, d, u_site, U, d_mask, counting->words, r->d_counts);
@@ -1585,13 +1643,20 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
     HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
     r->pending = true;
   }
+  if (matrix) {   // the matrix, between the result's own pair of events (vs_result_fill_ms)
+    VS_TRY(result_events(r));
+    HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
+    VS_TRY(launch_matrix(idx, r, u_site, U, d_mask, d_rank, counting->words, *matrix));
+    HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
+    r->pending = true;
+  }
   if (!lean) HIP_TRY(hipEventRecord(idx->ev[4], idx->stream));
   else {   // plan: the handle's two events on the plan stream; the rest: the result's pair (no separate rows kernel: ms_emit = 0)
     idx->tev[0] = idx->ev[0]; idx->tev[1] = idx->ev[1]; idx->tev[2] = r->ev_fill[0]; idx->tev[3] = r->ev_fill[0]; idx->tev[4] = r->ev_fill[1];
     idx->timing_owner = r;
   }
   idx->timing_pending = true;
-  idx->timing_fill_launches = (n_fill || (counting && d.A) || burden) ? 1 : 0;   // (async_fill: ms_fill is what the first stream saw of it, ~0; vs_result_fill_ms has the kernel's time)
+  idx->timing_fill_launches = (n_fill || (counting && d.A) || burden || matrix) ? 1 : 0;   // (async_fill: ms_fill is what the first stream saw of it, ~0; vs_result_fill_ms has the kernel's time)
   // async_submit: the batch is enqueued, its sizes are known (the plan's totals; a speculative batch: result_sizes) and its buffers are the
   // result's -- the call returns here; the timing events are read when asked for
   if (async_submit) return batch_enqueued(r, scratch, /*record_done=*/!lean);
@@ -1843,8 +1908,8 @@ static int run_type6(vs_index* idx, const vs_region* regions, uint64_t n, vs_res
 // expansion -- every batch size, never speculative, no arena (run_type6_shared: `counting`).  mask: a bit per sample of the subset,
 // empty for the whole cohort.
 static int run_counts_batch(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const std::vector<uint64_t>& mask,
-                            const BurdenReq* burden = nullptr) {
-  const CountReq cq{mask.empty() ? nullptr : mask.data(), (uint32_t)mask.size(), burden};
+                            const BurdenReq* burden = nullptr, const MatrixReq* matrix = nullptr) {
+  const CountReq cq{mask.empty() ? nullptr : mask.data(), (uint32_t)mask.size(), burden, matrix};
   return run_type6_shared(idx, regions, n, r, regions_on_device, nullptr, /*allow_async=*/true, /*may_speculate=*/false, &cq);
 }
 
@@ -2537,6 +2602,32 @@ static int drop_result(vs_result* r, int rc) {
   return rc;
 }
 
+// The columns of a samples-wide answer (burden, genotype matrix): the subset as a bit per sample (id 0, "ref", is never a carrier),
+// the columns in front of each word of the mask, and the distinct ids, ascending.  sample_ids NULL: the whole cohort, mask and
+// rank stay empty.
+static int sample_columns(const vs_index* idx, const uint32_t* sample_ids, uint64_t n_ids, std::vector<uint64_t>& mask, std::vector<uint32_t>& rank,
+                          std::vector<uint32_t>& cols) {
+  const uint32_t ns = idx->g.num_samples;
+  if (sample_ids) {
+    mask.assign((ns + 63) / 64, 0);
+    for (uint64_t i = 0; i < n_ids; ++i) {
+      const uint32_t id = sample_ids[i];
+      if (id == 0 || id >= ns) return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u is not a sample of the cohort (1 .. %u)", id, ns - 1);
+      mask[id >> 6] |= 1ull << (id & 63);
+    }
+    rank.resize(mask.size());
+    for (size_t w = 0; w < mask.size(); ++w) {
+      rank[w] = (uint32_t)cols.size();
+      for (uint64_t m = mask[w]; m; m &= m - 1) cols.push_back((uint32_t)(w * 64 + __builtin_ctzll(m)));
+    }
+  } else {
+    if (ns < 2) return fail(VS_ERR_ARG, "the cohort has no samples");
+    cols.resize(ns - 1);
+    for (uint32_t i = 0; i + 1 < ns; ++i) cols[i] = i + 1;
+  }
+  return VS_OK;
+}
+
 // The handle of a query: present and opened with a device.
 static int query_handle(const vs_index* idx) {
   if (!idx) return fail(VS_ERR_ARG, "null argument");
@@ -2775,6 +2866,12 @@ int vs_index_set_option(vs_index* idx, const char* key, int64_t value) {
   else if (k == "burden_chunk") {
     if (value != 0 && (value < 64 || value > 65536)) return fail(VS_ERR_ARG, "burden_chunk takes 0 (default) or 64..65536 rows");
     o.burden_chunk = (uint32_t)value;
+  } else if (k == "matrix_max_mib") {
+    if (value < 0 || value > 0xFFFFFFFFll) return fail(VS_ERR_ARG, "matrix_max_mib takes 0 (default: 32 GiB) or a number of MiB");
+    o.matrix_max_mib = (uint32_t)value;
+  } else if (k == "matrix_tile_cols") {
+    if (value != 0 && (value < 16 || value > 65536 || value % 16)) return fail(VS_ERR_ARG, "matrix_tile_cols takes 0 (default) or a multiple of 16 in 16..65536");
+    o.matrix_tile_cols = (uint32_t)value;
   }
   else if (k == "lat_debug" || k == "sc_group" || k == "fill_fused" || k == "fill_chunk" || k == "fill_mode" || k == "fill_dense_k" || k == "fill_stats" || k == "walk_stats" || k == "fill_ablate" ||
            k == "fill_lds_pad") {
@@ -2903,26 +3000,9 @@ int vs_query_sample_burden(vs_index* idx, const vs_region* regions, uint64_t n, 
   if (sample_ids && n_ids == 0) return fail(VS_ERR_ARG, "an empty sample subset (pass NULL for the whole cohort)");
   if (min_ac > max_ac) return fail(VS_ERR_ARG, "an empty allele-count window [%u, %u]", min_ac, max_ac);
   const uint32_t ns = idx->g.num_samples;
-  std::vector<uint64_t> mask;    // the subset as a bit per sample (id 0, "ref", is never a carrier)
-  std::vector<uint32_t> rank;    // the columns in front of each word of the mask
-  std::vector<uint32_t> cols;    // the distinct ids, ascending
-  if (sample_ids) {
-    mask.assign((ns + 63) / 64, 0);
-    for (uint64_t i = 0; i < n_ids; ++i) {
-      const uint32_t id = sample_ids[i];
-      if (id == 0 || id >= ns) return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u is not a sample of the cohort (1 .. %u)", id, ns - 1);
-      mask[id >> 6] |= 1ull << (id & 63);
-    }
-    rank.resize(mask.size());
-    for (size_t w = 0; w < mask.size(); ++w) {
-      rank[w] = (uint32_t)cols.size();
-      for (uint64_t m = mask[w]; m; m &= m - 1) cols.push_back((uint32_t)(w * 64 + __builtin_ctzll(m)));
-    }
-  } else {
-    if (ns < 2) return fail(VS_ERR_ARG, "the cohort has no samples");
-    cols.resize(ns - 1);
-    for (uint32_t i = 0; i + 1 < ns; ++i) cols[i] = i + 1;
-  }
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));
   const uint64_t n_cols = cols.size();
   if (n > (1ull << 31) / n_cols)
     return fail(VS_ERR_ARG, "a burden matrix of %llu regions x %llu columns exceeds 2^31 cells (%llu GiB at 16 bytes a cell): split the batch",
@@ -2932,6 +3012,23 @@ int vs_query_sample_burden(vs_index* idx, const vs_region* regions, uint64_t n, 
   return make_result(idx, kKindBurden, out, [&](vs_result* r) {
     r->h_cols = cols;
     return run_counts_batch(idx, regions, n, r, is_device_ptr(regions), mask, &bq);
+  });
+}
+
+int vs_query_genotype_matrix(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, vs_result** out) {
+  // (the arguments first, as the burden entry point checks them: on the host, also on a handle opened without a device)
+  if (!idx || !out || (n && !regions) || (!sample_ids && n_ids)) return fail(VS_ERR_ARG, "null argument");
+  if (n == 0) return fail(VS_ERR_ARG, "a genotype-matrix batch needs at least one region");
+  if (sample_ids && n_ids == 0) return fail(VS_ERR_ARG, "an empty sample subset (pass NULL for the whole cohort)");
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));
+  if (mask.size() * 8 > kMatrixMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", idx->g.num_samples);
+  const MatrixReq mq{rank.empty() ? nullptr : rank.data(), (uint32_t)cols.size()};
+  return make_result(idx, kKindMatrix, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    return run_counts_batch(idx, regions, n, r, is_device_ptr(regions), mask, nullptr, &mq);
   });
 }
 
@@ -3079,6 +3176,20 @@ static int cells_to_host(vs_result* r) {
   const hipError_t e = hipMemcpyAsync(b.p, r->d_cells, bytes, hipMemcpyDeviceToHost, idx->stream);
   const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(idx->stream) : e;
   if (e2 != hipSuccess) { pin_release(idx, b); return fail(VS_ERR_HIP, "copy of the burden matrix failed: %s", hipGetErrorString(e2)); }
+  r->cells_pin = b;
+  return VS_OK;
+}
+// A genotype-matrix result's matrix, pitch and all, in page-locked memory owned by the result (the caller has passed the gate).
+static int matrix_to_host(vs_result* r) {
+  if (r->cells_pin.p) return VS_OK;
+  vs_index* idx = r->idx;
+  VS_TRY(result_ready(r));
+  const size_t bytes = (size_t)(r->d.A * r->mx_pitch);
+  DevBuf b{nullptr, 0};
+  VS_TRY(pin_alloc(idx, bytes + 16, &b));
+  const hipError_t e = bytes ? hipMemcpyAsync(b.p, r->d_matrix, bytes, hipMemcpyDeviceToHost, idx->stream) : hipSuccess;
+  const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(idx->stream) : e;
+  if (e2 != hipSuccess) { pin_release(idx, b); return fail(VS_ERR_HIP, "copy of the genotype matrix failed: %s", hipGetErrorString(e2)); }
   r->cells_pin = b;
   return VS_OK;
 }
@@ -3255,7 +3366,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
         for (uint64_t a = r->h_var_begin[q], e = a + r->h_nvar[q]; a < e; ++a) nc += c[a].x;
       r->n_carriers_kept = nc;
     }
-    if (r->kind == kKindBurden) {   // the sum of `variants` over the matrix: the burden kernels' own word
+    if (r->kind == kKindBurden || r->kind == kKindMatrix) {   // the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
       VS_TRY(result_ready(r));
       uint64_t nc = 0;
       HIP_TRY(hipMemcpyAsync(&nc, r->d_cell_total, 8, hipMemcpyDeviceToHost, idx->stream));
@@ -3307,6 +3418,54 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
       const uint32_t id = r->h_cols[k];
       out += id < idx->g.sample_names.size() ? idx->g.sample_names[id] : std::string("?");
       for (uint32_t f : {c[k].x, c[k].y, c[k].z, c[k].w}) { out += '\t'; out += std::to_string(f); }
+      out += '\n';
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
+  if (r->kind == kKindMatrix) {   // the region's reported rows, a genotype per column
+    const size_t nc = r->h_cols.size(), pitch = (size_t)r->mx_pitch;
+    const VariantRow* rows;
+    if (r->have_headers) rows = r->h_rows.data() + a0;
+    else if (r->raw_rows) rows = r->raw_rows + a0;
+    else {
+      VS_TRY(fetch(idx, r->sl_rows, (const VariantRow*)r->d.rows + a0, (size_t)(a1 - a0)));
+      rows = r->sl_rows.data();
+    }
+    const uint8_t* c;
+    if (r->cells_pin.p) c = (const uint8_t*)r->cells_pin.p + a0 * pitch;
+    else {
+      VS_TRY(result_ready(r));
+      VS_TRY(fetch(idx, r->sl_matrix, (const uint8_t*)r->d_matrix + a0 * pitch, (size_t)(a1 - a0) * pitch));
+      c = r->sl_matrix.data();
+    }
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    std::string& out = r->text;
+    out = "Pos\tRef\tAlt";
+    for (size_t k = 0; k < nc; ++k) {
+      const uint32_t id = r->h_cols[k];
+      out += '\t';
+      out += id < idx->g.sample_names.size() ? idx->g.sample_names[id] : std::string("?");
+    }
+    out += '\n';
+    for (uint64_t a = a0; a < a1; ++a) {
+      const VariantRow& v = rows[a - a0];
+      if (v.count_flags & kRowDropped) continue;
+      out += std::to_string(v.pos);
+      out += '\t';
+      out.append(idx->seq_chars, v.ref_off, v.ref_len);
+      out += '\t';
+      out.append(idx->seq_chars, v.alt_off, v.alt_len);
+      const uint8_t* m = c + (a - a0) * pitch;
+      for (size_t k = 0; k < nc; ++k) {
+        out += '\t';
+        const uint32_t gt = m[k];
+        if (!gt) { out += '0'; continue; }
+        out += (gt & GT_1) ? '1' : '0';   // the characters of print_var
+        out += (gt & GT_PHASE) ? '|' : '/';
+        out += (gt & GT_2) ? '1' : '0';
+      }
       out += '\n';
     }
     *text = out.c_str();
@@ -3464,6 +3623,32 @@ int vs_result_sample_burden_device(vs_result* r, uint64_t* n_regions, uint64_t* 
   *dev_cells = r->d_cells;
   if (n_regions) *n_regions = r->d.Q;
   if (n_cols) *n_cols = r->h_cols.size();
+  return VS_OK;
+}
+
+int vs_result_get_genotype_matrix(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint64_t* row_pitch, const uint32_t** col_ids, const uint8_t** cells) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!cells) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindMatrix) return fail(VS_ERR_ARG, "not a genotype-matrix result (vs_query_genotype_matrix)");
+  VS_TRY(matrix_to_host(r));
+  *cells = (const uint8_t*)r->cells_pin.p;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (row_pitch) *row_pitch = r->mx_pitch;
+  if (col_ids) *col_ids = r->h_cols.data();
+  return VS_OK;
+}
+
+int vs_result_genotype_matrix_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint64_t* row_pitch, const void** dev_cells) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!dev_cells) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindMatrix) return fail(VS_ERR_ARG, "not a genotype-matrix result (vs_query_genotype_matrix)");
+  VS_TRY(result_ready(r));
+  HIP_TRY(hipStreamSynchronize(r->idx->stream));   // the matrix is complete when the pointer is handed out: the caller needs no event
+  *dev_cells = r->d_matrix;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (row_pitch) *row_pitch = r->mx_pitch;
   return VS_OK;
 }
 

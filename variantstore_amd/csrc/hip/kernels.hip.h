@@ -55,6 +55,8 @@
 //  k_count_slow_sites    counterpart; what a caller of type 6 would count on the host from the carrier lists)
 // k_sample_burden       the same counts along the other axis: a regions x samples matrix over each region's reported rows
 //  k_burden_split_plan   (vs_query_sample_burden: no reference counterpart); the chunks of the regions too long for one workgroup
+// k_genotype_matrix     what both reduce: table rows x samples, a byte per call, each (row block, column tile) built in LDS and
+//                       stored once (vs_query_genotype_matrix: no reference counterpart)
 #pragma once
 #include "k_image.hip.h"
 #include "k_sites.hip.h"
@@ -68,3 +70,4 @@
 #include "k_digest.hip.h"
 #include "k_counts.hip.h"
 #include "k_burden.hip.h"
+#include "k_matrix.hip.h"
