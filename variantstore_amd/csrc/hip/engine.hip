@@ -782,12 +782,19 @@ static int ralloc(vs_result* r, size_t n, T** p) {
 }
 
 // Several arrays out of ONE pooled buffer (every allocation is a search of the handle's pool, and a batch of a tenth of a
-// millisecond makes sixteen of them): sizes are added up, the buffer is taken once, the arrays are carved on 256-byte bounds.
+// millisecond makes sixteen of them): want() registers an array -- its pointer, its elements -- and adds up the sizes, the buffer of
+// `bytes` is taken once into `base`, carve() then points every registered array into it, in that order, on 256-byte bounds.
 struct Slab {
+  struct Part { void* ptr; size_t off; void (*set)(void* ptr, uint8_t* at); };
   size_t bytes = 0;
   uint8_t* base = nullptr;
-  size_t add(size_t b) { const size_t at = bytes; bytes += (b + 255) & ~(size_t)255; return at; }
-  template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(base + off); }
+  Part parts[16];   // (a shared batch registers eleven)
+  int n_parts = 0;
+  template <typename T> void want(T*& p, size_t count) {
+    parts[n_parts++] = Part{&p, bytes, [](void* ptr, uint8_t* at) { *static_cast<T**>(ptr) = reinterpret_cast<T*>(at); }};
+    bytes += (count * sizeof(T) + 255) & ~(size_t)255;
+  }
+  void carve() const { for (int i = 0; i < n_parts; ++i) parts[i].set(parts[i].ptr, base + parts[i].off); }
 };
 
 // Strings of a type-7 batch (ref, alt per query) as one byte pool + [2n+1] offsets.
@@ -1109,14 +1116,21 @@ static int capture_totals(vs_result* r) {
   else { idx->sort_hint = true; idx->sort_probe_in = 32; }   // (as after a batch that was sorted on the device: the next ones sort first -- also when nobody reads this one)
   return VS_OK;
 }
-// a burden batch (vs_query_sample_burden) is a count batch with a second consumer: the columns in front of each word of the mask
-// (NULL with the mask), their number, the window (0 .. UINT32_MAX: every reported row counts, k_allele_counts is not run)
-struct BurdenReq { const uint32_t* rank; uint32_t n_cols, min_ac, max_ac; };
-// a matrix batch (vs_query_genotype_matrix) is a count batch with a third consumer: the ranks as above and the number of columns
-struct MatrixReq { const uint32_t* rank; uint32_t n_cols; };
-struct CountReq { const uint64_t* mask; uint32_t words; const BurdenReq* burden; const MatrixReq* matrix = nullptr; };   // an allele-count batch: the subset's bit mask in host memory (NULL: the whole cohort)
+// What a shared batch (run_type6_shared) is for: the type-6 expansion of carrier lists, or one of the three column requests over
+// the same rows -- allele counts, the burden matrix, the genotype matrix.  The columns: the subset's bit mask in host memory (NULL:
+// the whole cohort) and its words; for burden and matrix the columns in front of each word of the mask (NULL with the mask) and
+// their number; for burden the window (0 .. UINT32_MAX: every reported row counts, k_allele_counts is not run).
+enum class ReqKind { Lists, Counts, Burden, Matrix };
+struct SharedReq {
+  ReqKind kind = ReqKind::Lists;
+  const uint64_t* mask = nullptr;
+  uint32_t words = 0;
+  const uint32_t* rank = nullptr;
+  uint32_t n_cols = 0, min_ac = 0, max_ac = UINT32_MAX;
+  bool window() const { return min_ac != 0 || max_ac != UINT32_MAX; }
+};
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
-                            bool allow_async, bool may_speculate = true, const CountReq* counting = nullptr);
+                            bool allow_async, bool may_speculate = true, const SharedReq& req = SharedReq{});
 // A speculative batch's sizes become the plan's totals here -- or, when the plan refused the batch on the device (more rows or arena
 // entries than were allocated, or regions that were not sorted), the batch is run again from the result's own copy of the regions,
 // with the exact sizes, before anything is read.  A redo that fails leaves the result torn: its code sticks (vs_result::redo_rc).
@@ -1225,12 +1239,12 @@ static int launch_burden_kernels(vs_index* idx, const BurdenArgs& a, uint64_t Q,
   HIP_TRY(hipGetLastError());
   return VS_OK;
 }
-static int launch_burden(vs_index* idx, vs_result* r, const uint32_t* u_site, uint64_t U, const uint64_t* d_mask, const uint32_t* d_rank, uint32_t words,
-                         const BurdenReq& bq, ScratchBufs& scratch) {
+static int launch_burden(vs_index* idx, vs_result* r, const uint32_t* u_site, uint64_t U, const uint64_t* d_mask, const uint32_t* d_rank, const SharedReq& bq,
+                         ScratchBufs& scratch) {
   const DevResult& d = r->d;
   BurdenArgs a{};
   a.rows = d.rows; a.u_site = u_site; a.U = U; a.var_begin = d.var_begin; a.q_nvar = d.q_nvar;
-  a.S = d_mask; a.S_rank = d_rank; a.s_words = d_mask ? words : 0;
+  a.S = d_mask; a.S_rank = d_rank; a.s_words = d_mask ? bq.words : 0;
   a.ac = r->d_counts; a.min_ac = bq.min_ac; a.max_ac = bq.max_ac;
   a.n_cols = bq.n_cols;
   a.tile_cols = std::min<uint32_t>(bq.n_cols, kBurdenTileCols);
@@ -1259,9 +1273,9 @@ static int launch_burden(vs_index* idx, vs_result* r, const uint32_t* u_site, ui
 
 // The genotype matrix of a count batch: one workgroup per (block of table rows, column tile).  The tile is at most the pitch and
 // at most kMatrixTileBytes; a block takes as many rows as fit beside it, up to one per thread.
-static int launch_matrix(vs_index* idx, vs_result* r, const uint32_t* u_site, uint64_t U, const uint64_t* d_mask, const uint32_t* d_rank, uint32_t words,
-                         const MatrixReq& mq) {
+static int launch_matrix(vs_index* idx, vs_result* r, const uint32_t* u_site, uint64_t U, const uint64_t* d_mask, const uint32_t* d_rank, const SharedReq& mq) {
   const DevResult& d = r->d;
+  const uint32_t words = mq.words;
   HIP_TRY(hipMemsetAsync(r->d_cell_total, 0, 16, idx->stream));
   if (!d.A) return VS_OK;
   MatrixArgs a{};
@@ -1284,50 +1298,105 @@ static int launch_matrix(vs_index* idx, vs_result* r, const uint32_t* u_site, ui
   return VS_OK;
 }
 
-// Query type 6 over a batch whose regions SHARE rows and carrier lists (every batch of more than 64 regions unless
-// option share_lists is 0).  Stages, each reading only what the stage before it left:
-//   plan   k_t6_bounds / _mid / _apply: bounds, E_prev, the per-region arrays, the row deltas, the slow-region list;
-//          the totals arrive in mapped host memory and the host spins on their sequence word (the one host wait of a batch)
-//   (sort  a batch that turns out not to be sorted by first site is sorted on the device and planned again)
-//   rows   k_t6_slow (private copies + the literal duplicate rule, only when the plan counted such regions)
-//   fill   k_fill_sites2: the shared rows AND their carrier lists, one launch; with resident lists k_share_rows2 alone;
-//          with async_fill k_share_rows2 here and k_fill_sites on the second stream
-//   done   k_post_done: a word in mapped host memory, the host spins on it
-//   counts (an allele-count batch, `counting`: vs_query_allele_counts) instead of the expansion: k_share_rows2 with the site of every
-//          row, k_count_slow_sites for the private rows, k_allele_counts.  Never speculative, no arena, and it leaves the handle's
-//          type-6 state (size hints, sort hint) as it found it: count batches interleaved with type-6 batches change none of theirs
-//   burden (a count batch with CountReq::burden: vs_query_sample_burden) the same, then -- behind the permutation of an unsorted batch,
-//          the matrix's rows are the regions in the caller's order -- k_allele_counts only under a window, k_sample_burden over
-//          (region, column tile) pairs, and for regions longer than a chunk k_burden_split_plan + the SPLIT launch
-//   matrix (a count batch with CountReq::matrix: vs_query_genotype_matrix) the same without k_allele_counts: behind the permutation,
-//          k_genotype_matrix over (block of table rows, column tile) pairs.  The matrix is sized from the plan's rows and refused
-//          beyond option matrix_max_mib before anything is allocated for it
-static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
-                            bool allow_async, bool may_speculate, const CountReq* counting) {
+// ---------------------------------------------------------------------------------------------------------------------
+// Query type 6 over a batch whose regions SHARE rows and carrier lists (every batch of more than 64 regions unless option
+// share_lists is 0), and every count, burden and genotype-matrix batch: the same plan and rows, another consumer (SharedReq).
+// Like the private-row batches further down it runs as stages over a context, each a function that reads only what the
+// stages before it left in the SharedCtx:
+//   shared_setup       per-region arrays, regions / mask / ranks on the device, the decisions taken up front, the plan's temporaries
+//   shared_plan_batch  shared_plan = k_t6_bounds / _mid / _totals / _apply: bounds, E_prev, the per-region arrays, the row deltas, the
+//                      slow-region list; the totals arrive in mapped host memory and the host spins on their sequence word (the one
+//                      host wait of a batch; a speculative batch does not wait).  A batch that turns out not to be sorted by first
+//                      site is sorted on the device (shared_sort) and planned again; a handle whose last batch was, sorts first
+//   shared_tables      sizes from the totals or the speculation; the table and, by the request's kind, arena | counts | burden cells
+//                      (counts only under a window) | the matrix, refused beyond option matrix_max_mib before anything is allocated
+//   shared_rows        k_t6_slow (private copies + the literal duplicate rule, only when the plan counted such regions), k_share_rows2
+//                      unless the expansion writes the rows itself; a column request: the site of every row (k_count_slow_sites)
+//   shared_expand      Lists: k_fill_sites2, the shared rows AND their carrier lists in one launch -- with async_fill k_fill_sites on
+//                      the second stream, with resident lists nothing | shared_counts  Counts: k_allele_counts over the table
+//   shared_permute_out an unsorted batch's per-region arrays back in the caller's order
+//   shared_cells       Burden, Matrix, behind the permutation -- the matrix's rows are the regions in the caller's order: k_allele_counts
+//                      only under a window, k_sample_burden over (region, column tile) pairs and for regions longer than a chunk
+//                      k_burden_split_plan + the SPLIT launch | k_genotype_matrix over (block of table rows, column tile) pairs
+//   shared_finish      enqueued: the completion event | synchronous: k_post_done, a word in mapped host memory, the host spins on it
+// A column request is never speculative, has no arena, and leaves the handle's type-6 state (size hints, sort hint) as it found
+// it: count batches interleaved with type-6 batches change none of theirs.
+// ---------------------------------------------------------------------------------------------------------------------
+struct SharedCtx {
+  vs_index* idx;
+  vs_result* r;
+  uint64_t n;
+  const SharedReq& req;
+  ScratchBufs scratch;
+  // the consumer, asked once: Lists -- carrier lists in an arena (the result's or the resident one), may speculate, owns the handle's
+  // type-6 hints; else a column request -- no arena, never speculative, hints untouched, the site of EVERY row (u_site).  Burden and
+  // Matrix are consumed behind k_permute_out, Lists and Counts in front of it
+  const bool lists, behind_perm;
+  // shared_setup: the decisions taken up front
+  bool allow_async = false, async_submit = false, sort_first = false, plan_aside = false, resident = false, spec = false;
+  hipStream_t ps = nullptr;                // the plan's stream: the handle's own unless plan_aside
+  const uint64_t* regions_dev = nullptr;   // regions already in device memory are copied by the kernel that reads them first: k_t6_bounds
+  const uint64_t* site_records = nullptr;
+  int slot = -1;                           // speculative: the batch's mailbox in the ring
+  PlanTotals* pt = nullptr;
+  uint64_t want_rows = 0, want_arena = 0;
+  uint64_t* d_mask = nullptr;   // a column request over a subset: its bit mask, copied with the regions
+  uint32_t* d_rank = nullptr;   // (burden, matrix) the columns in front of each mask word
+  // the plan's temporaries (e_prev_c: the arena prefix at E_prev, carried by the same scan -- k_rows.hip.h: ShareMax)
+  uint32_t items = 0, ntiles = 0, *e_prev = nullptr, *status = nullptr, *slow_list = nullptr, *coarse = nullptr;
+  uint64_t* e_prev_c = nullptr;
+  ShareMax* tile_max = nullptr;
+  Scan5* tile_sums = nullptr;
+  RunRec* runs = nullptr;
+  PlanDev* plan_dev = nullptr;
+  DevResult d_user{};        // shared_sort: the caller's per-region arrays while an unsorted batch works on sorted copies
+  uint32_t* perm = nullptr;  // sorted position -> region of the caller's batch (NULL: the batch is worked in the order given)
+  bool plan_end_enqueued = false;   // ev[1] recorded behind the (last) plan and waited for by the handle's stream
+  uint64_t plan_seq = 0, U = 0, n_slow = 0, n_runs = 0;   // what the plan produced
+  uint64_t n_fill = 0;          // shared_tables: carrier lists to expand, and the form of the rows and the expansion
+  bool async_fill = false, fused = false, lean = false;
+  uint32_t* u_site = nullptr;   // shared_rows: the site of every shared row (a column request: of every row)
+  uint32_t fill_launches = 0;   // the consumer's, for the phase times
+  SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
+      : idx(i), r(res), n(nn), req(q), scratch(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix) {}
+};
+
+// The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
+// result, shared_sort takes the sorted copies from the pool.
+template <typename F>
+static int region_arrays(DevResult& d, uint64_t** regions, uint64_t n, F&& f) {
+  VS_TRY(f(regions, 2 * n)); VS_TRY(f(&d.q_flags, n)); VS_TRY(f(&d.q_g0, n)); VS_TRY(f(&d.q_nvar, n)); VS_TRY(f(&d.q_ncar, n));
+  VS_TRY(f(&d.var_begin, n + 1)); VS_TRY(f(&d.car_base, n + 1)); VS_TRY(f(&d.var_count, n)); VS_TRY(f(&d.q_car_len, n));
+  return VS_OK;
+}
+// The table and the arena of a list batch, of the sizes in d.A / d.S (resident lists: the index's arena).
+static int shared_list_tables(SharedCtx& c) {
+  DevResult& d = c.r->d;
+  VS_TRY(ralloc(c.r, d.A, &d.rows));
+  if (c.resident) { d.carriers = c.idx->res_arena; return VS_OK; }
+  uint8_t* arena = nullptr;
+  VS_TRY(ralloc(c.r, d.S * d.car_width + 16, &arena));
+  d.carriers = arena;
+  return VS_OK;
+}
+
+// Leaves: the result's per-region arrays, regions (mask, ranks) on their way to the device behind ev[0], every decision of the
+// context's first block, the plan's temporaries -- and a speculative batch's slot, table and arena.
+static int shared_setup(SharedCtx& c, const vs_region* regions, bool regions_on_device, bool may_speculate) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t n = c.n;
+  const SharedReq& q = c.req;
   VS_TRY(begin_batch(idx));
   DevResult& d = r->d;
   d.Q = n;
   uint64_t* dreg = nullptr;
-  uint64_t* d_mask = nullptr;   // (an allele-count batch over a subset: its bit mask, copied with the regions)
-  uint32_t* d_rank = nullptr;   // (a burden batch over a subset: the columns in front of each mask word)
-  const BurdenReq* burden = counting ? counting->burden : nullptr;
-  const MatrixReq* matrix = counting ? counting->matrix : nullptr;
-  const uint32_t* h_rank = burden ? burden->rank : matrix ? matrix->rank : nullptr;
   {   // the per-region arrays of the result: one buffer
     Slab sl;
-    const size_t o_reg = sl.add(2 * n * 8), o_fl = sl.add(n * sizeof(*d.q_flags)), o_g0 = sl.add(n * sizeof(*d.q_g0)), o_nv = sl.add(n * sizeof(*d.q_nvar)),
-                 o_nc = sl.add(n * sizeof(*d.q_ncar)), o_vb = sl.add((n + 1) * sizeof(*d.var_begin)), o_cb = sl.add((n + 1) * sizeof(*d.car_base)),
-                 o_vc = sl.add(n * sizeof(*d.var_count)), o_cl = sl.add(n * sizeof(*d.q_car_len)),
-                 o_mk = sl.add(counting && counting->mask ? (size_t)counting->words * 8 : 0),
-                 o_rk = sl.add(h_rank ? (size_t)counting->words * 4 : 0);
+    (void)region_arrays(d, &dreg, n, [&](auto** p, uint64_t k) { sl.want(*p, k); return VS_OK; });
+    if (q.mask) sl.want(c.d_mask, q.words);
+    if (q.rank) sl.want(c.d_rank, q.words);
     VS_TRY(ralloc(r, sl.bytes, &sl.base));
-    if (counting && counting->mask) d_mask = sl.at<uint64_t>(o_mk);
-    if (h_rank) d_rank = sl.at<uint32_t>(o_rk);
-    dreg = sl.at<uint64_t>(o_reg);
-    d.q_flags = sl.at<std::remove_pointer_t<decltype(d.q_flags)>>(o_fl); d.q_g0 = sl.at<std::remove_pointer_t<decltype(d.q_g0)>>(o_g0);
-    d.q_nvar = sl.at<std::remove_pointer_t<decltype(d.q_nvar)>>(o_nv); d.q_ncar = sl.at<std::remove_pointer_t<decltype(d.q_ncar)>>(o_nc);
-    d.var_begin = sl.at<std::remove_pointer_t<decltype(d.var_begin)>>(o_vb); d.car_base = sl.at<std::remove_pointer_t<decltype(d.car_base)>>(o_cb);
-    d.var_count = sl.at<std::remove_pointer_t<decltype(d.var_count)>>(o_vc); d.q_car_len = sl.at<std::remove_pointer_t<decltype(d.q_car_len)>>(o_cl);
+    sl.carve();
   }
   d.regions = dreg;
   // async_submit: the PLAN of this batch runs on a stream of its own -- beside the expansion of the batch before it, which
@@ -1336,238 +1405,285 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   // was enqueued keeps its temporaries until its completion event, vs_result::ev_done), so its buffers are its own.  The
   // rest of the batch (rows, expansion) goes to the handle's stream behind an event.  Not for a handle that sorts first,
   // not with async_fill (whose second stream plays the opposite game).
-  const bool async_submit = allow_async && idx->opts.async_submit && !idx->opts.async_fill && !idx->opts.lat_debug;
-  const bool sort_first = !counting && idx->sort_hint && idx->sort_probe_in > 0;
-  bool plan_aside = async_submit && !sort_first;
-  if (plan_aside) VS_TRY(ensure_plan_stream(idx));
-  hipStream_t ps = plan_aside ? idx->plan_stream : idx->stream;
-  // (regions already in device memory are copied by the kernel that reads them first: k_t6_bounds)
-  const uint64_t* regions_dev = regions && regions_on_device && !site_records && (reinterpret_cast<uintptr_t>(regions) & 15) == 0
-                                    ? reinterpret_cast<const uint64_t*>(regions) : nullptr;
-  if (regions_dev) {}
-  else if (regions) HIP_TRY(hipMemcpyAsync(dreg, regions, n * 16, regions_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ps));
-  else HIP_TRY(hipMemsetAsync(dreg, 0, n * 16, ps));
-  if (d_mask) HIP_TRY(hipMemcpyAsync(d_mask, counting->mask, (size_t)counting->words * 8, hipMemcpyHostToDevice, ps));
-  if (d_rank) HIP_TRY(hipMemcpyAsync(d_rank, h_rank, (size_t)counting->words * 4, hipMemcpyHostToDevice, ps));
-  HIP_TRY(hipEventRecord(idx->ev[0], ps));
-  ScratchBufs scratch(idx);
-  const bool resident = !counting && idx->opts.resident_lists && idx->res_arena;
-  // ---- plan ----
-  uint32_t items = (uint32_t)((n + (uint64_t)kPlanBlock * kPlanMaxTiles - 1) / ((uint64_t)kPlanBlock * kPlanMaxTiles));
-  if (n >= 65536 && items < idx->opts.plan_items) items = idx->opts.plan_items;   // (regions per thread of the plan's kernels: see EngineOpts::plan_items)
-  const uint32_t ntiles = (uint32_t)((n + (uint64_t)kPlanBlock * items - 1) / ((uint64_t)kPlanBlock * items));
-  ShareMax* tile_max = nullptr;
-  Scan5* tile_sums = nullptr;
-  uint32_t *e_prev = nullptr, *status = nullptr, *slow_list = nullptr;
-  uint64_t* e_prev_c = nullptr;   // the arena prefix at E_prev, carried by the same scan (k_rows.hip.h: ShareMax)
-  RunRec* runs = nullptr;
-  uint32_t* coarse = nullptr;
-  PlanDev* plan_dev = nullptr;
+  c.async_submit = c.allow_async && idx->opts.async_submit && !idx->opts.async_fill && !idx->opts.lat_debug;
+  c.sort_first = c.lists && idx->sort_hint && idx->sort_probe_in > 0;
+  c.plan_aside = c.async_submit && !c.sort_first;
+  if (c.plan_aside) VS_TRY(ensure_plan_stream(idx));
+  c.ps = c.plan_aside ? idx->plan_stream : idx->stream;
+  c.regions_dev = regions && regions_on_device && !c.site_records && (reinterpret_cast<uintptr_t>(regions) & 15) == 0
+                      ? reinterpret_cast<const uint64_t*>(regions) : nullptr;
+  if (c.regions_dev) {}
+  else if (regions) HIP_TRY(hipMemcpyAsync(dreg, regions, n * 16, regions_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.ps));
+  else HIP_TRY(hipMemsetAsync(dreg, 0, n * 16, c.ps));
+  if (c.d_mask) HIP_TRY(hipMemcpyAsync(c.d_mask, q.mask, (size_t)q.words * 8, hipMemcpyHostToDevice, c.ps));
+  if (c.d_rank) HIP_TRY(hipMemcpyAsync(c.d_rank, q.rank, (size_t)q.words * 4, hipMemcpyHostToDevice, c.ps));
+  HIP_TRY(hipEventRecord(idx->ev[0], c.ps));
+  c.resident = c.lists && idx->opts.resident_lists && idx->res_arena;
+  c.items = (uint32_t)((n + (uint64_t)kPlanBlock * kPlanMaxTiles - 1) / ((uint64_t)kPlanBlock * kPlanMaxTiles));
+  if (n >= 65536 && c.items < idx->opts.plan_items) c.items = idx->opts.plan_items;   // (regions per thread of the plan's kernels: see EngineOpts::plan_items)
+  c.ntiles = (uint32_t)((n + (uint64_t)kPlanBlock * c.items - 1) / ((uint64_t)kPlanBlock * c.items));
   {   // the plan's temporaries: one buffer
     Slab sl;
-    const size_t o_co = sl.add((idx->d.G / kCoarseRows + 2) * 4), o_tm = sl.add(ntiles * sizeof(ShareMax)),
-                 o_ts = sl.add((ntiles + 1) * sizeof(Scan5)),   // (+ the totals: k_t6_totals)
-                 o_ep = sl.add(n * 4), o_st = sl.add(4), o_sl = sl.add(n * 4), o_ru = sl.add((n + 1) * sizeof(RunRec)), o_pd = sl.add(sizeof(PlanDev)),
-                 o_ec = sl.add(n * 8);
-    VS_TRY(dev_alloc(idx, sl.bytes, (void**)&sl.base, &scratch.bufs));
-    coarse = sl.at<uint32_t>(o_co); tile_max = sl.at<ShareMax>(o_tm); tile_sums = sl.at<Scan5>(o_ts);
-    e_prev = sl.at<uint32_t>(o_ep); status = sl.at<uint32_t>(o_st); slow_list = sl.at<uint32_t>(o_sl); runs = sl.at<RunRec>(o_ru);
-    plan_dev = sl.at<PlanDev>(o_pd); e_prev_c = sl.at<uint64_t>(o_ec);
+    sl.want(c.coarse, idx->d.G / kCoarseRows + 2); sl.want(c.tile_max, c.ntiles);
+    sl.want(c.tile_sums, c.ntiles + 1);   // (+ the totals: k_t6_totals)
+    sl.want(c.e_prev, n); sl.want(c.status, 1); sl.want(c.slow_list, n); sl.want(c.runs, n + 1); sl.want(c.plan_dev, 1); sl.want(c.e_prev_c, n);
+    VS_TRY(dev_alloc(idx, sl.bytes, (void**)&sl.base, &c.scratch.bufs));
+    sl.carve();
   }
   // SPECULATIVE (round 6, option t6_speculate): the default batch -- async_submit, rows and lists in one launch, regions given as regions --
   // on a handle whose previous shared batch was about this size does not wait for the plan's totals: table and arena are sized from that
   // batch (+ 1/8), k_t6_totals leaves the totals and its verdict in device memory for the kernels behind it (PlanDev) and in this batch's
   // own mailbox for the host, which reads it when the result is first asked for anything (result_sizes) -- and redoes a refused batch.
-  const uint64_t want_rows = idx->t6_hint_rows, want_arena = idx->t6_hint_arena;
-  const bool spec = may_speculate && !counting && idx->opts.t6_speculate && plan_aside && regions && !site_records && !resident && idx->opts.fill_fused && !idx->opts.fill_mode &&
-                    !idx->opts.fill_stats && !idx->opts.lat_debug && want_rows > 0 && idx->t6_hint_n > 0 && n * 4 <= idx->t6_hint_n * 5 && n * 5 >= idx->t6_hint_n * 4;
-  int slot = -1;
-  if (spec) {
-    slot = (int)(idx->plan_slot_next++ % vs_index::kPlanSlots);
-    if (idx->plan_slot_owner[slot]) VS_TRY(capture_totals(idx->plan_slot_owner[slot]));   // (eight batches back: long done; its totals move into the result)
+  c.want_rows = idx->t6_hint_rows; c.want_arena = idx->t6_hint_arena;
+  c.spec = may_speculate && c.lists && idx->opts.t6_speculate && c.plan_aside && regions && !c.site_records && !c.resident && idx->opts.fill_fused && !idx->opts.fill_mode &&
+           !idx->opts.fill_stats && !idx->opts.lat_debug && c.want_rows > 0 && idx->t6_hint_n > 0 && n * 4 <= idx->t6_hint_n * 5 && n * 5 >= idx->t6_hint_n * 4;
+  if (c.spec) {
+    c.slot = (int)(idx->plan_slot_next++ % vs_index::kPlanSlots);
+    if (idx->plan_slot_owner[c.slot]) VS_TRY(capture_totals(idx->plan_slot_owner[c.slot]));   // (eight batches back: long done; its totals move into the result)
   }
-  PlanTotals* pt = reinterpret_cast<PlanTotals*>(idx->pinned + (spec ? vs_index::kPinPlanRing + (size_t)slot * 8 : vs_index::kPinPlan));
+  c.pt = reinterpret_cast<PlanTotals*>(idx->pinned + (c.spec ? vs_index::kPinPlanRing + (size_t)c.slot * 8 : vs_index::kPinPlan));
   d.car_width = idx->d.wpc <= 63 ? 2 : 4;
-  if (spec) {   // table and arena BEFORE the plan: the rows of the regions under the duplicate rule are written on the plan's stream (k_t6_slow below)
-    d.A = want_rows; d.S = want_arena;
-    VS_TRY(ralloc(r, d.A, &d.rows));
-    uint8_t* arena = nullptr;
-    VS_TRY(ralloc(r, d.S * d.car_width + 16, &arena));
-    d.carriers = arena;
+  if (c.spec) {   // table and arena BEFORE the plan: the rows of the regions under the duplicate rule are written on the plan's stream (shared_plan)
+    d.A = c.want_rows; d.S = c.want_arena;
+    VS_TRY(shared_list_tables(c));
   }
-  auto launch_bounds = [&](int src) {
-    if (src == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_t6_bounds<0>), dim3(ntiles), dim3(kPlanBlock), 0, ps, idx->d, d, regions_dev, items, tile_max, status);
-    else if (src == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_t6_bounds<1>), dim3(ntiles), dim3(kPlanBlock), 0, ps, idx->d, d, site_records, items, tile_max, status);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_t6_bounds<2>), dim3(ntiles), dim3(kPlanBlock), 0, ps, idx->d, d, (const uint64_t*)nullptr, items, tile_max, status);
-  };
-  // the plan over the regions as they stand in `d`; the totals arrive in mapped host memory
-  bool plan_end_enqueued = false;   // ev[1] recorded behind the (last) plan and waited for by the handle's stream
-  uint64_t plan_seq = 0;
-  auto plan = [&](int src) -> int {
-    plan_end_enqueued = false;
-    launch_bounds(src);   // (block 0 clears `status`)
-    hipLaunchKernelGGL(k_t6_mid, dim3(ntiles), dim3(kPlanBlock), 0, ps, idx->d, d, (const ShareMax*)tile_max, items, e_prev, e_prev_c, tile_sums, status);
-    const uint64_t seq = ++idx->share_seq;
-    hipLaunchKernelGGL(k_t6_totals, dim3(1), dim3(kPlanBlock), 0, ps, tile_sums, ntiles, (const uint32_t*)status, pt, seq, idx->res_entries, resident ? 1u : 0u,
-                       spec ? plan_dev : (PlanDev*)nullptr, want_rows, want_arena);
-    plan_seq = seq;
-    if (resident) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_t6_apply<true>), dim3(ntiles), dim3(kPlanBlock), 0, ps, idx->d, d, (const uint32_t*)e_prev, (const uint64_t*)e_prev_c, (const Scan5*)tile_sums,
-                                     ntiles, items, runs, coarse, slow_list, (const uint32_t*)status, idx->res_entries);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_t6_apply<false>), dim3(ntiles), dim3(kPlanBlock), 0, ps, idx->d, d, (const uint32_t*)e_prev, (const uint64_t*)e_prev_c, (const Scan5*)tile_sums,
-                            ntiles, items, runs, coarse, slow_list, (const uint32_t*)status, (uint64_t)0);
-    // speculative: the private rows of the regions under the duplicate rule (count and verdict from the plan's record) on the PLAN's stream,
-    // beside the previous batch's expansion like the rest of the plan -- the handle's stream then carries the expansion alone
-    if (spec) hipLaunchKernelGGL(k_t6_slow, dim3((unsigned)((std::min<uint64_t>(n, 1024) + 3) / 4)), dim3(256), 0, ps, idx->d, d, (const uint32_t*)slow_list, (uint64_t)0,
-                                 (const PlanDev*)plan_dev);
-    HIP_TRY(hipGetLastError());
-    // the plan's end event, and the handle's stream waiting for it, are enqueued while the plan is still on its way to the totals:
-    // two calls less between "the totals are here" and "the expansion is launched" (a batch of a tenth of a millisecond is the host's)
-    if (plan_aside) {
-      HIP_TRY(hipEventRecord(idx->ev[1], ps));
-      HIP_TRY(hipStreamWaitEvent(idx->stream, idx->ev[1], 0));
-      plan_end_enqueued = true;
-    }
-    return spec ? VS_OK : wait_posted(idx, &pt->seq, seq, 200);   // (a speculative batch: nobody waits here)
-  };
-  // A batch that is not sorted by first site: counting sort of the regions over the site index (k_sort_*), the batch
-  // then works on sorted copies of its per-region arrays (`d` points at them from here on, `d_user` keeps the
-  // caller's) and k_permute_out hands the outcome back at the end.
-  DevResult d_user{};        // the caller's per-region arrays while an unsorted batch works on sorted copies
-  uint32_t* perm = nullptr;  // sorted position -> region of the caller's batch (NULL: the batch is worked in the order given)
-  auto sort_batch = [&]() -> int {
-    const uint64_t G = idx->d.G;
-    uint32_t* count = nullptr;
-    unsigned long long* cursor = nullptr;
-    VS_TRY(dev_alloc(idx, (G + 2) * 4, (void**)&count, &scratch.bufs));
-    VS_TRY(dev_alloc(idx, (G + 2) * 8, (void**)&cursor, &scratch.bufs));
-    VS_TRY(dev_alloc(idx, n * 4, (void**)&perm, &scratch.bufs));
-    HIP_TRY(hipMemsetAsync(count, 0, (G + 1) * 4, idx->stream));
-    hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, idx->stream, d, count);
-    VS_TRY(exclusive_scan<uint32_t>(idx, (const uint32_t*)count, G + 1, (uint64_t*)cursor, &scratch.bufs));
-    hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, idx->stream, d, cursor, perm);
-    d_user = d;
-    uint64_t* sregions = nullptr;
-    VS_TRY(dev_alloc(idx, 2 * n * 8, (void**)&sregions, &scratch.bufs));
-    VS_TRY(dev_alloc(idx, n, (void**)&d.q_flags, &scratch.bufs));
-    VS_TRY(dev_alloc(idx, n * 4, (void**)&d.q_g0, &scratch.bufs));
-    VS_TRY(dev_alloc(idx, n * 8, (void**)&d.q_nvar, &scratch.bufs));
-    VS_TRY(dev_alloc(idx, n * 8, (void**)&d.q_ncar, &scratch.bufs));
-    VS_TRY(dev_alloc(idx, (n + 1) * 8, (void**)&d.var_begin, &scratch.bufs));
-    VS_TRY(dev_alloc(idx, (n + 1) * 8, (void**)&d.car_base, &scratch.bufs));
-    VS_TRY(dev_alloc(idx, n * 8, (void**)&d.q_car_len, &scratch.bufs));
-    VS_TRY(dev_alloc(idx, n * 8, (void**)&d.var_count, &scratch.bufs));
-    hipLaunchKernelGGL(k_permute_in, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, idx->stream, d_user, d, (const uint32_t*)perm, sregions);
-    d.regions = sregions;
-    HIP_TRY(hipGetLastError());
-    return VS_OK;
-  };
-  const int src = site_records ? 1 : 0;
-  // (a handle whose last batch needed sorting sorts first; it looks at the order as given again every 32nd batch)
-  if (sort_first) {
+  return VS_OK;
+}
+
+// The first kernel of a plan.  src 0: the regions (regions_dev, or the copy in `d`), 1: site records, 2: the sorted copy in `d`.
+static void shared_bounds(SharedCtx& c, int src) {
+  const dim3 grid(c.ntiles), block(kPlanBlock);
+  if (src == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_t6_bounds<0>), grid, block, 0, c.ps, c.idx->d, c.r->d, c.regions_dev, c.items, c.tile_max, c.status);
+  else if (src == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_t6_bounds<1>), grid, block, 0, c.ps, c.idx->d, c.r->d, c.site_records, c.items, c.tile_max, c.status);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_t6_bounds<2>), grid, block, 0, c.ps, c.idx->d, c.r->d, (const uint64_t*)nullptr, c.items, c.tile_max, c.status);
+}
+// One plan pass over the regions as they stand in `d`, on the plan's stream.  Leaves the per-region arrays, runs, coarse and
+// slow_list, plan_seq, and the totals in *pt -- waited for here unless the batch is speculative (PlanDev has them for the device).
+static int shared_plan(SharedCtx& c, int src) {
+  vs_index* idx = c.idx;
+  const DevResult& d = c.r->d;
+  const dim3 grid(c.ntiles), block(kPlanBlock);
+  c.plan_end_enqueued = false;
+  shared_bounds(c, src);   // (block 0 clears `status`)
+  hipLaunchKernelGGL(k_t6_mid, grid, block, 0, c.ps, idx->d, d, (const ShareMax*)c.tile_max, c.items, c.e_prev, c.e_prev_c, c.tile_sums, c.status);
+  const uint64_t seq = ++idx->share_seq;
+  hipLaunchKernelGGL(k_t6_totals, dim3(1), block, 0, c.ps, c.tile_sums, c.ntiles, (const uint32_t*)c.status, c.pt, seq, idx->res_entries, c.resident ? 1u : 0u,
+                     c.spec ? c.plan_dev : (PlanDev*)nullptr, c.want_rows, c.want_arena);
+  c.plan_seq = seq;
+  if (c.resident) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_t6_apply<true>), grid, block, 0, c.ps, idx->d, d, (const uint32_t*)c.e_prev, (const uint64_t*)c.e_prev_c, (const Scan5*)c.tile_sums,
+                                     c.ntiles, c.items, c.runs, c.coarse, c.slow_list, (const uint32_t*)c.status, idx->res_entries);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_t6_apply<false>), grid, block, 0, c.ps, idx->d, d, (const uint32_t*)c.e_prev, (const uint64_t*)c.e_prev_c, (const Scan5*)c.tile_sums,
+                          c.ntiles, c.items, c.runs, c.coarse, c.slow_list, (const uint32_t*)c.status, (uint64_t)0);
+  // speculative: the private rows of the regions under the duplicate rule (count and verdict from the plan's record) on the PLAN's stream,
+  // beside the previous batch's expansion like the rest of the plan -- the handle's stream then carries the expansion alone
+  if (c.spec) hipLaunchKernelGGL(k_t6_slow, dim3((unsigned)((std::min<uint64_t>(c.n, 1024) + 3) / 4)), dim3(256), 0, c.ps, idx->d, d, (const uint32_t*)c.slow_list, (uint64_t)0,
+                                 (const PlanDev*)c.plan_dev);
+  HIP_TRY(hipGetLastError());
+  // the plan's end event, and the handle's stream waiting for it, are enqueued while the plan is still on its way to the totals:
+  // two calls less between "the totals are here" and "the expansion is launched" (a batch of a tenth of a millisecond is the host's)
+  if (c.plan_aside) {
+    HIP_TRY(hipEventRecord(idx->ev[1], c.ps));
+    HIP_TRY(hipStreamWaitEvent(idx->stream, idx->ev[1], 0));
+    c.plan_end_enqueued = true;
+  }
+  return c.spec ? VS_OK : wait_posted(idx, &c.pt->seq, seq, 200);   // (a speculative batch: nobody waits here)
+}
+// A batch that is not sorted by first site: counting sort of the regions over the site index (k_sort_*) on the handle's stream,
+// behind a k_t6_bounds that left every region's first site.  Leaves perm, d_user (the caller's arrays) and `d` pointing at sorted
+// copies of its per-region arrays; shared_permute_out hands the outcome back at the end.
+static int shared_sort(SharedCtx& c) {
+  vs_index* idx = c.idx;
+  DevResult& d = c.r->d;
+  const uint64_t n = c.n, G = idx->d.G;
+  uint32_t* count = nullptr;
+  unsigned long long* cursor = nullptr;
+  VS_TRY(dev_alloc(idx, (G + 2) * 4, (void**)&count, &c.scratch.bufs));
+  VS_TRY(dev_alloc(idx, (G + 2) * 8, (void**)&cursor, &c.scratch.bufs));
+  VS_TRY(dev_alloc(idx, n * 4, (void**)&c.perm, &c.scratch.bufs));
+  HIP_TRY(hipMemsetAsync(count, 0, (G + 1) * 4, idx->stream));
+  hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, idx->stream, d, count);
+  VS_TRY(exclusive_scan<uint32_t>(idx, (const uint32_t*)count, G + 1, (uint64_t*)cursor, &c.scratch.bufs));
+  hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, idx->stream, d, cursor, c.perm);
+  c.d_user = d;
+  uint64_t* sregions = nullptr;
+  VS_TRY(region_arrays(d, &sregions, n, [&](auto** p, uint64_t k) { return dev_alloc(idx, k * sizeof(**p), (void**)p, &c.scratch.bufs); }));
+  hipLaunchKernelGGL(k_permute_in, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, idx->stream, c.d_user, d, (const uint32_t*)c.perm, sregions);
+  d.regions = sregions;
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+// The policy around the two: a handle whose last batch needed sorting sorts first (it looks at the order as given again every
+// 32nd batch); a speculative batch leaves the verdict to the device; every other batch waits for its totals and sorts when they
+// say so.  Leaves a planned batch, ev[1] behind the plan, the handle's sort hint (list batches only).
+static int shared_plan_batch(SharedCtx& c) {
+  vs_index* idx = c.idx;
+  const int src = c.site_records ? 1 : 0;
+  if (c.sort_first) {
     --idx->sort_probe_in;
-    launch_bounds(src);
-    VS_TRY(sort_batch());
-    VS_TRY(plan(2));
-  } else if (spec) {
-    VS_TRY(plan(src));   // (sorted or not is the device's verdict)
+    shared_bounds(c, src);
+    VS_TRY(shared_sort(c));
+    VS_TRY(shared_plan(c, 2));
+  } else if (c.spec) {
+    VS_TRY(shared_plan(c, src));   // (sorted or not is the device's verdict)
   } else {
-    VS_TRY(plan(src));
-    if (pt->not_sorted) {
-      if (plan_aside) {   // the sort and the second plan run on the handle's stream (behind the plan stream's work so far)
-        HIP_TRY(hipStreamSynchronize(ps));
-        plan_aside = false; ps = idx->stream;
+    VS_TRY(shared_plan(c, src));
+    if (c.pt->not_sorted) {
+      if (c.plan_aside) {   // the sort and the second plan run on the handle's stream (behind the plan stream's work so far)
+        HIP_TRY(hipStreamSynchronize(c.ps));
+        c.plan_aside = false; c.ps = idx->stream;
       }
-      VS_TRY(sort_batch());
-      VS_TRY(plan(2));
-      if (!counting) { idx->sort_hint = true; idx->sort_probe_in = 32; }
-    } else if (!counting) idx->sort_hint = false;
+      VS_TRY(shared_sort(c));
+      VS_TRY(shared_plan(c, 2));
+      if (c.lists) { idx->sort_hint = true; idx->sort_probe_in = 32; }
+    } else if (c.lists) idx->sort_hint = false;
   }
-  if (!spec && pt->not_sorted) return fail(VS_ERR_INTERNAL, "the batch is not sorted by first site after the device-side sort");
-  if (!plan_end_enqueued) HIP_TRY(hipEventRecord(idx->ev[1], ps));   // (a plan on the handle's own stream: the phase boundary only)
+  if (!c.spec && c.pt->not_sorted) return fail(VS_ERR_INTERNAL, "the batch is not sorted by first site after the device-side sort");
+  if (!c.plan_end_enqueued) HIP_TRY(hipEventRecord(idx->ev[1], c.ps));   // (a plan on the handle's own stream: the phase boundary only)
+  return VS_OK;
+}
+
+// The plan's rows are known: a genotype matrix beyond the limit is refused here, before it or the table is allocated.
+static int matrix_fits(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  r->mx_pitch = ((uint64_t)c.req.n_cols + 15) & ~15ull;
+  if (r->d.A <= cap / r->mx_pitch) return VS_OK;
+  (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+  (void)hipStreamSynchronize(idx->stream);
+  return fail(VS_ERR_ARG, "a genotype matrix of %llu rows x %u columns takes %llu bytes (rows %llu bytes apart), more than the limit of %llu MiB "
+              "(option matrix_max_mib): split the batch", (unsigned long long)r->d.A, c.req.n_cols, (unsigned long long)(r->d.A * r->mx_pitch),
+              (unsigned long long)r->mx_pitch, (unsigned long long)(cap >> 20));
+}
+// Reads the totals (*pt) or the speculation.  Leaves U / n_slow / n_runs, the result's sizes and bookkeeping, a speculative batch
+// registered with its slot, what the request's kind allocates, and the form of the rows and the expansion (n_fill .. lean).
+static int shared_tables(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  DevResult& d = r->d;
+  const SharedReq& q = c.req;
+  const PlanTotals* pt = c.pt;
   // (speculative: every size below is what was ALLOCATED -- an upper bound the launches are made for; the kernels take the real ones from PlanDev)
-  const uint64_t U = spec ? want_rows : pt->shared_rows, n_slow = spec ? 0 : pt->n_slow, n_runs = spec ? 0 : pt->n_runs;
-  if (!spec) { d.A = pt->rows; d.S = counting ? 0 : pt->arena; }
-  r->n_rows_reported = spec ? 0 : pt->reported;
-  if (spec) {
-    r->sizes_pending = true; r->totals_captured = false; r->plan_slot = slot; r->plan_seq = plan_seq; r->cap_rows = want_rows; r->cap_arena = want_arena;
-    idx->plan_slot_owner[slot] = r;
+  c.U = c.spec ? c.want_rows : pt->shared_rows; c.n_slow = c.spec ? 0 : pt->n_slow; c.n_runs = c.spec ? 0 : pt->n_runs;
+  if (!c.spec) { d.A = pt->rows; d.S = c.lists ? pt->arena : 0; }
+  r->n_rows_reported = c.spec ? 0 : pt->reported;
+  if (c.spec) {
+    r->sizes_pending = true; r->totals_captured = false; r->plan_slot = c.slot; r->plan_seq = c.plan_seq; r->cap_rows = c.want_rows; r->cap_arena = c.want_arena;
+    idx->plan_slot_owner[c.slot] = r;
     idx->t6_speculated++;
-  } else if (!counting) t6_hint_update(idx, n, pt->rows, pt->arena);
+  } else if (c.lists) t6_hint_update(idx, c.n, pt->rows, pt->arena);
+  c.n_fill = c.lists && !c.resident ? c.U : 0;
   r->shared_lists = true;
-  r->resident = resident;
+  r->resident = c.resident;
   r->scattered_lists = false;
-  r->n_unique_sites = resident || counting ? 0 : U;
-  if (counting) {
-    if (matrix) {   // (the plan's rows are known: the matrix is refused here, before it or the table is allocated)
-      const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
-      r->mx_pitch = ((uint64_t)matrix->n_cols + 15) & ~15ull;
-      if (d.A > cap / r->mx_pitch) {
-        (void)hipStreamSynchronize(ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
-        (void)hipStreamSynchronize(idx->stream);
-        return fail(VS_ERR_ARG, "a genotype matrix of %llu rows x %u columns takes %llu bytes (rows %llu bytes apart), more than the limit of %llu MiB "
-                    "(option matrix_max_mib): split the batch", (unsigned long long)d.A, matrix->n_cols, (unsigned long long)(d.A * r->mx_pitch),
-                    (unsigned long long)r->mx_pitch, (unsigned long long)(cap >> 20));
-      }
-    }
-    VS_TRY(ralloc(r, d.A, &d.rows));
-    const bool window = burden && (burden->min_ac != 0 || burden->max_ac != UINT32_MAX);
-    if (matrix) {
+  r->n_unique_sites = c.n_fill;
+  switch (q.kind) {
+    case ReqKind::Lists:
+      if (!c.spec) VS_TRY(shared_list_tables(c));   // (speculative: taken in front of the plan)
+      break;
+    case ReqKind::Counts:
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      break;
+    case ReqKind::Burden:
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      if (q.window()) VS_TRY(ralloc(r, d.A, &r->d_counts));   // (the filter's input, made only under a window)
+      VS_TRY(ralloc(r, (size_t)c.n * q.n_cols, &r->d_cells));
+      VS_TRY(ralloc(r, 2, &r->d_cell_total));   // (+ the number of chunks of the split regions)
+      break;
+    case ReqKind::Matrix:
+      VS_TRY(matrix_fits(c));
+      VS_TRY(ralloc(r, d.A, &d.rows));
       VS_TRY(ralloc(r, (size_t)(d.A * r->mx_pitch), &r->d_matrix));
       VS_TRY(ralloc(r, 2, &r->d_cell_total));
-    } else if (!burden || window) VS_TRY(ralloc(r, d.A, &r->d_counts));   // (a burden batch: the filter's input, made only under a window)
-    if (burden) {
-      VS_TRY(ralloc(r, (size_t)n * burden->n_cols, &r->d_cells));
-      VS_TRY(ralloc(r, 2, &r->d_cell_total));   // (+ the number of chunks of the split regions)
-    }
-  } else if (!spec) {
-    VS_TRY(ralloc(r, d.A, &d.rows));
-    if (resident) d.carriers = idx->res_arena;
-    else {
-      uint8_t* arena = nullptr;
-      VS_TRY(ralloc(r, d.S * d.car_width + 16, &arena));
-      d.carriers = arena;
-    }
+      break;
   }
-  // ---- shared rows + carrier lists: which form ----
-  const uint64_t n_fill = resident || counting ? 0 : U;
-  const bool async_fill = allow_async && idx->opts.async_fill && n_fill > 0;
-  const bool fused = idx->opts.fill_fused && !resident && !async_fill && !counting;
+  c.async_fill = c.allow_async && idx->opts.async_fill && c.n_fill > 0;
+  c.fused = idx->opts.fill_fused && c.lists && !c.resident && !c.async_fill;
   // Every event on a stream is a packet the GPU works through (~3 us each): the default batch -- async_submit, rows and lists in one
   // launch, no permutation -- records TWO on the handle's stream, the result's own pair around the expansion, and its phase
   // times are read from those (round 3 recorded five per batch, and this round's completion event would have made it eight).
-  const bool lean = async_submit && fused && n_fill > 0 && !perm;
-  if (!lean) HIP_TRY(hipEventRecord(idx->ev[2], idx->stream));
-  // ---- rows of the regions under the duplicate rule ----
-  if (n_slow) {   // (a speculative batch launched the kernel behind its plan, with the count from the plan's record)
-    const uint64_t waves = std::min<uint64_t>(n_slow, 16384);
-    hipLaunchKernelGGL(k_t6_slow, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, idx->stream, idx->d, d, (const uint32_t*)slow_list, n_slow, (const PlanDev*)nullptr);
-  }
-  // ---- shared rows + carrier lists ----
-  uint32_t* u_site = nullptr;
-  if (counting && d.A) VS_TRY(dev_alloc(idx, d.A * 4 + 8, (void**)&u_site, &scratch.bufs));   // (counts: the private rows' sites too)
-  if (U && !fused) {
-    if (!resident && !counting) VS_TRY(dev_alloc(idx, U * 4 + 8, (void**)&u_site, &scratch.bufs));
-    hipLaunchKernelGGL(k_share_rows2, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, idx->stream, idx->d, d, (const RunRec*)runs, (const uint32_t*)coarse, n_runs, U, u_site);
+  c.lean = c.async_submit && c.fused && c.n_fill > 0 && !c.perm;
+  return VS_OK;
+}
+
+// Leaves the table's rows -- the private ones of the regions under the duplicate rule, the shared ones unless the expansion
+// writes them (fused) -- and u_site; ev[2] / ev[3] around them unless lean.
+static int shared_rows(SharedCtx& c) {
+  vs_index* idx = c.idx;
+  const DevResult& d = c.r->d;
+  if (!c.lean) HIP_TRY(hipEventRecord(idx->ev[2], idx->stream));
+  const unsigned slow_blocks = (unsigned)((std::min<uint64_t>(c.n_slow, 16384) + 3) / 4);
+  if (c.n_slow)   // (a speculative batch launched the kernel behind its plan, with the count from the plan's record)
+    hipLaunchKernelGGL(k_t6_slow, dim3(slow_blocks), dim3(256), 0, idx->stream, idx->d, d, (const uint32_t*)c.slow_list, c.n_slow, (const PlanDev*)nullptr);
+  if (!c.lists && d.A) VS_TRY(dev_alloc(idx, d.A * 4 + 8, (void**)&c.u_site, &c.scratch.bufs));   // (a column request: the private rows' sites too)
+  if (c.U && !c.fused) {
+    if (c.n_fill) VS_TRY(dev_alloc(idx, c.U * 4 + 8, (void**)&c.u_site, &c.scratch.bufs));
+    hipLaunchKernelGGL(k_share_rows2, dim3((unsigned)((c.U + 255) / 256)), dim3(256), 0, idx->stream, idx->d, d, (const RunRec*)c.runs, (const uint32_t*)c.coarse, c.n_runs, c.U, c.u_site);
   }
   HIP_TRY(hipGetLastError());
-  if (!lean) HIP_TRY(hipEventRecord(idx->ev[3], idx->stream));
-  if (counting && d.A) {
-    // the counts: the private rows' sites behind the shared ones, then one launch over the whole table between the result's own pair
-    // of events (vs_result_fill_ms)
-    if (n_slow) {
-      const uint64_t waves = std::min<uint64_t>(n_slow, 16384);
-      hipLaunchKernelGGL(k_count_slow_sites, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, idx->stream, d, (const uint32_t*)slow_list, n_slow, u_site);
-    }
-    if (!burden && !matrix) {
-      VS_TRY(result_events(r));
-      HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
-      launch_allele_counts(idx, d, u_site, U, d_mask, counting->words, r->d_counts);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
-      r->pending = true;
-    }
+  if (!c.lean) HIP_TRY(hipEventRecord(idx->ev[3], idx->stream));
+  if (!c.lists && d.A && c.n_slow)   // the private rows' sites behind the shared ones
+    hipLaunchKernelGGL(k_count_slow_sites, dim3(slow_blocks), dim3(256), 0, idx->stream, d, (const uint32_t*)c.slow_list, c.n_slow, c.u_site);
+  return VS_OK;
+}
+
+#ifdef VS_TUNING
+// option fill_stats: the per-task clocks k_fill_sites2 left in tstat, read back and summed up on stderr
+static int print_fill_stats(vs_index* idx, const unsigned long long* tstat, uint64_t nt, uint32_t chunk) {
+  std::vector<uint32_t> h(nt * 4);
+  HIP_TRY(hipMemcpyAsync(h.data(), tstat, nt * 16, hipMemcpyDeviceToHost, idx->stream));
+  HIP_TRY(hipStreamSynchronize(idx->stream));
+  double sp = 0, sl = 0, sd = 0, st = 0, nd = 0; uint32_t mx = 0;
+  for (uint64_t t = 0; t < nt; ++t) {
+    const uint32_t tot = h[4 * t + 3] & 0xFFFFFFu;
+    sp += h[4 * t]; sl += h[4 * t + 1]; sd += h[4 * t + 2]; st += tot; nd += h[4 * t + 3] >> 24; mx = std::max(mx, tot);
   }
-  if (async_fill) {
+  fprintf(stderr, "fill stats: %llu tasks of %u rows | mean ticks (10 ns) per task: parameters + rows %.1f, list phase %.1f, dense phase %.1f, whole task %.1f (max %u) | "
+          "dense variants per task %.2f\n", (unsigned long long)nt, chunk, sp / nt, sl / nt, sd / nt, st / nt, mx, nd / nt);
+  return VS_OK;
+}
+#endif
+// The fused expansion: k_fill_sites2 writes the shared rows AND their carrier lists, between the result's own pair of events.
+static int shared_expand_fused(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t U = c.U;
+  // rows per wave task: 32 (one look-up of the run records and one round of parameter loads per 32 rows; 16-row tasks -- round 3's
+  // choice for the kernel that did not write rows -- measure the same to 5 % slower, 64 and 8 slower: tools/ab_t6.py)
+  const uint32_t chunk = idx->opts.fill_chunk ? idx->opts.fill_chunk : 32;
+  const uint32_t gt_words = fill_gt_words(idx);
+  size_t lds_bytes = fill_lds_bytes(idx);
+  uint32_t ablate = 0;
+  unsigned long long* tstat = nullptr;
+  if ((U + chunk - 1) / chunk / 4 > 0x7FFFFFF0ull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu shared rows)", (unsigned long long)U);
+#ifdef VS_TUNING
+  constexpr bool kTune = true;
+  lds_bytes += std::min<size_t>(idx->opts.fill_lds_pad, 96 << 10);
+  ablate = idx->opts.fill_ablate;
+  if (idx->opts.fill_stats) {
+    VS_TRY(dev_alloc(idx, ((U + chunk - 1) / chunk + 4) * 16, (void**)&tstat, &c.scratch.bufs));
+    HIP_TRY(hipMemsetAsync(tstat, 0, ((U + chunk - 1) / chunk + 4) * 16, idx->stream));
+  }
+#else
+  constexpr bool kTune = false;
+#endif
+  const int mode = idx->opts.fill_mode;
+  VS_TRY(result_events(r));   // the kernel's own duration, whenever the result is asked for it (vs_result_fill_ms)
+  HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
+  const PlanDev* pd = c.spec ? c.plan_dev : nullptr;
+  if (idx->d.wpc > 63) launch_fill2<true, kTune>(idx, r->d, c.runs, c.coarse, c.n_runs, U, chunk, lds_bytes, ablate, gt_words, tstat, mode, pd);
+  else launch_fill2<false, kTune>(idx, r->d, c.runs, c.coarse, c.n_runs, U, chunk, lds_bytes, ablate, gt_words, tstat, mode, pd);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
+  r->pending = true;
+#ifdef VS_TUNING
+  if (tstat) VS_TRY(print_fill_stats(idx, tstat, (U + chunk - 1) / chunk, chunk));
+#endif
+  return VS_OK;
+}
+// Lists: the carrier lists of the n_fill shared rows, in one of three forms (resident lists: none, the rows point into the index's arena).
+static int shared_expand(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  c.fill_launches = c.n_fill ? 1 : 0;   // (async_fill: ms_fill is what the first stream saw of it, ~0; vs_result_fill_ms has the kernel's time)
+  if (c.async_fill) {
     // the expansion goes to the handle's second stream behind an event and the call returns once the FIRST stream is done
     // (rows, per-region arrays); the next batch's plan and rows then run beside it.  The call's temporaries (the site
     // index the expansion reads) stay with the result until it is freed.
@@ -1576,99 +1692,92 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
     HIP_TRY(hipEventRecord(idx->fill_ev[0], idx->stream));
     HIP_TRY(hipStreamWaitEvent(idx->fill_stream, idx->fill_ev[0], 0));
     HIP_TRY(hipEventRecord(r->ev_fill[0], idx->fill_stream));
-    VS_TRY(fill_lists(idx, d, true, u_site, n_fill, idx->fill_stream));
+    VS_TRY(fill_lists(idx, r->d, true, c.u_site, c.n_fill, idx->fill_stream));
     HIP_TRY(hipEventRecord(r->ev_fill[1], idx->fill_stream));
     r->pending = true;
-  } else if (n_fill && !fused) {
-    VS_TRY(fill_lists(idx, d, true, u_site, n_fill));
-  } else if (n_fill) {
-    // rows per wave task: 32 (one look-up of the run records and one round of parameter loads per 32 rows; 16-row tasks -- round 3's
-    // choice for the kernel that did not write rows -- measure the same to 5 % slower, 64 and 8 slower: tools/ab_t6.py)
-    uint32_t chunk = idx->opts.fill_chunk ? idx->opts.fill_chunk : 32;
-    const uint32_t gt_words = fill_gt_words(idx);
-#ifdef VS_TUNING
-    const size_t lds_bytes = fill_lds_bytes(idx) + std::min<size_t>(idx->opts.fill_lds_pad, 96 << 10);
-    const uint32_t ablate = idx->opts.fill_ablate;
-    constexpr bool kTune = true;
-#else
-    const size_t lds_bytes = fill_lds_bytes(idx);
-    const uint32_t ablate = 0;
-    constexpr bool kTune = false;
-#endif
-    if ((U + chunk - 1) / chunk / 4 > 0x7FFFFFF0ull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu shared rows)", (unsigned long long)U);
-    unsigned long long* tstat = nullptr;
-#ifdef VS_TUNING
-    if (idx->opts.fill_stats) {
-      VS_TRY(dev_alloc(idx, ((U + chunk - 1) / chunk + 4) * 16, (void**)&tstat, &scratch.bufs));
-      HIP_TRY(hipMemsetAsync(tstat, 0, ((U + chunk - 1) / chunk + 4) * 16, idx->stream));
-    }
-#endif
-    const int mode = idx->opts.fill_mode;
-    VS_TRY(result_events(r));   // the kernel's own duration, whenever the result is asked for it (vs_result_fill_ms)
-    HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
-    const PlanDev* pd = spec ? plan_dev : nullptr;
-    if (idx->d.wpc > 63) launch_fill2<true, kTune>(idx, d, runs, coarse, n_runs, U, chunk, lds_bytes, ablate, gt_words, tstat, mode, pd);
-    else launch_fill2<false, kTune>(idx, d, runs, coarse, n_runs, U, chunk, lds_bytes, ablate, gt_words, tstat, mode, pd);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
-    r->pending = true;
-#ifdef VS_TUNING
-    if (tstat) {
-      const uint64_t nt = (U + chunk - 1) / chunk;
-      std::vector<uint32_t> h(nt * 4);
-      HIP_TRY(hipMemcpyAsync(h.data(), tstat, nt * 16, hipMemcpyDeviceToHost, idx->stream));
-      HIP_TRY(hipStreamSynchronize(idx->stream));
-      double sp = 0, sl = 0, sd = 0, st = 0, nd = 0; uint32_t mx = 0;
-      for (uint64_t t = 0; t < nt; ++t) {
-        const uint32_t tot = h[4 * t + 3] & 0xFFFFFFu;
-        sp += h[4 * t]; sl += h[4 * t + 1]; sd += h[4 * t + 2]; st += tot; nd += h[4 * t + 3] >> 24; mx = std::max(mx, tot);
-      }
-      fprintf(stderr, "fill stats: %llu tasks of %u rows | mean ticks (10 ns) per task: parameters + rows %.1f, list phase %.1f, dense phase %.1f, whole task %.1f (max %u) | "
-              "dense variants per task %.2f\n", (unsigned long long)nt, chunk, sp / nt, sl / nt, sd / nt, st / nt, mx, nd / nt);
-    }
-#endif
+    return VS_OK;
   }
-  if (perm) {   // every region's outcome back to its place in the caller's order (rows and lists are shared: nothing else moves)
-    const DevResult ds = d;
-    d.regions = d_user.regions; d.q_flags = d_user.q_flags; d.q_g0 = d_user.q_g0; d.q_nvar = d_user.q_nvar; d.q_ncar = d_user.q_ncar;
-    d.var_begin = d_user.var_begin; d.car_base = d_user.car_base; d.q_car_len = d_user.q_car_len; d.var_count = d_user.var_count;
-    hipLaunchKernelGGL(k_permute_out, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, idx->stream, ds, d, (const uint32_t*)perm);
-    HIP_TRY(hipGetLastError());
-  }
-  if (burden) {   // the matrix, between the result's own pair of events (vs_result_fill_ms): the filter's counts are inside the pair
-    VS_TRY(result_events(r));
-    HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
-    if (r->d_counts && d.A) launch_allele_counts(idx, d, u_site, U, d_mask, counting->words, r->d_counts);
-    VS_TRY(launch_burden(idx, r, u_site, U, d_mask, d_rank, counting->words, *burden, scratch));
-    HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
-    r->pending = true;
-  }
-  if (matrix) {   // the matrix, between the result's own pair of events (vs_result_fill_ms)
-    VS_TRY(result_events(r));
-    HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
-    VS_TRY(launch_matrix(idx, r, u_site, U, d_mask, d_rank, counting->words, *matrix));
-    HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
-    r->pending = true;
-  }
-  if (!lean) HIP_TRY(hipEventRecord(idx->ev[4], idx->stream));
+  if (!c.n_fill) return VS_OK;
+  return c.fused ? shared_expand_fused(c) : fill_lists(idx, r->d, true, c.u_site, c.n_fill);
+}
+// Counts: one launch over the whole table between the result's own pair of events (vs_result_fill_ms).
+static int shared_counts(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  if (!r->d.A) return VS_OK;
+  VS_TRY(result_events(r));
+  HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
+  launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
+  r->pending = true;
+  c.fill_launches = 1;
+  return VS_OK;
+}
+// Burden, Matrix: the matrix between the result's own pair of events (vs_result_fill_ms); a burden filter's counts are inside the pair.
+static int shared_cells(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  VS_TRY(result_events(r));
+  HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
+  if (c.req.kind == ReqKind::Burden) {
+    if (r->d_counts && r->d.A) launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
+    VS_TRY(launch_burden(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.req, c.scratch));
+  } else VS_TRY(launch_matrix(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+  HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
+  r->pending = true;
+  c.fill_launches = 1;
+  return VS_OK;
+}
+
+// An unsorted batch: every region's outcome back to its place in the caller's order (rows and lists are shared: nothing else
+// moves).  Leaves `d` pointing at the caller's per-region arrays again.
+static int shared_permute_out(SharedCtx& c) {
+  if (!c.perm) return VS_OK;
+  DevResult& d = c.r->d;
+  const DevResult ds = d, &du = c.d_user;
+  d.regions = du.regions; d.q_flags = du.q_flags; d.q_g0 = du.q_g0; d.q_nvar = du.q_nvar; d.q_ncar = du.q_ncar;
+  d.var_begin = du.var_begin; d.car_base = du.car_base; d.q_car_len = du.q_car_len; d.var_count = du.var_count;
+  hipLaunchKernelGGL(k_permute_out, dim3((unsigned)((c.n + 256) / 256)), dim3(256), 0, c.idx->stream, ds, d, (const uint32_t*)c.perm);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+
+// The batch's last event and the handle's timing state; then the batch is ENQUEUED (async_submit: its sizes are known -- the
+// plan's totals; a speculative batch: result_sizes --, its buffers are the result's, the timing events are read when asked) or
+// waited for: k_post_done, temporaries back to the pool (async_fill: to the result), the phase times.
+static int shared_finish(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  if (!c.lean) HIP_TRY(hipEventRecord(idx->ev[4], idx->stream));
   else {   // plan: the handle's two events on the plan stream; the rest: the result's pair (no separate rows kernel: ms_emit = 0)
     idx->tev[0] = idx->ev[0]; idx->tev[1] = idx->ev[1]; idx->tev[2] = r->ev_fill[0]; idx->tev[3] = r->ev_fill[0]; idx->tev[4] = r->ev_fill[1];
     idx->timing_owner = r;
   }
   idx->timing_pending = true;
-  idx->timing_fill_launches = (n_fill || (counting && d.A) || burden || matrix) ? 1 : 0;   // (async_fill: ms_fill is what the first stream saw of it, ~0; vs_result_fill_ms has the kernel's time)
-  // async_submit: the batch is enqueued, its sizes are known (the plan's totals; a speculative batch: result_sizes) and its buffers are the
-  // result's -- the call returns here; the timing events are read when asked for
-  if (async_submit) return batch_enqueued(r, scratch, /*record_done=*/!lean);
+  idx->timing_fill_launches = c.fill_launches;
+  if (c.async_submit) return batch_enqueued(r, c.scratch, /*record_done=*/!c.lean);
   uint64_t* done = idx->pinned + vs_index::kPinDone;
   const uint64_t seq = ++idx->done_seq;
   hipLaunchKernelGGL(k_post_done, dim3(1), dim3(1), 0, idx->stream, done, seq);
   HIP_TRY(hipGetLastError());
   VS_TRY(wait_posted(idx, done, seq, 2000));
   idx->batch_in_flight = false;
-  if (async_fill) scratch.hand_to(r->bufs);
-  scratch.release();
+  if (c.async_fill) c.scratch.hand_to(r->bufs);
+  c.scratch.release();
   return collect_timing(idx);
+}
+
+static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
+                            bool allow_async, bool may_speculate, const SharedReq& req) {
+  SharedCtx c(idx, r, n, req);
+  c.allow_async = allow_async;
+  c.site_records = site_records;
+  VS_TRY(shared_setup(c, regions, regions_on_device, may_speculate));
+  VS_TRY(shared_plan_batch(c));
+  VS_TRY(shared_tables(c));
+  VS_TRY(shared_rows(c));
+  if (!c.behind_perm) VS_TRY(c.lists ? shared_expand(c) : shared_counts(c));
+  VS_TRY(shared_permute_out(c));
+  if (c.behind_perm) VS_TRY(shared_cells(c));
+  return shared_finish(c);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1904,13 +2013,10 @@ static int run_type6(vs_index* idx, const vs_region* regions, uint64_t n, vs_res
   return run_private_batch(idx, regions, n, r, regions_on_device, site_records, 0, nullptr, allow_async);
 }
 
-// Allele counts (vs_query_allele_counts): the plan and the shared rows of type 6, then k_allele_counts over the rows instead of the
-// expansion -- every batch size, never speculative, no arena (run_type6_shared: `counting`).  mask: a bit per sample of the subset,
-// empty for the whole cohort.
-static int run_counts_batch(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const std::vector<uint64_t>& mask,
-                            const BurdenReq* burden = nullptr, const MatrixReq* matrix = nullptr) {
-  const CountReq cq{mask.empty() ? nullptr : mask.data(), (uint32_t)mask.size(), burden, matrix};
-  return run_type6_shared(idx, regions, n, r, regions_on_device, nullptr, /*allow_async=*/true, /*may_speculate=*/false, &cq);
+// A column request (allele counts, burden, genotype matrix): the plan and the shared rows of type 6, then the request's own kernels
+// over the rows instead of the expansion -- every batch size, never speculative, no arena (SharedCtx::lists).
+static int run_column_batch(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, const SharedReq& req) {
+  return run_type6_shared(idx, regions, n, r, is_device_ptr(regions), nullptr, /*allow_async=*/true, /*may_speculate=*/false, req);
 }
 
 // lanes per region of the one-chain walks of query types 2, 3 and 5 (k_sample_walk_sc, k_sample_seq): 1, or kScGroup running the same chain
@@ -2602,19 +2708,31 @@ static int drop_result(vs_result* r, int rc) {
   return rc;
 }
 
-// The columns of a samples-wide answer (burden, genotype matrix): the subset as a bit per sample (id 0, "ref", is never a carrier),
-// the columns in front of each word of the mask, and the distinct ids, ascending.  sample_ids NULL: the whole cohort, mask and
-// rank stay empty.
+// The arguments every column query checks first, on the host -- also on a handle opened without a device; `batch`: its name in the message.
+static int column_query_args(const vs_index* idx, const void* out, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, const char* batch) {
+  if (!idx || !out || (n && !regions) || (!sample_ids && n_ids)) return fail(VS_ERR_ARG, "null argument");
+  if (n == 0) return fail(VS_ERR_ARG, "%s batch needs at least one region", batch);
+  if (sample_ids && n_ids == 0) return fail(VS_ERR_ARG, "an empty sample subset (pass NULL for the whole cohort)");
+  return VS_OK;
+}
+// A sample subset as a bit per sample (id 0, "ref", is never a carrier).
+static int sample_mask(const vs_index* idx, const uint32_t* sample_ids, uint64_t n_ids, std::vector<uint64_t>& mask) {
+  const uint32_t ns = idx->g.num_samples;
+  mask.assign((ns + 63) / 64, 0);
+  for (uint64_t i = 0; i < n_ids; ++i) {
+    const uint32_t id = sample_ids[i];
+    if (id == 0 || id >= ns) return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u is not a sample of the cohort (1 .. %u)", id, ns - 1);
+    mask[id >> 6] |= 1ull << (id & 63);
+  }
+  return VS_OK;
+}
+// The columns of a samples-wide answer (burden, genotype matrix): the subset's mask, the columns in front of each word of it,
+// and the distinct ids, ascending.  sample_ids NULL: the whole cohort, mask and rank stay empty.
 static int sample_columns(const vs_index* idx, const uint32_t* sample_ids, uint64_t n_ids, std::vector<uint64_t>& mask, std::vector<uint32_t>& rank,
                           std::vector<uint32_t>& cols) {
   const uint32_t ns = idx->g.num_samples;
   if (sample_ids) {
-    mask.assign((ns + 63) / 64, 0);
-    for (uint64_t i = 0; i < n_ids; ++i) {
-      const uint32_t id = sample_ids[i];
-      if (id == 0 || id >= ns) return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u is not a sample of the cohort (1 .. %u)", id, ns - 1);
-      mask[id >> 6] |= 1ull << (id & 63);
-    }
+    VS_TRY(sample_mask(idx, sample_ids, n_ids, mask));
     rank.resize(mask.size());
     for (size_t w = 0; w < mask.size(); ++w) {
       rank[w] = (uint32_t)cols.size();
@@ -2971,33 +3089,29 @@ int vs_query_expand_site_ranges(vs_index* idx, const void* device_records, uint6
   });
 }
 
+// The request of a column query from the host vectors of its entry point (they outlive the batch's submission).
+static SharedReq column_request(ReqKind kind, const std::vector<uint64_t>& mask, const std::vector<uint32_t>& rank, uint64_t n_cols) {
+  SharedReq q;
+  q.kind = kind; q.mask = mask.empty() ? nullptr : mask.data(); q.words = (uint32_t)mask.size();
+  q.rank = rank.empty() ? nullptr : rank.data(); q.n_cols = (uint32_t)n_cols;
+  return q;
+}
+
 int vs_query_allele_counts(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, vs_result** out) {
-  // (the arguments first: they are checked on the host, also on a handle opened without a device)
-  if (!idx || !out || (n && !regions) || (!sample_ids && n_ids)) return fail(VS_ERR_ARG, "null argument");
-  if (n == 0) return fail(VS_ERR_ARG, "an allele-count batch needs at least one region");
-  std::vector<uint64_t> mask;   // the subset as a bit per sample (id 0, "ref", is never a carrier)
+  VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "an allele-count"));
+  std::vector<uint64_t> mask;   // (NULL: the whole cohort -- also of a cohort without samples, which the samples-wide answers refuse)
   if (sample_ids) {
-    if (n_ids == 0) return fail(VS_ERR_ARG, "an empty sample subset (pass NULL for the whole cohort)");
-    const uint32_t ns = idx->g.num_samples;
-    mask.assign((ns + 63) / 64, 0);
-    for (uint64_t i = 0; i < n_ids; ++i) {
-      const uint32_t id = sample_ids[i];
-      if (id == 0 || id >= ns) return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u is not a sample of the cohort (1 .. %u)", id, ns - 1);
-      mask[id >> 6] |= 1ull << (id & 63);
-    }
-    if (mask.size() * 8 > kCountMaskMaxBytes) return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the counting kernel's LDS", ns);
+    VS_TRY(sample_mask(idx, sample_ids, n_ids, mask));
+    if (mask.size() * 8 > kCountMaskMaxBytes)
+      return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the counting kernel's LDS", idx->g.num_samples);
   }
-  return make_result(idx, kKindCounts, out, [&](vs_result* r) {
-    return run_counts_batch(idx, regions, n, r, is_device_ptr(regions), mask);
-  });
+  const SharedReq req = column_request(ReqKind::Counts, mask, {}, 0);
+  return make_result(idx, kKindCounts, out, [&](vs_result* r) { return run_column_batch(idx, regions, n, r, req); });
 }
 
 int vs_query_sample_burden(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t min_ac, uint32_t max_ac,
                            vs_result** out) {
-  // (the arguments first, in the order of the count entry point: they are checked on the host, also on a handle opened without a device)
-  if (!idx || !out || (n && !regions) || (!sample_ids && n_ids)) return fail(VS_ERR_ARG, "null argument");
-  if (n == 0) return fail(VS_ERR_ARG, "a burden batch needs at least one region");
-  if (sample_ids && n_ids == 0) return fail(VS_ERR_ARG, "an empty sample subset (pass NULL for the whole cohort)");
+  VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "a burden"));
   if (min_ac > max_ac) return fail(VS_ERR_ARG, "an empty allele-count window [%u, %u]", min_ac, max_ac);
   const uint32_t ns = idx->g.num_samples;
   std::vector<uint64_t> mask;
@@ -3008,27 +3122,25 @@ int vs_query_sample_burden(vs_index* idx, const vs_region* regions, uint64_t n, 
     return fail(VS_ERR_ARG, "a burden matrix of %llu regions x %llu columns exceeds 2^31 cells (%llu GiB at 16 bytes a cell): split the batch",
                 (unsigned long long)n, (unsigned long long)n_cols, (unsigned long long)((n >> 26) * n_cols));
   if (mask.size() * 8 > kBurdenMaskMaxBytes) return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the burden kernel's LDS", ns);
-  const BurdenReq bq{rank.empty() ? nullptr : rank.data(), (uint32_t)n_cols, min_ac, max_ac};
+  SharedReq req = column_request(ReqKind::Burden, mask, rank, n_cols);
+  req.min_ac = min_ac; req.max_ac = max_ac;
   return make_result(idx, kKindBurden, out, [&](vs_result* r) {
     r->h_cols = cols;
-    return run_counts_batch(idx, regions, n, r, is_device_ptr(regions), mask, &bq);
+    return run_column_batch(idx, regions, n, r, req);
   });
 }
 
 int vs_query_genotype_matrix(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, vs_result** out) {
-  // (the arguments first, as the burden entry point checks them: on the host, also on a handle opened without a device)
-  if (!idx || !out || (n && !regions) || (!sample_ids && n_ids)) return fail(VS_ERR_ARG, "null argument");
-  if (n == 0) return fail(VS_ERR_ARG, "a genotype-matrix batch needs at least one region");
-  if (sample_ids && n_ids == 0) return fail(VS_ERR_ARG, "an empty sample subset (pass NULL for the whole cohort)");
+  VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "a genotype-matrix"));
   std::vector<uint64_t> mask;
   std::vector<uint32_t> rank, cols;
   VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));
   if (mask.size() * 8 > kMatrixMaskMaxBytes)
     return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", idx->g.num_samples);
-  const MatrixReq mq{rank.empty() ? nullptr : rank.data(), (uint32_t)cols.size()};
+  const SharedReq req = column_request(ReqKind::Matrix, mask, rank, cols.size());
   return make_result(idx, kKindMatrix, out, [&](vs_result* r) {
     r->h_cols = cols;
-    return run_counts_batch(idx, regions, n, r, is_device_ptr(regions), mask, nullptr, &mq);
+    return run_column_batch(idx, regions, n, r, req);
   });
 }
 
@@ -3150,49 +3262,23 @@ int vs_index_find(vs_index* idx, const uint64_t* pos, uint64_t n, uint32_t* vert
 }
 
 // ---------------------------------------------------------------- result access
-// An allele-count result's counts in page-locked memory owned by the result (the caller has passed the gate).
-static int counts_to_host(vs_result* r) {
-  if (r->counts_pin.p) return VS_OK;
+// `bytes` of a result's array in device memory into page-locked memory owned by the result (`pin`), once; `what`: its name in the
+// error text.  An empty array: no copy, the (16-byte) buffer is there all the same.  (The caller has passed the gate.)
+static int array_to_host(vs_result* r, const void* dev, size_t bytes, DevBuf* pin, const char* what) {
+  if (pin->p) return VS_OK;
   vs_index* idx = r->idx;
   VS_TRY(result_ready(r));
   DevBuf b{nullptr, 0};
-  VS_TRY(pin_alloc(idx, (size_t)r->d.A * sizeof(uint4) + 16, &b));
-  if (r->d.A) {
-    const hipError_t e = hipMemcpyAsync(b.p, r->d_counts, (size_t)r->d.A * sizeof(uint4), hipMemcpyDeviceToHost, idx->stream);
+  VS_TRY(pin_alloc(idx, bytes + 16, &b));
+  if (bytes) {
+    const hipError_t e = hipMemcpyAsync(b.p, dev, bytes, hipMemcpyDeviceToHost, idx->stream);
     const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(idx->stream) : e;
-    if (e2 != hipSuccess) { pin_release(idx, b); return fail(VS_ERR_HIP, "copy of the allele counts failed: %s", hipGetErrorString(e2)); }
+    if (e2 != hipSuccess) { pin_release(idx, b); return fail(VS_ERR_HIP, "copy of the %s failed: %s", what, hipGetErrorString(e2)); }
   }
-  r->counts_pin = b;
+  *pin = b;
   return VS_OK;
 }
-// A burden result's matrix in page-locked memory owned by the result (the caller has passed the gate).
-static int cells_to_host(vs_result* r) {
-  if (r->cells_pin.p) return VS_OK;
-  vs_index* idx = r->idx;
-  VS_TRY(result_ready(r));
-  const size_t bytes = (size_t)r->d.Q * r->h_cols.size() * sizeof(uint4);
-  DevBuf b{nullptr, 0};
-  VS_TRY(pin_alloc(idx, bytes + 16, &b));
-  const hipError_t e = hipMemcpyAsync(b.p, r->d_cells, bytes, hipMemcpyDeviceToHost, idx->stream);
-  const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(idx->stream) : e;
-  if (e2 != hipSuccess) { pin_release(idx, b); return fail(VS_ERR_HIP, "copy of the burden matrix failed: %s", hipGetErrorString(e2)); }
-  r->cells_pin = b;
-  return VS_OK;
-}
-// A genotype-matrix result's matrix, pitch and all, in page-locked memory owned by the result (the caller has passed the gate).
-static int matrix_to_host(vs_result* r) {
-  if (r->cells_pin.p) return VS_OK;
-  vs_index* idx = r->idx;
-  VS_TRY(result_ready(r));
-  const size_t bytes = (size_t)(r->d.A * r->mx_pitch);
-  DevBuf b{nullptr, 0};
-  VS_TRY(pin_alloc(idx, bytes + 16, &b));
-  const hipError_t e = bytes ? hipMemcpyAsync(b.p, r->d_matrix, bytes, hipMemcpyDeviceToHost, idx->stream) : hipSuccess;
-  const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(idx->stream) : e;
-  if (e2 != hipSuccess) { pin_release(idx, b); return fail(VS_ERR_HIP, "copy of the genotype matrix failed: %s", hipGetErrorString(e2)); }
-  r->cells_pin = b;
-  return VS_OK;
-}
+static int counts_to_host(vs_result* r) { return array_to_host(r, r->d_counts, (size_t)r->d.A * sizeof(uint4), &r->counts_pin, "allele counts"); }
 // Start (stream) the raw copy of a result: rows and -- on request -- the arena go into one page-locked block.  (The caller has passed
 // the gate.)
 static int raw_copy_begin(vs_result* r, bool with_carriers, hipStream_t stream) {
@@ -3606,7 +3692,7 @@ int vs_result_get_sample_burden(vs_result* r, uint64_t* n_regions, uint64_t* n_c
   if (!cells) return fail(VS_ERR_ARG, "null argument");
   if (r->kind != kKindBurden) return fail(VS_ERR_ARG, "not a burden result (vs_query_sample_burden)");
   static_assert(sizeof(vs_sample_burden) == sizeof(uint4), "cell layout of the ABI");
-  VS_TRY(cells_to_host(r));
+  VS_TRY(array_to_host(r, r->d_cells, (size_t)r->d.Q * r->h_cols.size() * sizeof(uint4), &r->cells_pin, "burden matrix"));
   *cells = (const vs_sample_burden*)r->cells_pin.p;
   if (n_regions) *n_regions = r->d.Q;
   if (n_cols) *n_cols = r->h_cols.size();
@@ -3614,12 +3700,19 @@ int vs_result_get_sample_burden(vs_result* r, uint64_t* n_regions, uint64_t* n_c
   return VS_OK;
 }
 
-int vs_result_sample_burden_device(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, const void** dev_cells) {
+// The *_device accessors: the gate, a result of `kind` (else the text `not_kind`), and the matrix complete when its pointer is
+// handed out -- the caller needs no event.
+static int device_matrix_ready(vs_result* r, const void* out, int kind, const char* not_kind) {
   VS_TRY(result_enter(r, Want::Variants, true));
-  if (!dev_cells) return fail(VS_ERR_ARG, "null argument");
-  if (r->kind != kKindBurden) return fail(VS_ERR_ARG, "not a burden result (vs_query_sample_burden)");
+  if (!out) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kind) return fail(VS_ERR_ARG, "%s", not_kind);
   VS_TRY(result_ready(r));
-  HIP_TRY(hipStreamSynchronize(r->idx->stream));   // the matrix is complete when the pointer is handed out: the caller needs no event
+  HIP_TRY(hipStreamSynchronize(r->idx->stream));
+  return VS_OK;
+}
+
+int vs_result_sample_burden_device(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, const void** dev_cells) {
+  VS_TRY(device_matrix_ready(r, dev_cells, kKindBurden, "not a burden result (vs_query_sample_burden)"));
   *dev_cells = r->d_cells;
   if (n_regions) *n_regions = r->d.Q;
   if (n_cols) *n_cols = r->h_cols.size();
@@ -3630,7 +3723,7 @@ int vs_result_get_genotype_matrix(vs_result* r, uint64_t* n_rows, uint64_t* n_co
   VS_TRY(result_enter(r, Want::Variants, true));
   if (!cells) return fail(VS_ERR_ARG, "null argument");
   if (r->kind != kKindMatrix) return fail(VS_ERR_ARG, "not a genotype-matrix result (vs_query_genotype_matrix)");
-  VS_TRY(matrix_to_host(r));
+  VS_TRY(array_to_host(r, r->d_matrix, (size_t)(r->d.A * r->mx_pitch), &r->cells_pin, "genotype matrix"));   // (pitch and all)
   *cells = (const uint8_t*)r->cells_pin.p;
   if (n_rows) *n_rows = r->d.A;
   if (n_cols) *n_cols = r->h_cols.size();
@@ -3640,11 +3733,7 @@ int vs_result_get_genotype_matrix(vs_result* r, uint64_t* n_rows, uint64_t* n_co
 }
 
 int vs_result_genotype_matrix_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint64_t* row_pitch, const void** dev_cells) {
-  VS_TRY(result_enter(r, Want::Variants, true));
-  if (!dev_cells) return fail(VS_ERR_ARG, "null argument");
-  if (r->kind != kKindMatrix) return fail(VS_ERR_ARG, "not a genotype-matrix result (vs_query_genotype_matrix)");
-  VS_TRY(result_ready(r));
-  HIP_TRY(hipStreamSynchronize(r->idx->stream));   // the matrix is complete when the pointer is handed out: the caller needs no event
+  VS_TRY(device_matrix_ready(r, dev_cells, kKindMatrix, "not a genotype-matrix result (vs_query_genotype_matrix)"));
   *dev_cells = r->d_matrix;
   if (n_rows) *n_rows = r->d.A;
   if (n_cols) *n_cols = r->h_cols.size();
