@@ -273,6 +273,51 @@ int vs_result_get_genotype_matrix(vs_result* r, uint64_t* n_rows, uint64_t* n_co
 /* The matrix as it lies in HBM: n_rows rows of row_pitch bytes, valid until vs_result_free.  The engine has synchronised its
  * stream when this returns: the caller needs no event. */
 int vs_result_genotype_matrix_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint64_t* row_pitch, const void** dev_cells);
+/* Banded LD over regions: the step behind the genotype matrix -- every row of the variant table against the next `window` rows, the
+ * input of pruning, clumping, fine-mapping windows and haplotype-block calls (no reference counterpart).  T, its rows, S and its
+ * n columns are those of vs_query_genotype_matrix over the same regions and sample_ids; A is the number of rows of T.  The dosage
+ * of a cell is d = popcount(cell & 6) of the genotype-matrix cell: 0 for a non-carrier and everywhere on a row the duplicate rule
+ * dropped.  The answer is a band of A x window four-byte cells, band[i * window + k] for the pair of table rows (i, j = i + 1 + k):
+ *   VS_LD_DOT   int32   Sxy = sum over the columns s of d_i(s) * d_j(s), exact
+ *   VS_LD_R2    float   the squared dosage correlation from exact integers: with Sx = sum d = the row's alt_alleles over S and
+ *                       Sxx = sum d^2 = alt_alleles + 2 hom_alt, in 64-bit integers cov = n Sxy - Sx Sy, vx = n Sxx - Sx^2,
+ *                       vy = n Syy - Sy^2, then r2 = (float)((double)cov * (double)cov / ((double)vx * (double)vy)), and 0.0f when
+ *                       vx == 0 or vy == 0 (a monomorphic row, a dropped row, n = 1)
+ * Pairs are taken by table index and nothing else: a pair with i + 1 + k >= A is 0, a pair that straddles the end of the shared
+ * rows is computed like any other; region q's pairs are those inside row_begin[q] .. row_begin[q] + row_count[q].  Every cell of
+ * the band is stored exactly once by the kernel, zeros included.  The result also carries the count record of every table row over
+ * S (vs_allele_counts, what vs_query_allele_counts reports): the r2 was formed from it, and it turns a DOT band into covariance, D
+ * or r.
+ * `regions` and `sample_ids` as for vs_query_genotype_matrix.  Checked on the host, in this order, before the handle's device is
+ * asked for (a handle opened without a device reports them first and VS_ERR_NO_DEVICE otherwise): n == 0, sample_ids == NULL with
+ * n_ids != 0, non-NULL sample_ids with n_ids == 0, window == 0 or window > 256, stat neither VS_LD_DOT nor VS_LD_R2 -> VS_ERR_ARG;
+ * id 0 or id >= num_samples -> VS_ERR_UNKNOWN_SAMPLE.  The band is formed from a temporary genotype matrix (rows x row_pitch
+ * bytes; it is not part of the result: it goes back to the handle's pool at the end of the call or, where the call returns with
+ * its kernels enqueued -- option "async_submit", the default --, as soon as an accessor or vs_result_free has waited for them, the
+ * result still open); matrix and band together may not exceed option
+ * "matrix_max_mib" MiB (default 32 GiB): beyond it the call is refused with VS_ERR_ARG once the plan has given the rows and before
+ * anything is allocated; the message names rows, columns, window and bytes.
+ * Every batch size takes the batch pipeline; an LD batch is never speculative and leaves the handle's type-6 state as it was.  The
+ * result holds the type-6 per-region arrays and variant table, no carrier arena, the counts and the band: vs_result_get_raw /
+ * vs_result_get_view with with_carriers = 0, vs_result_layout (arena and lists 0), vs_result_fill_ms (the batch's own kernels: the
+ * counts, the temporary matrix and the band kernel), vs_result_totals (n_carriers = the nonzero cells of the matrix, as for the
+ * matrix query) and vs_result_format_region ("PosA\tRefA\tAltA\tPosB\tRefB\tAltB\t" + "Dot" or "R2", then one line for every pair
+ * a < b of the region's reported, non-dropped rows whose table indices are at most `window` apart, the value as %d or %.6g) work;
+ * with_carriers = 1, vs_result_digest, vs_result_pack_headers / _pack_regions and vs_comm_allgather_regions* fail with
+ * VS_ERR_UNSUPPORTED, vs_result_get_allele_counts, vs_result_get_sample_burden and vs_result_get_genotype_matrix with VS_ERR_ARG. */
+#define VS_LD_DOT 0u
+#define VS_LD_R2 1u
+int vs_query_ld_band(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t window,
+                     uint32_t stat, vs_result** out);
+/* The band of an LD result copied into page-locked memory owned by the result: band[i * window + k] (int32 under VS_LD_DOT, float
+ * under VS_LD_R2: `stat` says which), counts[i] the count record of table row i over S, col_ids[c] the sample id of column c.
+ * Every out-pointer but `band` may be NULL.  VS_ERR_ARG on any other result. */
+int vs_result_get_ld_band(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* window, uint32_t* stat, const uint32_t** col_ids,
+                          const vs_allele_counts** counts, const void** band);
+/* Band and counts as they lie in HBM (n_rows x window cells of 4 bytes; n_rows records of 16 bytes), valid until vs_result_free.
+ * The engine has synchronised its stream when this returns: the caller needs no event. */
+int vs_result_ld_band_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* window, uint32_t* stat, const void** dev_counts,
+                             const void** dev_band);
 
 /* host view of a sequence result: region i is chars[seq_begin[i] .. seq_begin[i+1]) */
 int vs_result_get_sequences(vs_result* r, uint64_t* n_regions, const uint8_t** region_flags, const uint64_t** seq_begin,

@@ -300,6 +300,60 @@ class QueryResult:
             out.append({"pos": int(pos), "ref": ref, "alt": alt, "calls": calls})
         return out
 
+    LD_STATS = {"dot": 0, "r2": 1}   # VS_LD_DOT, VS_LD_R2
+
+    def ld_band(self):
+        """An LD result (VariantStore.ld_band) as numpy arrays: `band` ((A, W): band[i, k] belongs to the pair of table rows
+        (i, i + 1 + k); int32 dot products of the dosages under stat "dot", float32 squared correlations under "r2"; 0 where
+        i + 1 + k >= A), `counts` (structured as for allele_counts: the count record of every table row over the query's
+        samples), `columns` (uint32[C], the sample ids the statistics run over), `window`, `stat`, the table's `rows` and per
+        region `row_begin` and `row_count` -- region q's pairs are those inside rows[row_begin[q] : row_begin[q] + row_count[q]].
+        Copies, valid after the result is closed."""
+        a, c = C.c_uint64(), C.c_uint64()
+        w, st = C.c_uint32(), C.c_uint32()
+        cols = C.POINTER(C.c_uint32)()
+        cnt = C.POINTER(_lib.AlleleCounts)()
+        p = C.c_void_p()
+        _check(self._lib.vs_result_get_ld_band(self._h, C.byref(a), C.byref(c), C.byref(w), C.byref(st), C.byref(cols), C.byref(cnt),
+                                               C.byref(p)), "vs_result_get_ld_band")
+        na, nc, nw = int(a.value), int(c.value), int(w.value)
+        stat = "r2" if st.value == self.LD_STATS["r2"] else "dot"
+        dtype = np.float32 if stat == "r2" else np.int32
+        if na:
+            band = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(na * nw * 4,)).view(dtype).reshape(na, nw).copy()
+            counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint8)), shape=(na * 16,)).view(self.COUNT_DTYPE).copy()
+        else:
+            band, counts = np.zeros((0, nw), dtype), np.zeros(0, self.COUNT_DTYPE)
+        raw = self.raw(with_carriers=False)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "columns": np.ctypeslib.as_array(cols, shape=(nc,)).copy(), "window": nw, "stat": stat, "counts": counts,
+                "band": band}
+
+    def ld_band_device(self):
+        """(band address, counts address, n_rows, n_cols, window, stat) of an LD result as it lies in this GPU's memory: n_rows x
+        window cells of 4 bytes (int32 under "dot", float32 under "r2") and n_rows count records of four uint32, complete when
+        this returns and valid until the result is closed."""
+        a, c = C.c_uint64(), C.c_uint64()
+        w, st = C.c_uint32(), C.c_uint32()
+        pc, pb = C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_ld_band_device(self._h, C.byref(a), C.byref(c), C.byref(w), C.byref(st), C.byref(pc), C.byref(pb)),
+               "vs_result_ld_band_device")
+        return (int(pb.value or 0), int(pc.value or 0), int(a.value), int(c.value), int(w.value),
+                "r2" if st.value == self.LD_STATS["r2"] else "dot")
+
+    def region_ld(self, q):
+        """The pairs region q of an LD result reports: a list of dicts with `a` and `b` (each (pos, ref, alt)) and `value` (int under
+        "dot", float under "r2") for every pair of the region's reported rows at most the window apart in the table."""
+        lines = self.region_text(q).split("\n")
+        dot = lines[0].endswith("Dot")
+        out = []
+        for line in lines[1:]:
+            if not line:
+                continue
+            pa, ra, aa, pb, rb, ab, v = line.split("\t")
+            out.append({"a": (int(pa), ra, aa), "b": (int(pb), rb, ab), "value": int(v) if dot else float(v)})
+        return out
+
     def region_variants(self, q) -> List[Variant]:
         out = []
         for line in self.region_text(q).split("\n")[1:]:
@@ -534,6 +588,18 @@ class VariantStore:
         res.subset_size = subset
         return res
 
+    def _sample_set(self, samples):
+        """(the id array or None, its pointer, its length) of a column request's `samples`: names or ids, None for the whole cohort."""
+        if samples is None:
+            return None, None, 0
+        if isinstance(samples, (str, bytes)):
+            samples = [samples]
+        ids = np.ascontiguousarray([self.sample_id(x) if isinstance(x, str) else int(x) for x in samples], dtype=np.uint32)
+        ids_ptr, n_ids = ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.shape[0]
+        if n_ids == 0:   # (the C ABI's NULL-or-non-empty rule: an empty list is not the whole cohort)
+            ids_ptr = (C.c_uint32 * 1)()
+        return ids, ids_ptr, n_ids
+
     def sample_burden(self, regions, samples=None, min_ac=0, max_ac=None) -> QueryResult:
         """Per-sample burden over regions (vs_query_sample_burden): a regions x samples matrix -- for every region and every
         sample of `samples` (names or ids, taken as a set; None: the whole cohort) the variants of the region the sample
@@ -542,15 +608,7 @@ class VariantStore:
         QueryResult.sample_burden / sample_burden_device / region_text."""
         arr, ptr, n = _regions_array(regions)
         h = C.c_void_p()
-        if samples is None:
-            ids, ids_ptr, n_ids = None, None, 0
-        else:
-            if isinstance(samples, (str, bytes)):
-                samples = [samples]
-            ids = np.ascontiguousarray([self.sample_id(x) if isinstance(x, str) else int(x) for x in samples], dtype=np.uint32)
-            ids_ptr, n_ids = ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.shape[0]
-            if n_ids == 0:   # (the C ABI's NULL-or-non-empty rule: an empty list is not the whole cohort)
-                ids_ptr = (C.c_uint32 * 1)()
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
         _check(self._lib.vs_query_sample_burden(self._h, ptr, n, ids_ptr, n_ids, int(min_ac),
                                                 0xFFFFFFFF if max_ac is None else int(max_ac), C.byref(h)), "vs_query_sample_burden")
         return QueryResult(self, h)
@@ -562,16 +620,27 @@ class VariantStore:
         genotype_matrix_device / region_genotypes / region_text."""
         arr, ptr, n = _regions_array(regions)
         h = C.c_void_p()
-        if samples is None:
-            ids, ids_ptr, n_ids = None, None, 0
-        else:
-            if isinstance(samples, (str, bytes)):
-                samples = [samples]
-            ids = np.ascontiguousarray([self.sample_id(x) if isinstance(x, str) else int(x) for x in samples], dtype=np.uint32)
-            ids_ptr, n_ids = ids.ctypes.data_as(C.POINTER(C.c_uint32)), ids.shape[0]
-            if n_ids == 0:   # (the C ABI's NULL-or-non-empty rule: an empty list is not the whole cohort)
-                ids_ptr = (C.c_uint32 * 1)()
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
         _check(self._lib.vs_query_genotype_matrix(self._h, ptr, n, ids_ptr, n_ids, C.byref(h)), "vs_query_genotype_matrix")
+        return QueryResult(self, h)
+
+    def ld_band(self, regions, samples=None, window=64, stat="r2") -> QueryResult:
+        """Banded LD over regions (vs_query_ld_band): every row of the variant table a type-6 batch over `regions` produces against
+        the next `window` rows (1 .. 256), over the dosages of `samples` (names or ids, taken as a set; None: the whole cohort).
+        `stat`: "r2" (squared dosage correlation, float32) or "dot" (sum of dosage products, int32, exact).  `regions` as for
+        allele_counts.  Read the result with QueryResult.ld_band / ld_band_device / region_ld / region_text."""
+        arr, ptr, n = _regions_array(regions)
+        h = C.c_void_p()
+        if isinstance(stat, str):
+            if stat.lower() not in QueryResult.LD_STATS:
+                raise ValueError(f"stat {stat!r}: 'r2' or 'dot'")
+            stat = QueryResult.LD_STATS[stat.lower()]
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        window = int(window)
+        if not 0 <= window <= 0xFFFFFFFF:   # (ctypes would wrap it: 0 is refused by the C ABI like any window outside 1 .. 256)
+            window = 0
+        _check(self._lib.vs_query_ld_band(self._h, ptr, n, ids_ptr, n_ids, window, int(stat) & 0xFFFFFFFF, C.byref(h)),
+               "vs_query_ld_band")
         return QueryResult(self, h)
 
     def get_sample_var_in_ref(self, regions, sample) -> QueryResult:

@@ -112,6 +112,8 @@ bool dir_exists(const std::string& p) {
 struct Args {
   std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out, samples_file;
   uint32_t min_ac = 0, max_ac = UINT32_MAX;   // `burden`: the alternate-allele-count window of the rows that count
+  uint32_t ld_window = 64;   // `ld`: every row against the next ld_window rows; --dot: dot products instead of r^2
+  bool ld_dot = false;
   uint32_t type = 0, mode = 0;
   uint64_t hops = 0;
   bool have_hops = false;
@@ -708,7 +710,19 @@ int genotypes_usage() {
   return EXIT_FAILURE;
 }
 
-int counts_main(const Args& a, bool burden = false, bool genotypes = false) {
+// `variantstore ld`: banded LD of the regions (vs_query_ld_band) over the same samples.  Output as `counts`: "#region <i> <x>:<y>",
+// then the region's text ("PosA RefA AltA PosB RefB AltB R2|Dot", one line per pair of its reported rows at most -w rows apart).
+int ld_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore ld -p <output-prefix> -r <region> [-S <sample-name-file>] [-w <window>] [--dot] [-o <outfile>]\n"
+               "                        [--device <n>]\n\n"
+               "        For every pair of variants query type 6 reports in a region that lie at most <window> rows (default 64, at\n"
+               "        most 256) apart: the squared correlation of the samples' alternate-allele dosages (of the whole cohort or of\n"
+               "        the samples named in the file), or with --dot the sum of the dosage products.\n";
+  return EXIT_FAILURE;
+}
+
+int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
   if (rc != VS_OK) die(rc, "load");
@@ -733,10 +747,11 @@ int counts_main(const Args& a, bool burden = false, bool genotypes = false) {
   std::vector<vs_region> batch;
   for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
   vs_result* res = nullptr;
-  if (genotypes) rc = vs_query_genotype_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
+  if (ld) rc = vs_query_ld_band(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_window, a.ld_dot ? VS_LD_DOT : VS_LD_R2, &res);
+  else if (genotypes) rc = vs_query_genotype_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
   else if (burden) rc = vs_query_sample_burden(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.min_ac, a.max_ac, &res);
   else rc = vs_query_allele_counts(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
-  if (rc != VS_OK) die(rc, genotypes ? "genotypes" : burden ? "burden" : "counts");
+  if (rc != VS_OK) die(rc, ld ? "ld" : genotypes ? "genotypes" : burden ? "burden" : "counts");
   std::ofstream file;
   if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
   std::ostream& out = a.outfile.empty() ? std::cout : file;
@@ -794,10 +809,12 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if (a.cmd == "ld" && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if (a.cmd == "ld" && f == "--dot") a.ld_dot = true;
       else if (f == "-r" || f == "--region") a.region = need(i);
       else if (f == "-S" || f == "--samples") a.samples_file = need(i);
       else if (f == "-o" || f == "--output_file") a.outfile = need(i);
@@ -816,6 +833,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "genotypes") {
     if (a.prefix.empty() || a.region.empty()) return genotypes_usage();
     return counts_main(a, /*burden=*/false, /*genotypes=*/true);
+  }
+  if (a.cmd == "ld") {
+    if (a.prefix.empty() || a.region.empty()) return ld_usage();
+    return counts_main(a, /*burden=*/false, /*genotypes=*/false, /*ld=*/true);
   }
   if (a.cmd == "construct") {
     if (a.ref.empty() || a.vcf.empty() || a.prefix.empty()) return usage();

@@ -195,6 +195,8 @@ struct vs_result {
   vs_index* idx = nullptr;
   DevResult d{};
   std::vector<DevBuf> bufs;
+  std::vector<DevBuf> call_temps;   // temporaries of the call that an enqueued batch's kernels still use and no accessor reads (an LD batch's
+                                    // genotype matrix): back to the pool as soon as the batch is known to have finished (result_ready)
   // host copies
   bool have_headers = false, have_carriers = false;
   std::vector<uint8_t> h_flags;
@@ -235,7 +237,7 @@ struct vs_result {
   const VariantRow* raw_rows = nullptr;
   const uint8_t* raw_arena = nullptr;   // NULL: carriers not copied
   int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts;
-                 // kKindBurden: per-sample burden; kKindMatrix: genotype matrix
+                 // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -251,6 +253,12 @@ struct vs_result {
   uint8_t* d_matrix = nullptr;
   uint64_t mx_pitch = 0;
   std::vector<uint8_t> sl_matrix;   // the rows of ONE region, fetched when the matrix is not on the host (vs_result_format_region)
+  // LD results (vs_query_ld_band): table rows x window cells of four bytes in HBM (int32 under VS_LD_DOT, float under VS_LD_R2), the
+  // count record of every table row in d_counts / counts_pin as for a count result, the column ids h_cols, the nonzero cells of the
+  // (temporary) genotype matrix in d_cell_total; the band's page-locked host copy is cells_pin
+  uint32_t* d_band = nullptr;
+  uint32_t ld_window = 0, ld_stat = 0;
+  std::vector<uint32_t> sl_band;   // the band rows of ONE region (vs_result_format_region)
   // sequence results (query types 2 and 3)
   DevSeqResult sq{};
   uint64_t seq_bytes = 0;
@@ -265,9 +273,12 @@ static int refuse_counts(const char* what) {
 }
 constexpr int kKindBurden = 9;   // ... of a burden result: the rows of type 6, a regions x samples matrix instead of carrier lists
 constexpr int kKindMatrix = 10;  // ... of a genotype-matrix result: the rows of type 6, a table rows x samples byte matrix instead of carrier lists
-static bool no_lists(const vs_result* r) { return r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix; }
+constexpr int kKindLd = 11;      // ... of an LD result: the rows of type 6, a table rows x window band of pair statistics instead of carrier lists
+static bool no_lists(const vs_result* r) { return r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd; }
 static int refuse_no_lists(const vs_result* r, const char* what) {
   if (r->kind == kKindCounts) return refuse_counts(what);
+  if (r->kind == kKindLd)
+    return fail(VS_ERR_UNSUPPORTED, "%s: an LD result holds a rows x window band of pair statistics, no carrier lists (vs_result_get_ld_band)", what);
   if (r->kind == kKindMatrix)
     return fail(VS_ERR_UNSUPPORTED, "%s: a genotype-matrix result holds a rows x samples matrix, no carrier lists (vs_result_get_genotype_matrix)", what);
   return fail(VS_ERR_UNSUPPORTED, "%s: a burden result holds a regions x samples matrix, no carrier lists (vs_result_get_sample_burden)", what);
@@ -896,6 +907,7 @@ static int result_ready(vs_result* r) {
     HIP_TRY(hipEventSynchronize(r->ev_fill[1]));
     HIP_TRY(hipEventElapsedTime(&r->fill_ms, r->ev_fill[0], r->ev_fill[1]));
   }
+  release_bufs(r->idx, r->call_temps);   // (the batch has finished: nothing in flight reads them, the result never does)
   return VS_OK;
 }
 
@@ -1119,14 +1131,16 @@ static int capture_totals(vs_result* r) {
 // What a shared batch (run_type6_shared) is for: the type-6 expansion of carrier lists, or one of the three column requests over
 // the same rows -- allele counts, the burden matrix, the genotype matrix.  The columns: the subset's bit mask in host memory (NULL:
 // the whole cohort) and its words; for burden and matrix the columns in front of each word of the mask (NULL with the mask) and
-// their number; for burden the window (0 .. UINT32_MAX: every reported row counts, k_allele_counts is not run).
-enum class ReqKind { Lists, Counts, Burden, Matrix };
+// their number; for burden the window (0 .. UINT32_MAX: every reported row counts, k_allele_counts is not run); for LD the band's
+// window and statistic.
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
   uint32_t words = 0;
   const uint32_t* rank = nullptr;
   uint32_t n_cols = 0, min_ac = 0, max_ac = UINT32_MAX;
+  uint32_t ld_window = 0, ld_stat = 0;
   bool window() const { return min_ac != 0 || max_ac != UINT32_MAX; }
 };
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
@@ -1272,8 +1286,10 @@ static int launch_burden(vs_index* idx, vs_result* r, const uint32_t* u_site, ui
 }
 
 // The genotype matrix of a count batch: one workgroup per (block of table rows, column tile).  The tile is at most the pitch and
-// at most kMatrixTileBytes; a block takes as many rows as fit beside it, up to one per thread.
-static int launch_matrix(vs_index* idx, vs_result* r, const uint32_t* u_site, uint64_t U, const uint64_t* d_mask, const uint32_t* d_rank, const SharedReq& mq) {
+// at most kMatrixTileBytes; a block takes as many rows as fit beside it, up to one per thread.  `cells`: the result's matrix, or
+// the temporary one of an LD batch.
+static int launch_matrix(vs_index* idx, vs_result* r, uint8_t* cells, const uint32_t* u_site, uint64_t U, const uint64_t* d_mask, const uint32_t* d_rank,
+                         const SharedReq& mq) {
   const DevResult& d = r->d;
   const uint32_t words = mq.words;
   HIP_TRY(hipMemsetAsync(r->d_cell_total, 0, 16, idx->stream));
@@ -1285,7 +1301,7 @@ static int launch_matrix(vs_index* idx, vs_result* r, const uint32_t* u_site, ui
   a.tile_cols = std::min<uint32_t>(a.pitch, idx->opts.matrix_tile_cols ? idx->opts.matrix_tile_cols : kMatrixTileCols);
   a.n_tiles = (a.pitch + a.tile_cols - 1) / a.tile_cols;
   a.rows_per_block = std::max<uint32_t>(1, std::min<uint32_t>(kMatrixMaxRows, kMatrixTileBytes / a.tile_cols));
-  a.cells = r->d_matrix; a.total = r->d_cell_total;
+  a.cells = cells; a.total = r->d_cell_total;
   const uint64_t blocks = (d.A + a.rows_per_block - 1) / a.rows_per_block * a.n_tiles;
   if (blocks > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu row blocks x %u column tiles)",
                                            (unsigned long long)(blocks / a.n_tiles), a.n_tiles);
@@ -1298,9 +1314,36 @@ static int launch_matrix(vs_index* idx, vs_result* r, const uint32_t* u_site, ui
   return VS_OK;
 }
 
+// The band of an LD batch from its temporary genotype matrix and the table's counts: one workgroup per kLdRows table rows.
+static int launch_ld(vs_index* idx, vs_result* r, const uint8_t* cells, const SharedReq& lq) {
+  const DevResult& d = r->d;
+  if (!d.A) return VS_OK;
+  LdArgs a{};
+  a.cells = cells; a.A = d.A; a.pitch = (uint32_t)r->mx_pitch; a.n_cols = lq.n_cols;
+  a.window = lq.ld_window; a.n_tiles = (lq.ld_window + 15) / 16 + 1;
+  a.counts = r->d_counts; a.band = r->d_band;
+  const uint64_t blocks = (d.A + kLdRows - 1) / kLdRows;
+  if (blocks > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu row blocks)", (unsigned long long)blocks);
+  const size_t lds = (size_t)(kLdRows + 16 * (a.n_tiles - 1)) * kLdStride;
+  const bool small = a.n_tiles <= kLdSmallTiles, r2 = lq.ld_stat == VS_LD_R2;
+  const void* fn = small ? (r2 ? reinterpret_cast<const void*>(&k_ld_band<kLdSmallTiles, true>) : reinterpret_cast<const void*>(&k_ld_band<kLdSmallTiles, false>))
+                         : (r2 ? reinterpret_cast<const void*>(&k_ld_band<kLdMaxTiles, true>) : reinterpret_cast<const void*>(&k_ld_band<kLdMaxTiles, false>));
+  if (lds > (48 << 10)) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const dim3 grid((unsigned)blocks), block(256);
+  if (small) {
+    if (r2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_band<kLdSmallTiles, true>), grid, block, lds, idx->stream, a);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_band<kLdSmallTiles, false>), grid, block, lds, idx->stream, a);
+  } else {
+    if (r2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_band<kLdMaxTiles, true>), grid, block, lds, idx->stream, a);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_band<kLdMaxTiles, false>), grid, block, lds, idx->stream, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Query type 6 over a batch whose regions SHARE rows and carrier lists (every batch of more than 64 regions unless option
-// share_lists is 0), and every count, burden and genotype-matrix batch: the same plan and rows, another consumer (SharedReq).
+// share_lists is 0), and every count, burden, genotype-matrix and LD batch: the same plan and rows, another consumer (SharedReq).
 // Like the private-row batches further down it runs as stages over a context, each a function that reads only what the
 // stages before it left in the SharedCtx:
 //   shared_setup       per-region arrays, regions / mask / ranks on the device, the decisions taken up front, the plan's temporaries
@@ -1309,15 +1352,17 @@ static int launch_matrix(vs_index* idx, vs_result* r, const uint32_t* u_site, ui
 //                      host wait of a batch; a speculative batch does not wait).  A batch that turns out not to be sorted by first
 //                      site is sorted on the device (shared_sort) and planned again; a handle whose last batch was, sorts first
 //   shared_tables      sizes from the totals or the speculation; the table and, by the request's kind, arena | counts | burden cells
-//                      (counts only under a window) | the matrix, refused beyond option matrix_max_mib before anything is allocated
+//                      (counts only under a window) | the matrix, refused beyond option matrix_max_mib before anything is allocated |
+//                      LD: counts, the band and -- with the call's temporaries -- the matrix it is formed from, under the same limit
 //   shared_rows        k_t6_slow (private copies + the literal duplicate rule, only when the plan counted such regions), k_share_rows2
 //                      unless the expansion writes the rows itself; a column request: the site of every row (k_count_slow_sites)
 //   shared_expand      Lists: k_fill_sites2, the shared rows AND their carrier lists in one launch -- with async_fill k_fill_sites on
 //                      the second stream, with resident lists nothing | shared_counts  Counts: k_allele_counts over the table
 //   shared_permute_out an unsorted batch's per-region arrays back in the caller's order
-//   shared_cells       Burden, Matrix, behind the permutation -- the matrix's rows are the regions in the caller's order: k_allele_counts
+//   shared_cells       Burden, Matrix, LD, behind the permutation -- the matrix's rows are the regions in the caller's order: k_allele_counts
 //                      only under a window, k_sample_burden over (region, column tile) pairs and for regions longer than a chunk
-//                      k_burden_split_plan + the SPLIT launch | k_genotype_matrix over (block of table rows, column tile) pairs
+//                      k_burden_split_plan + the SPLIT launch | k_genotype_matrix over (block of table rows, column tile) pairs |
+//                      LD: k_allele_counts over the table, k_genotype_matrix into the temporary, k_ld_band over blocks of table rows
 //   shared_finish      enqueued: the completion event | synchronous: k_post_done, a word in mapped host memory, the host spins on it
 // A column request is never speculative, has no arena, and leaves the handle's type-6 state (size hints, sort hint) as it found
 // it: count batches interleaved with type-6 batches change none of theirs.
@@ -1328,9 +1373,10 @@ struct SharedCtx {
   uint64_t n;
   const SharedReq& req;
   ScratchBufs scratch;
+  ScratchBufs ld_tmp;   // an LD batch's temporary genotype matrix, apart from the rest: an enqueued batch keeps it only until it has finished
   // the consumer, asked once: Lists -- carrier lists in an arena (the result's or the resident one), may speculate, owns the handle's
-  // type-6 hints; else a column request -- no arena, never speculative, hints untouched, the site of EVERY row (u_site).  Burden and
-  // Matrix are consumed behind k_permute_out, Lists and Counts in front of it
+  // type-6 hints; else a column request -- no arena, never speculative, hints untouched, the site of EVERY row (u_site).  Burden,
+  // Matrix and LD are consumed behind k_permute_out, Lists and Counts in front of it
   const bool lists, behind_perm;
   // shared_setup: the decisions taken up front
   bool allow_async = false, async_submit = false, sort_first = false, plan_aside = false, resident = false, spec = false;
@@ -1356,9 +1402,10 @@ struct SharedCtx {
   uint64_t n_fill = 0;          // shared_tables: carrier lists to expand, and the form of the rows and the expansion
   bool async_fill = false, fused = false, lean = false;
   uint32_t* u_site = nullptr;   // shared_rows: the site of every shared row (a column request: of every row)
+  uint8_t* ld_matrix = nullptr; // shared_tables: the temporary genotype matrix of an LD batch (ld_tmp)
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -1543,13 +1590,20 @@ static int shared_plan_batch(SharedCtx& c) {
 }
 
 // The plan's rows are known: a genotype matrix beyond the limit is refused here, before it or the table is allocated.
+// An LD batch: the temporary matrix and the band together, under the same limit.
 static int matrix_fits(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
   const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
   r->mx_pitch = ((uint64_t)c.req.n_cols + 15) & ~15ull;
-  if (r->d.A <= cap / r->mx_pitch) return VS_OK;
+  const uint64_t row_bytes = r->mx_pitch + (c.req.kind == ReqKind::LD ? 4ull * c.req.ld_window : 0);
+  if (r->d.A <= cap / row_bytes) return VS_OK;
   (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
   (void)hipStreamSynchronize(idx->stream);
+  if (c.req.kind == ReqKind::LD)
+    return fail(VS_ERR_ARG, "an LD band of %llu rows x %u columns with window %u takes %llu bytes (%llu of the genotype matrix it is formed from, %llu of the band), "
+                "more than the limit of %llu MiB (option matrix_max_mib): split the batch", (unsigned long long)r->d.A, c.req.n_cols, c.req.ld_window,
+                (unsigned long long)(r->d.A * row_bytes), (unsigned long long)(r->d.A * r->mx_pitch), (unsigned long long)(r->d.A * 4 * c.req.ld_window),
+                (unsigned long long)(cap >> 20));
   return fail(VS_ERR_ARG, "a genotype matrix of %llu rows x %u columns takes %llu bytes (rows %llu bytes apart), more than the limit of %llu MiB "
               "(option matrix_max_mib): split the batch", (unsigned long long)r->d.A, c.req.n_cols, (unsigned long long)(r->d.A * r->mx_pitch),
               (unsigned long long)r->mx_pitch, (unsigned long long)(cap >> 20));
@@ -1595,6 +1649,17 @@ static int shared_tables(SharedCtx& c) {
       VS_TRY(ralloc(r, (size_t)(d.A * r->mx_pitch), &r->d_matrix));
       VS_TRY(ralloc(r, 2, &r->d_cell_total));
       break;
+    case ReqKind::LD: {   // (the matrix kernel's count of nonzero cells lives in the band's buffer, behind the band)
+      VS_TRY(matrix_fits(c));
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(dev_alloc(idx, (size_t)(d.A * r->mx_pitch), (void**)&c.ld_matrix, &c.ld_tmp.bufs));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      const size_t band_words = ((size_t)d.A * q.ld_window + 3) & ~(size_t)3;
+      VS_TRY(ralloc(r, band_words + 4, &r->d_band));
+      r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_band + band_words);
+      r->ld_window = q.ld_window; r->ld_stat = q.ld_stat;
+      break;
+    }
   }
   c.async_fill = c.allow_async && idx->opts.async_fill && c.n_fill > 0;
   c.fused = idx->opts.fill_fused && c.lists && !c.resident && !c.async_fill;
@@ -1713,7 +1778,8 @@ static int shared_counts(SharedCtx& c) {
   c.fill_launches = 1;
   return VS_OK;
 }
-// Burden, Matrix: the matrix between the result's own pair of events (vs_result_fill_ms); a burden filter's counts are inside the pair.
+// Burden, Matrix, LD: the request's kernels between the result's own pair of events (vs_result_fill_ms); a burden filter's counts
+// are inside the pair, and so are the three launches of an LD batch: counts, temporary matrix, band.
 static int shared_cells(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
   VS_TRY(result_events(r));
@@ -1721,7 +1787,11 @@ static int shared_cells(SharedCtx& c) {
   if (c.req.kind == ReqKind::Burden) {
     if (r->d_counts && r->d.A) launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
     VS_TRY(launch_burden(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.req, c.scratch));
-  } else VS_TRY(launch_matrix(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+  } else if (c.req.kind == ReqKind::LD) {
+    if (r->d.A) launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
+    VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+    VS_TRY(launch_ld(idx, r, c.ld_matrix, c.req));
+  } else VS_TRY(launch_matrix(idx, r, r->d_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
   HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
   r->pending = true;
   c.fill_launches = 1;
@@ -1753,7 +1823,11 @@ static int shared_finish(SharedCtx& c) {
   }
   idx->timing_pending = true;
   idx->timing_fill_launches = c.fill_launches;
-  if (c.async_submit) return batch_enqueued(r, c.scratch, /*record_done=*/!c.lean);
+  if (c.async_submit) {
+    VS_TRY(batch_enqueued(r, c.scratch, /*record_done=*/!c.lean));
+    c.ld_tmp.hand_to(r->call_temps);   // (until the completion event has passed: result_ready)
+    return VS_OK;
+  }
   uint64_t* done = idx->pinned + vs_index::kPinDone;
   const uint64_t seq = ++idx->done_seq;
   hipLaunchKernelGGL(k_post_done, dim3(1), dim3(1), 0, idx->stream, done, seq);
@@ -1762,6 +1836,7 @@ static int shared_finish(SharedCtx& c) {
   idx->batch_in_flight = false;
   if (c.async_fill) c.scratch.hand_to(r->bufs);
   c.scratch.release();
+  c.ld_tmp.release();
   return collect_timing(idx);
 }
 
@@ -2013,7 +2088,7 @@ static int run_type6(vs_index* idx, const vs_region* regions, uint64_t n, vs_res
   return run_private_batch(idx, regions, n, r, regions_on_device, site_records, 0, nullptr, allow_async);
 }
 
-// A column request (allele counts, burden, genotype matrix): the plan and the shared rows of type 6, then the request's own kernels
+// A column request (allele counts, burden, genotype matrix, LD band): the plan and the shared rows of type 6, then the request's own kernels
 // over the rows instead of the expansion -- every batch size, never speculative, no arena (SharedCtx::lists).
 static int run_column_batch(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, const SharedReq& req) {
   return run_type6_shared(idx, regions, n, r, is_device_ptr(regions), nullptr, /*allow_async=*/true, /*may_speculate=*/false, req);
@@ -3040,6 +3115,7 @@ void vs_result_free(vs_result* r) {
     if (r->idx->timing_owner == r) (void)collect_timing(r->idx);   // (its events go back to the pool below)
     for (auto& e : r->ev_fill) if (e) { r->idx->ev_pool.push_back(e); e = nullptr; }
     if (r->ev_done) { r->idx->ev_pool.push_back(r->ev_done); r->ev_done = nullptr; }
+    release_bufs(r->idx, r->call_temps);   // (only where result_ready failed)
     release_bufs(r->idx, r->bufs);
     pin_release(r->idx, r->raw_pin);
     pin_release(r->idx, r->counts_pin);
@@ -3139,6 +3215,24 @@ int vs_query_genotype_matrix(vs_index* idx, const vs_region* regions, uint64_t n
     return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", idx->g.num_samples);
   const SharedReq req = column_request(ReqKind::Matrix, mask, rank, cols.size());
   return make_result(idx, kKindMatrix, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
+int vs_query_ld_band(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t window, uint32_t stat,
+                     vs_result** out) {
+  VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "an LD"));
+  if (window == 0 || window > kLdMaxWindow) return fail(VS_ERR_ARG, "an LD window of %u rows (1 .. %u)", window, kLdMaxWindow);
+  if (stat != VS_LD_DOT && stat != VS_LD_R2) return fail(VS_ERR_ARG, "LD statistic %u is neither VS_LD_DOT nor VS_LD_R2", stat);
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));
+  if (mask.size() * 8 > kMatrixMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", idx->g.num_samples);
+  SharedReq req = column_request(ReqKind::LD, mask, rank, cols.size());
+  req.ld_window = window; req.ld_stat = stat;
+  return make_result(idx, kKindLd, out, [&](vs_result* r) {
     r->h_cols = cols;
     return run_column_batch(idx, regions, n, r, req);
   });
@@ -3452,7 +3546,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
         for (uint64_t a = r->h_var_begin[q], e = a + r->h_nvar[q]; a < e; ++a) nc += c[a].x;
       r->n_carriers_kept = nc;
     }
-    if (r->kind == kKindBurden || r->kind == kKindMatrix) {   // the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
+    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd) {   // (LD: of the matrix the band was formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
       VS_TRY(result_ready(r));
       uint64_t nc = 0;
       HIP_TRY(hipMemcpyAsync(&nc, r->d_cell_total, 8, hipMemcpyDeviceToHost, idx->stream));
@@ -3553,6 +3647,54 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
         out += (gt & GT_2) ? '1' : '0';
       }
       out += '\n';
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
+  if (r->kind == kKindLd) {   // the pairs a < b of the region's reported rows whose table indices are at most the window apart
+    const uint64_t W = r->ld_window;
+    const VariantRow* rows;
+    if (r->have_headers) rows = r->h_rows.data() + a0;
+    else if (r->raw_rows) rows = r->raw_rows + a0;
+    else {
+      VS_TRY(fetch(idx, r->sl_rows, (const VariantRow*)r->d.rows + a0, (size_t)(a1 - a0)));
+      rows = r->sl_rows.data();
+    }
+    const uint32_t* b;
+    if (r->cells_pin.p) b = (const uint32_t*)r->cells_pin.p + a0 * W;
+    else {
+      VS_TRY(result_ready(r));
+      VS_TRY(fetch(idx, r->sl_band, (const uint32_t*)r->d_band + a0 * W, (size_t)((a1 - a0) * W)));
+      b = r->sl_band.data();
+    }
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    std::string& out = r->text;
+    out = "PosA\tRefA\tAltA\tPosB\tRefB\tAltB\t";
+    out += r->ld_stat == VS_LD_R2 ? "R2\n" : "Dot\n";
+    auto site = [&](const VariantRow& v) {
+      out += std::to_string(v.pos);
+      out += '\t';
+      out.append(idx->seq_chars, v.ref_off, v.ref_len);
+      out += '\t';
+      out.append(idx->seq_chars, v.alt_off, v.alt_len);
+      out += '\t';
+    };
+    char num[48];
+    for (uint64_t a = a0; a < a1; ++a) {
+      if (rows[a - a0].count_flags & kRowDropped) continue;
+      for (uint64_t k = 0; k < W && a + 1 + k < a1; ++k) {
+        if (rows[a + 1 + k - a0].count_flags & kRowDropped) continue;
+        site(rows[a - a0]);
+        site(rows[a + 1 + k - a0]);
+        const uint32_t cell = b[(a - a0) * W + k];
+        if (r->ld_stat == VS_LD_R2) {
+          float f;
+          memcpy(&f, &cell, 4);
+          snprintf(num, sizeof num, "%.6g\n", (double)f);
+        } else snprintf(num, sizeof num, "%d\n", (int)cell);
+        out += num;
+      }
     }
     *text = out.c_str();
     if (len) *len = out.size();
@@ -3738,6 +3880,35 @@ int vs_result_genotype_matrix_device(vs_result* r, uint64_t* n_rows, uint64_t* n
   if (n_rows) *n_rows = r->d.A;
   if (n_cols) *n_cols = r->h_cols.size();
   if (row_pitch) *row_pitch = r->mx_pitch;
+  return VS_OK;
+}
+
+int vs_result_get_ld_band(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* window, uint32_t* stat, const uint32_t** col_ids,
+                          const vs_allele_counts** counts, const void** band) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!band) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindLd) return fail(VS_ERR_ARG, "not an LD result (vs_query_ld_band)");
+  VS_TRY(array_to_host(r, r->d_band, (size_t)(r->d.A * r->ld_window) * 4, &r->cells_pin, "LD band"));
+  VS_TRY(counts_to_host(r));
+  *band = r->cells_pin.p;
+  if (counts) *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (window) *window = r->ld_window;
+  if (stat) *stat = r->ld_stat;
+  if (col_ids) *col_ids = r->h_cols.data();
+  return VS_OK;
+}
+
+int vs_result_ld_band_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* window, uint32_t* stat, const void** dev_counts,
+                             const void** dev_band) {
+  VS_TRY(device_matrix_ready(r, dev_band, kKindLd, "not an LD result (vs_query_ld_band)"));
+  *dev_band = r->d_band;
+  if (dev_counts) *dev_counts = r->d_counts;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (window) *window = r->ld_window;
+  if (stat) *stat = r->ld_stat;
   return VS_OK;
 }
 

@@ -57,6 +57,9 @@
 //  k_burden_split_plan   (vs_query_sample_burden: no reference counterpart); the chunks of the regions too long for one workgroup
 // k_genotype_matrix     what both reduce: table rows x samples, a byte per call, each (row block, column tile) built in LDS and
 //                       stored once (vs_query_genotype_matrix: no reference counterpart)
+// k_ld_band             the band of D D^T over that matrix's dosages -- every table row against the next W rows -- on the matrix
+//                       cores (v_mfma_i32_16x16x64_i8, exact), as dot products or r^2 (vs_query_ld_band: no reference counterpart;
+//                       the one kernel here on the matrix cores; by DESIGN 5e's count its reads of the matrix bound it, not the MFMAs)
 #pragma once
 #include "k_image.hip.h"
 #include "k_sites.hip.h"
@@ -71,3 +74,4 @@
 #include "k_counts.hip.h"
 #include "k_burden.hip.h"
 #include "k_matrix.hip.h"
+#include "k_ld.hip.h"
