@@ -197,6 +197,41 @@ int vs_query_allele_counts(vs_index* idx, const vs_region* regions, uint64_t n, 
 /* The counts of an allele-count result, copied into page-locked memory owned by the result: counts[i] belongs to
  * vs_result_raw.rows[i] (table order), so region q's are counts[row_begin[q] .. row_begin[q] + row_count[q]). */
 int vs_result_get_allele_counts(vs_result* r, uint64_t* n_rows, const vs_allele_counts** counts);
+/* Grouped allele counts: the counts above for each of several disjoint GROUPS of samples in one pass -- cases and controls, the
+ * populations of a cohort, batches (no reference counterpart: what a caller would get from one vs_query_allele_counts call per group).
+ * sample_ids[i] belongs to group group_of[i] in 0 .. n_groups - 1 (both HOST arrays of n_ids entries); a sample that is not listed
+ * belongs to no group, the same (sample, group) pair given twice counts once, a group may be empty (size 0, all counts 0).
+ * counts[i * n_groups + g] is the vs_allele_counts record of table row i over the samples of group g, with exactly the semantics of
+ * vs_query_allele_counts with that group as the subset (index genotype bits: a `1|2` call counts 2 on both ALT rows, a haploid `1` is
+ * gt_1 alone; a row dropped by the duplicate rule counts 0 in every group).  A batch whose table is empty gives 0 rows and is no error.
+ * `regions` as for vs_query_allele_counts (host or device memory, n >= 1).  Checked on the host, in this order, before the handle's
+ * device is asked for (a handle opened without a device reports them first and VS_ERR_NO_DEVICE otherwise): n == 0, NULL sample_ids,
+ * NULL group_of, n_ids == 0, n_groups == 0 or n_groups > VS_GROUPS_MAX -> VS_ERR_ARG; some group_of[i] >= n_groups -> VS_ERR_ARG; id 0
+ * ("ref") or an id >= num_samples -> VS_ERR_UNKNOWN_SAMPLE; a sample listed in two different groups -> VS_ERR_ARG (the message names
+ * the sample id and both groups); a group name (group_names: NULL, or n_groups strings that are copied into the result) with a tab
+ * or a newline -> VS_ERR_ARG.  The kernel keeps one label byte per sample id in LDS, 32 KiB of it (beside 29 KiB of accumulators,
+ * staged genotype words and wave state: two workgroups per CU), and its packed 16-bit count fields hold 2 x samples: a cohort of more
+ * than 32768 sample ids ("ref" included) is refused with VS_ERR_UNSUPPORTED.
+ * rows x n_groups x 16 bytes are held to option "matrix_max_mib" (default 32 GiB): a larger request is refused with VS_ERR_ARG once
+ * the plan has given the rows and before anything is allocated; the message names rows, groups and bytes.
+ * Every batch size takes the batch pipeline; a grouped-count batch is never speculative and leaves the handle's type-6 state as it
+ * was.  The result holds the type-6 per-region arrays and variant table, no carrier arena, and the records: vs_result_get_raw /
+ * vs_result_get_view with with_carriers = 0, vs_result_layout (arena and lists 0), vs_result_fill_ms (the group kernel),
+ * vs_result_totals (n_carriers = the sum of `carriers` over the rows every region reports and all groups) and
+ * vs_result_format_region ("Pos\tRef\tAlt\tGroup\tN\tCarriers\tAC\tHomAlt\tPhased\n", then one line per reported, non-dropped row
+ * and per group in group order; Group is the group's name, or its decimal index without names; N its size) work; with_carriers = 1,
+ * vs_result_digest, vs_result_pack_headers / _pack_regions and vs_comm_allgather_regions* fail with VS_ERR_UNSUPPORTED, the other
+ * kinds' getters with VS_ERR_ARG. */
+#define VS_GROUPS_MAX 64u
+int vs_query_group_counts(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, const uint32_t* group_of,
+                          uint64_t n_ids, uint32_t n_groups, const char* const* group_names, vs_result** out);
+/* The records of a grouped-count result copied into page-locked memory owned by the result: counts[i * n_groups + g];
+ * group_sizes[g] the number of distinct samples of group g (either may be NULL but `counts`).  VS_ERR_ARG on any other result. */
+int vs_result_get_group_counts(vs_result* r, uint64_t* n_rows, uint32_t* n_groups, const uint32_t** group_sizes,
+                               const vs_allele_counts** counts);
+/* The records as they lie in HBM: n_rows x n_groups records of 16 bytes, row-major, valid until vs_result_free.  The engine has
+ * synchronised its stream when this returns: the caller needs no event. */
+int vs_result_group_counts_device(vs_result* r, uint64_t* n_rows, uint32_t* n_groups, const void** dev_counts);
 /* Per-sample burden over regions: the counts above along the other axis -- a regions x samples matrix, the input of gene-burden
  * and collapsing tests and of per-sample QC counts (no reference counterpart: what a caller of type 6 would reduce on the host
  * from every carrier list).  Let R(q) be the rows type 6 reports for region q (same order, duplicate rule and region flags; a
@@ -518,7 +553,8 @@ void vs_comm_destroy(vs_comm* c);
  *                     the capacity of its recording walk (tests of that path)
  *   "burden_chunk"    rows of a region one workgroup of the burden kernel walks (vs_query_sample_burden): a region with more is
  *                     split between several, which add to its cells with atomics.  0 (default): 4096; else 64..65536
- *   "matrix_max_mib"  the largest genotype matrix (vs_query_genotype_matrix), in MiB, a batch may ask for.  0 (default): 32 GiB
+ *   "matrix_max_mib"  the largest genotype matrix (vs_query_genotype_matrix; also an LD batch's matrix + band and the records of
+ *                     vs_query_group_counts), in MiB, a batch may ask for.  0 (default): 32 GiB
  *   "matrix_tile_cols" columns of a workgroup's tile of the matrix kernel: 0 (default): 4096; else a multiple of 16 in 16..65536
  *                     (small cohorts reach tile boundaries with it)
  * Tuning builds (VS_BUILD_TUNING=1 python -m variantstore_amd.build --force) add "lat_debug", "fill_fused", "fill_chunk",

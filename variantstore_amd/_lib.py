@@ -98,6 +98,11 @@ SYMBOLS = {
     "vs_query_var_in_ref_device": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P)]),
     "vs_query_allele_counts": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(_P)]),
     "vs_result_get_allele_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.POINTER(AlleleCounts))]),
+    "vs_query_group_counts": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64,
+                                        C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(_P)]),
+    "vs_result_get_group_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)),
+                                             C.POINTER(C.POINTER(AlleleCounts))]),
+    "vs_result_group_counts_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]),
     "vs_query_sample_burden": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32,
                                          C.POINTER(_P)]),
     "vs_result_get_sample_burden": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint32)),

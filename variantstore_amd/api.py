@@ -236,6 +236,49 @@ class QueryResult:
                         "phased": int(ph), "af": ac / (2.0 * self.subset_size) if self.subset_size else 0.0})
         return out
 
+    def group_counts(self):
+        """A grouped-count result (VariantStore.group_counts) as numpy arrays: the variant table's `rows`, `counts` (structured
+        as for allele_counts, shape (A, G): counts[i, g] is row i over the samples of group g), `group_sizes` (uint32[G]),
+        `group_names` (list of G strings) and per region `row_begin`, `row_count` and `flags`.  Copies, valid after the result
+        is closed."""
+        n, g = C.c_uint64(), C.c_uint32()
+        sizes = C.POINTER(C.c_uint32)()
+        p = C.POINTER(_lib.AlleleCounts)()
+        _check(self._lib.vs_result_get_group_counts(self._h, C.byref(n), C.byref(g), C.byref(sizes), C.byref(p)),
+               "vs_result_get_group_counts")
+        a, ng = int(n.value), int(g.value)
+        counts = (np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(a * ng * 16,)).view(self.COUNT_DTYPE).copy()
+                  if a else np.zeros(0, self.COUNT_DTYPE)).reshape(a, ng)
+        raw = self.raw(with_carriers=False)
+        names = getattr(self, "group_names", None) or [str(i) for i in range(ng)]
+        return {"rows": raw["rows"].copy(), "counts": counts, "group_sizes": np.ctypeslib.as_array(sizes, shape=(ng,)).copy(),
+                "group_names": list(names), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "flags": raw["region_flags"].copy()}
+
+    def region_group_counts(self, q):
+        """The rows region q of a grouped-count result reports (dropped ones left out): a list of dicts with pos, ref, alt and
+        `groups`, which maps each group's name to carriers, alt_alleles, hom_alt, phased, n (the group's size) and
+        af = alt_alleles / (2 n) -- 0.0 for an empty group."""
+        out = []
+        for line in self.region_text(q).split("\n")[1:]:
+            if not line:
+                continue
+            pos, ref, alt, name, n, car, ac, hom, ph = line.split("\t")
+            if not out or (out[-1]["pos"], out[-1]["ref"], out[-1]["alt"]) != (int(pos), ref, alt) or name in out[-1]["groups"]:
+                out.append({"pos": int(pos), "ref": ref, "alt": alt, "groups": {}})
+            n, ac = int(n), int(ac)
+            out[-1]["groups"][name] = {"carriers": int(car), "alt_alleles": ac, "hom_alt": int(hom), "phased": int(ph), "n": n,
+                                       "af": ac / (2.0 * n) if n else 0.0}
+        return out
+
+    def group_counts_device(self):
+        """(address, A, G) of a grouped-count result's records as they lie in this GPU's memory: A x G records of four uint32
+        (carriers, alt_alleles, hom_alt, phased), row-major, complete when this returns and valid until the result is closed."""
+        n, g = C.c_uint64(), C.c_uint32()
+        p = C.c_void_p()
+        _check(self._lib.vs_result_group_counts_device(self._h, C.byref(n), C.byref(g), C.byref(p)), "vs_result_group_counts_device")
+        return int(p.value or 0), int(n.value), int(g.value)
+
     BURDEN_DTYPE = np.dtype([("variants", "<u4"), ("alt_alleles", "<u4"), ("hom_alt", "<u4"), ("phased", "<u4")])
 
     def sample_burden(self):
@@ -586,6 +629,36 @@ class VariantStore:
         _check(self._lib.vs_query_allele_counts(self._h, ptr, n, ids_ptr, n_ids, C.byref(h)), "vs_query_allele_counts")
         res = QueryResult(self, h)
         res.subset_size = subset
+        return res
+
+    def group_counts(self, regions, groups) -> QueryResult:
+        """Grouped allele counts over regions (vs_query_group_counts): the rows type 6 reports, each with carriers, alt_alleles,
+        hom_alt and phased over every one of several disjoint groups of samples -- one pass instead of one allele_counts call per
+        group.  `groups`: a dict name -> iterable of samples (names or ids; dict order is group order), or a sequence of such
+        iterables, named "0", "1", ...  A sample that is listed nowhere belongs to no group; a group may be empty.  `regions` as
+        for allele_counts.  Read the result with QueryResult.group_counts / region_group_counts / group_counts_device / region_text."""
+        if isinstance(groups, dict):
+            names, members = [str(k) for k in groups], list(groups.values())
+        else:
+            members = list(groups)
+            names = None
+        ids, gof = [], []
+        for g, m in enumerate(members):
+            if isinstance(m, (str, bytes)):
+                m = [m]
+            for x in m:
+                ids.append(self.sample_id(x) if isinstance(x, str) else int(x))
+                gof.append(g)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        gof = np.ascontiguousarray(gof, dtype=np.uint32)
+        arr, ptr, n = _regions_array(regions)
+        name_arr = (C.c_char_p * len(names))(*[s.encode() for s in names]) if names is not None else None
+        h = C.c_void_p()
+        _check(self._lib.vs_query_group_counts(self._h, ptr, n, ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               gof.ctypes.data_as(C.POINTER(C.c_uint32)), ids.shape[0], len(members), name_arr,
+                                               C.byref(h)), "vs_query_group_counts")
+        res = QueryResult(self, h)
+        res.group_names = names if names is not None else [str(i) for i in range(len(members))]
         return res
 
     def _sample_set(self, samples):

@@ -39,6 +39,7 @@
 #include <ctime>
 #include <fstream>
 #include <iostream>
+#include <map>
 #include <string>
 #include <thread>
 #include <tuple>
@@ -110,7 +111,7 @@ bool dir_exists(const std::string& p) {
 }
 
 struct Args {
-  std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out, samples_file;
+  std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out, samples_file, groups_file;
   uint32_t min_ac = 0, max_ac = UINT32_MAX;   // `burden`: the alternate-allele-count window of the rows that count
   uint32_t ld_window = 64;   // `ld`: every row against the next ld_window rows; --dot: dot products instead of r^2
   bool ld_dot = false;
@@ -722,6 +723,76 @@ int ld_usage() {
   return EXIT_FAILURE;
 }
 
+// `variantstore groups`: allele counts per sample group (vs_query_group_counts).  The -G file holds one `sample<TAB or space>group` per
+// line; the groups are numbered in order of first appearance.  Output as `counts`: "#region <i> <x>:<y>", then the region's text
+// ("Pos Ref Alt Group N Carriers AC HomAlt Phased", one line per reported row and group).
+int groups_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore groups -p <output-prefix> -r <region> -G <sample-group-file> [-o <outfile>] [--device <n>]\n\n"
+               "        Allele counts of the variants query type 6 reports in each region, separately for every group of samples\n"
+               "        (cases / controls, populations, batches): the file holds one `sample group` pair per line, at most 64 groups,\n"
+               "        a sample in at most one of them; samples that are not listed are counted nowhere.\n";
+  return EXIT_FAILURE;
+}
+
+int groups_main(const Args& a) {
+  vs_index* idx = nullptr;
+  int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
+  if (rc != VS_OK) die(rc, "load");
+  auto fail_with = [&](const std::string& msg) { error(msg); vs_index_close(idx); return EXIT_FAILURE; };
+  std::ifstream in(a.groups_file);
+  if (!in) return fail_with("cannot open group file " + a.groups_file);
+  std::vector<uint32_t> ids, group_of;
+  std::vector<std::string> names;
+  std::map<uint32_t, uint32_t> seen;   // sample id -> its group
+  std::string line;
+  while (std::getline(in, line)) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.find_first_not_of(" \t") == std::string::npos) continue;
+    const size_t s0 = line.find_first_not_of(" \t"), s1 = line.find_first_of(" \t", s0);
+    const size_t g0 = s1 == std::string::npos ? s1 : line.find_first_not_of(" \t", s1);
+    if (g0 == std::string::npos) return fail_with("no group on the line: " + line);
+    const std::string sample = line.substr(s0, s1 - s0);
+    std::string group = line.substr(g0);
+    group.erase(group.find_last_not_of(" \t") + 1);
+    uint32_t sid = 0;
+    if (vs_index_sample_id(idx, sample.c_str(), &sid) != VS_OK || sid == 0) return fail_with("Sample not found: " + sample);
+    uint32_t g = (uint32_t)(std::find(names.begin(), names.end(), group) - names.begin());
+    if (g == names.size()) {
+      if (names.size() == VS_GROUPS_MAX) return fail_with("more than " + std::to_string(VS_GROUPS_MAX) + " groups in " + a.groups_file);
+      names.push_back(group);
+    }
+    const auto it = seen.find(sid);
+    if (it != seen.end() && it->second != g) return fail_with("sample " + sample + " is in two groups: " + names[it->second] + " and " + group);
+    seen[sid] = g;
+    ids.push_back(sid);
+    group_of.push_back(g);
+  }
+  if (ids.empty()) return fail_with("no sample-group pairs in " + a.groups_file);
+  std::vector<const char*> name_ptrs;
+  for (auto& n : names) name_ptrs.push_back(n.c_str());
+  std::vector<vs_region> batch;
+  for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
+  vs_result* res = nullptr;
+  rc = vs_query_group_counts(idx, batch.data(), batch.size(), ids.data(), group_of.data(), ids.size(), (uint32_t)names.size(), name_ptrs.data(), &res);
+  if (rc != VS_OK) die(rc, "groups");
+  std::ofstream file;
+  if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
+  std::ostream& out = a.outfile.empty() ? std::cout : file;
+  for (size_t i = 0; i < batch.size(); ++i) {
+    const char* text = nullptr;
+    uint64_t len = 0;
+    rc = vs_result_format_region(res, i, &text, &len);
+    if (rc != VS_OK) die(rc, "result");
+    out << "#region " << i << " " << batch[i].x << ":" << batch[i].y << "\n";
+    out.write(text, len);
+  }
+  out.flush();
+  vs_result_free(res);
+  vs_index_close(idx);
+  return EXIT_SUCCESS;
+}
+
 int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
@@ -809,14 +880,15 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "groups") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "ld" && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "ld" && f == "--dot") a.ld_dot = true;
       else if (f == "-r" || f == "--region") a.region = need(i);
-      else if (f == "-S" || f == "--samples") a.samples_file = need(i);
+      else if (a.cmd == "groups" && (f == "-G" || f == "--groups")) a.groups_file = need(i);
+      else if (a.cmd != "groups" && (f == "-S" || f == "--samples")) a.samples_file = need(i);
       else if (f == "-o" || f == "--output_file") a.outfile = need(i);
       else if (f == "--device") a.device = atoi(need(i).c_str());
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
@@ -825,6 +897,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "counts") {
     if (a.prefix.empty() || a.region.empty()) return counts_usage();
     return counts_main(a);
+  }
+  if (a.cmd == "groups") {
+    if (a.prefix.empty() || a.region.empty() || a.groups_file.empty()) return groups_usage();
+    return groups_main(a);
   }
   if (a.cmd == "burden") {
     if (a.prefix.empty() || a.region.empty()) return burden_usage();

@@ -237,10 +237,15 @@ struct vs_result {
   const VariantRow* raw_rows = nullptr;
   const uint8_t* raw_arena = nullptr;   // NULL: carriers not copied
   int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts;
-                 // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD
+                 // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
+  // grouped-count results (vs_query_group_counts): n_groups records per table row in d_counts / counts_pin (row-major), the groups'
+  // sizes and -- when the caller gave them -- names (else the decimal index stands for a group)
+  uint32_t n_groups = 0;
+  std::vector<uint32_t> group_sizes;
+  std::vector<std::string> group_names;
   // burden results (vs_query_sample_burden): the regions x columns matrix in HBM (16 bytes per cell, row-major), the sum of its
   // `variants` (a device word the kernels add to), the column ids, and the matrix's page-locked host copy
   uint4* d_cells = nullptr;
@@ -274,9 +279,14 @@ static int refuse_counts(const char* what) {
 constexpr int kKindBurden = 9;   // ... of a burden result: the rows of type 6, a regions x samples matrix instead of carrier lists
 constexpr int kKindMatrix = 10;  // ... of a genotype-matrix result: the rows of type 6, a table rows x samples byte matrix instead of carrier lists
 constexpr int kKindLd = 11;      // ... of an LD result: the rows of type 6, a table rows x window band of pair statistics instead of carrier lists
-static bool no_lists(const vs_result* r) { return r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd; }
+constexpr int kKindGroups = 12;  // ... of a grouped-count result: the rows of type 6, a count record per row and sample group instead of carrier lists
+static bool no_lists(const vs_result* r) {
+  return r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups;
+}
 static int refuse_no_lists(const vs_result* r, const char* what) {
   if (r->kind == kKindCounts) return refuse_counts(what);
+  if (r->kind == kKindGroups)
+    return fail(VS_ERR_UNSUPPORTED, "%s: a grouped-count result holds counts per row and group, no carrier lists (vs_result_get_group_counts)", what);
   if (r->kind == kKindLd)
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD result holds a rows x window band of pair statistics, no carrier lists (vs_result_get_ld_band)", what);
   if (r->kind == kKindMatrix)
@@ -1132,8 +1142,8 @@ static int capture_totals(vs_result* r) {
 // the same rows -- allele counts, the burden matrix, the genotype matrix.  The columns: the subset's bit mask in host memory (NULL:
 // the whole cohort) and its words; for burden and matrix the columns in front of each word of the mask (NULL with the mask) and
 // their number; for burden the window (0 .. UINT32_MAX: every reported row counts, k_allele_counts is not run); for LD the band's
-// window and statistic.
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD };
+// window and statistic.  Groups: `mask` is the label table (a byte per sample id, eight to a word), n_cols the number of groups.
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1233,6 +1243,15 @@ static void launch_allele_counts(vs_index* idx, const DevResult& d, const uint32
                                  (const VariantRow*)d.rows, u_site, d.A, U, d_mask, words, out);
   else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_allele_counts<false>), dim3(blocks), dim3(256), 0, idx->stream, idx->d,
                           (const VariantRow*)d.rows, u_site, d.A, U, (const uint64_t*)nullptr, 0u, out);
+}
+
+// k_group_counts over the whole table of a grouped-count batch (d_labels: the label table, `words` words of eight label bytes)
+static void launch_group_counts(vs_index* idx, const DevResult& d, const uint32_t* u_site, uint64_t U, const uint64_t* d_labels, uint32_t words, uint32_t n_groups,
+                                uint4* out) {
+  const uint64_t per_block = 4ull * group_rows_per_wave(n_groups);
+  const unsigned blocks = (unsigned)((d.A + per_block - 1) / per_block);
+  hipLaunchKernelGGL(k_group_counts, dim3(blocks), dim3(256), (size_t)words * 8, idx->stream, idx->d, (const VariantRow*)d.rows, u_site, d.A, U, d_labels, words,
+                     n_groups, out);
 }
 
 // The burden matrix of a count batch whose per-region arrays are in the caller's order: one workgroup per (region, column tile), and
@@ -1343,7 +1362,7 @@ static int launch_ld(vs_index* idx, vs_result* r, const uint8_t* cells, const Sh
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Query type 6 over a batch whose regions SHARE rows and carrier lists (every batch of more than 64 regions unless option
-// share_lists is 0), and every count, burden, genotype-matrix and LD batch: the same plan and rows, another consumer (SharedReq).
+// share_lists is 0), and every count, grouped-count, burden, genotype-matrix and LD batch: the same plan and rows, another consumer (SharedReq).
 // Like the private-row batches further down it runs as stages over a context, each a function that reads only what the
 // stages before it left in the SharedCtx:
 //   shared_setup       per-region arrays, regions / mask / ranks on the device, the decisions taken up front, the plan's temporaries
@@ -1357,7 +1376,8 @@ static int launch_ld(vs_index* idx, vs_result* r, const uint8_t* cells, const Sh
 //   shared_rows        k_t6_slow (private copies + the literal duplicate rule, only when the plan counted such regions), k_share_rows2
 //                      unless the expansion writes the rows itself; a column request: the site of every row (k_count_slow_sites)
 //   shared_expand      Lists: k_fill_sites2, the shared rows AND their carrier lists in one launch -- with async_fill k_fill_sites on
-//                      the second stream, with resident lists nothing | shared_counts  Counts: k_allele_counts over the table
+//                      the second stream, with resident lists nothing | shared_counts  Counts: k_allele_counts over the table,
+//                      Groups: k_group_counts over the table
 //   shared_permute_out an unsorted batch's per-region arrays back in the caller's order
 //   shared_cells       Burden, Matrix, LD, behind the permutation -- the matrix's rows are the regions in the caller's order: k_allele_counts
 //                      only under a window, k_sample_burden over (region, column tile) pairs and for regions longer than a chunk
@@ -1376,7 +1396,7 @@ struct SharedCtx {
   ScratchBufs ld_tmp;   // an LD batch's temporary genotype matrix, apart from the rest: an enqueued batch keeps it only until it has finished
   // the consumer, asked once: Lists -- carrier lists in an arena (the result's or the resident one), may speculate, owns the handle's
   // type-6 hints; else a column request -- no arena, never speculative, hints untouched, the site of EVERY row (u_site).  Burden,
-  // Matrix and LD are consumed behind k_permute_out, Lists and Counts in front of it
+  // Matrix and LD are consumed behind k_permute_out, Lists, Counts and Groups in front of it
   const bool lists, behind_perm;
   // shared_setup: the decisions taken up front
   bool allow_async = false, async_submit = false, sort_first = false, plan_aside = false, resident = false, spec = false;
@@ -1589,6 +1609,18 @@ static int shared_plan_batch(SharedCtx& c) {
   return VS_OK;
 }
 
+// The plan's rows are known: grouped counts beyond the limit (rows x groups records of 16 bytes) are refused here, before they or the
+// table are allocated.
+static int group_counts_fit(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  const uint64_t row_bytes = 16ull * c.req.n_cols;
+  if (r->d.A <= cap / row_bytes) return VS_OK;
+  (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+  (void)hipStreamSynchronize(idx->stream);
+  return fail(VS_ERR_ARG, "grouped counts of %llu rows x %u groups take %llu bytes, more than the limit of %llu MiB (option matrix_max_mib): split the batch",
+              (unsigned long long)r->d.A, c.req.n_cols, (unsigned long long)(r->d.A * row_bytes), (unsigned long long)(cap >> 20));
+}
 // The plan's rows are known: a genotype matrix beyond the limit is refused here, before it or the table is allocated.
 // An LD batch: the temporary matrix and the band together, under the same limit.
 static int matrix_fits(SharedCtx& c) {
@@ -1636,6 +1668,11 @@ static int shared_tables(SharedCtx& c) {
     case ReqKind::Counts:
       VS_TRY(ralloc(r, d.A, &d.rows));
       VS_TRY(ralloc(r, d.A, &r->d_counts));
+      break;
+    case ReqKind::Groups:
+      VS_TRY(group_counts_fit(c));
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(ralloc(r, (size_t)(d.A * q.n_cols), &r->d_counts));
       break;
     case ReqKind::Burden:
       VS_TRY(ralloc(r, d.A, &d.rows));
@@ -1765,13 +1802,14 @@ static int shared_expand(SharedCtx& c) {
   if (!c.n_fill) return VS_OK;
   return c.fused ? shared_expand_fused(c) : fill_lists(idx, r->d, true, c.u_site, c.n_fill);
 }
-// Counts: one launch over the whole table between the result's own pair of events (vs_result_fill_ms).
+// Counts, Groups: one launch over the whole table between the result's own pair of events (vs_result_fill_ms).
 static int shared_counts(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
   if (!r->d.A) return VS_OK;
   VS_TRY(result_events(r));
   HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
-  launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
+  if (c.req.kind == ReqKind::Groups) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, r->d_counts);
+  else launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
   r->pending = true;
@@ -3185,6 +3223,45 @@ int vs_query_allele_counts(vs_index* idx, const vs_region* regions, uint64_t n, 
   return make_result(idx, kKindCounts, out, [&](vs_result* r) { return run_column_batch(idx, regions, n, r, req); });
 }
 
+int vs_query_group_counts(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, const uint32_t* group_of, uint64_t n_ids,
+                          uint32_t n_groups, const char* const* group_names, vs_result** out) {
+  if (!idx || !out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
+  if (n == 0) return fail(VS_ERR_ARG, "a grouped-count batch needs at least one region");
+  if (!sample_ids || !group_of) return fail(VS_ERR_ARG, "null argument: a grouped-count batch takes sample ids and the group of each");
+  if (n_ids == 0) return fail(VS_ERR_ARG, "an empty list of samples: no group has a member");
+  if (n_groups == 0 || n_groups > VS_GROUPS_MAX) return fail(VS_ERR_ARG, "%u groups (1 .. %u)", n_groups, VS_GROUPS_MAX);
+  for (uint64_t i = 0; i < n_ids; ++i)
+    if (group_of[i] >= n_groups) return fail(VS_ERR_ARG, "group %u of sample id %u is out of range (%u groups)", group_of[i], sample_ids[i], n_groups);
+  const uint32_t ns = idx->g.num_samples;
+  for (uint64_t i = 0; i < n_ids; ++i)
+    if (sample_ids[i] == 0 || sample_ids[i] >= ns)
+      return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u is not a sample of the cohort (1 .. %u)", sample_ids[i], ns - 1);
+  std::vector<uint64_t> labels(((size_t)ns + 7) / 8, ~0ull);   // a byte per sample id: kGroupNone = in no group
+  uint8_t* lab = reinterpret_cast<uint8_t*>(labels.data());
+  std::vector<uint32_t> sizes(n_groups, 0);
+  for (uint64_t i = 0; i < n_ids; ++i) {
+    const uint32_t id = sample_ids[i], g = group_of[i];
+    if (lab[id] == kGroupNone) { lab[id] = (uint8_t)g; sizes[g]++; }
+    else if (lab[id] != g) return fail(VS_ERR_ARG, "sample id %u is listed in group %u and in group %u: a sample belongs to at most one group", id, (uint32_t)lab[id], g);
+  }
+  std::vector<std::string> names;
+  if (group_names)
+    for (uint32_t g = 0; g < n_groups; ++g) {
+      if (!group_names[g]) return fail(VS_ERR_ARG, "null name of group %u", g);
+      names.emplace_back(group_names[g]);
+      if (names.back().find_first_of("\t\n") != std::string::npos) return fail(VS_ERR_ARG, "the name of group %u holds a tab or a newline", g);
+    }
+  if (labels.size() * 8 > kGroupLabelMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "the label table of a cohort of %u samples does not fit the group-count kernel's LDS (at most %zu sample ids)", ns, kGroupLabelMaxBytes);
+  const SharedReq req = column_request(ReqKind::Groups, labels, {}, n_groups);
+  return make_result(idx, kKindGroups, out, [&](vs_result* r) {
+    r->n_groups = n_groups;
+    r->group_sizes = sizes;
+    r->group_names = names;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
 int vs_query_sample_burden(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t min_ac, uint32_t max_ac,
                            vs_result** out) {
   VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "a burden"));
@@ -3372,7 +3449,10 @@ static int array_to_host(vs_result* r, const void* dev, size_t bytes, DevBuf* pi
   *pin = b;
   return VS_OK;
 }
-static int counts_to_host(vs_result* r) { return array_to_host(r, r->d_counts, (size_t)r->d.A * sizeof(uint4), &r->counts_pin, "allele counts"); }
+static int counts_to_host(vs_result* r) {   // (a grouped-count result: n_groups records per row)
+  const size_t per_row = r->kind == kKindGroups ? r->n_groups : 1;
+  return array_to_host(r, r->d_counts, (size_t)r->d.A * per_row * sizeof(uint4), &r->counts_pin, "allele counts");
+}
 // Start (stream) the raw copy of a result: rows and -- on request -- the arena go into one page-locked block.  (The caller has passed
 // the gate.)
 static int raw_copy_begin(vs_result* r, bool with_carriers, hipStream_t stream) {
@@ -3546,6 +3626,16 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
         for (uint64_t a = r->h_var_begin[q], e = a + r->h_nvar[q]; a < e; ++a) nc += c[a].x;
       r->n_carriers_kept = nc;
     }
+    if (r->kind == kKindGroups) {   // the same over every group: a carrier in no group counts nowhere
+      VS_TRY(fetch_region_meta(r));
+      VS_TRY(counts_to_host(r));
+      const uint4* c = (const uint4*)r->counts_pin.p;
+      const uint64_t G = r->n_groups;
+      uint64_t nc = 0;
+      for (uint64_t q = 0; q < r->d.Q; ++q)
+        for (uint64_t a = r->h_var_begin[q] * G, e = a + r->h_nvar[q] * G; a < e; ++a) nc += c[a].x;
+      r->n_carriers_kept = nc;
+    }
     if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd) {   // (LD: of the matrix the band was formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
       VS_TRY(result_ready(r));
       uint64_t nc = 0;
@@ -3700,6 +3790,42 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
     if (len) *len = out.size();
     return VS_OK;
   }
+  if (r->kind == kKindGroups) {   // the region's reported rows, a line per row and group
+    VS_TRY(counts_to_host(r));
+    const VariantRow* rows;
+    if (r->have_headers) rows = r->h_rows.data() + a0;
+    else if (r->raw_rows) rows = r->raw_rows + a0;
+    else {
+      VS_TRY(fetch(idx, r->sl_rows, (const VariantRow*)r->d.rows + a0, (size_t)(a1 - a0)));
+      HIP_TRY(hipStreamSynchronize(idx->stream));
+      rows = r->sl_rows.data();
+    }
+    const uint4* c = (const uint4*)r->counts_pin.p;
+    const uint32_t G = r->n_groups;
+    std::string& out = r->text;
+    out = "Pos\tRef\tAlt\tGroup\tN\tCarriers\tAC\tHomAlt\tPhased\n";
+    std::string head;
+    for (uint64_t a = a0; a < a1; ++a) {
+      const VariantRow& v = rows[a - a0];
+      if (v.count_flags & kRowDropped) continue;
+      head = std::to_string(v.pos);
+      head += '\t';
+      head.append(idx->seq_chars, v.ref_off, v.ref_len);
+      head += '\t';
+      head.append(idx->seq_chars, v.alt_off, v.alt_len);
+      head += '\t';
+      for (uint32_t g = 0; g < G; ++g) {
+        const uint4 k = c[a * G + g];
+        out += head;
+        out += r->group_names.empty() ? std::to_string(g) : r->group_names[g];
+        for (uint32_t f : {r->group_sizes[g], k.x, k.y, k.z, k.w}) { out += '\t'; out += std::to_string(f); }
+        out += '\n';
+      }
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
   if (r->kind == kKindCounts) {   // the region's reported rows with their counts
     VS_TRY(counts_to_host(r));
     const VariantRow* rows;
@@ -3829,6 +3955,18 @@ int vs_result_get_allele_counts(vs_result* r, uint64_t* n_rows, const vs_allele_
   return VS_OK;
 }
 
+int vs_result_get_group_counts(vs_result* r, uint64_t* n_rows, uint32_t* n_groups, const uint32_t** group_sizes, const vs_allele_counts** counts) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!counts) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindGroups) return fail(VS_ERR_ARG, "not a grouped-count result (vs_query_group_counts)");
+  VS_TRY(counts_to_host(r));
+  *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_groups) *n_groups = r->n_groups;
+  if (group_sizes) *group_sizes = r->group_sizes.data();
+  return VS_OK;
+}
+
 int vs_result_get_sample_burden(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, const uint32_t** col_ids, const vs_sample_burden** cells) {
   VS_TRY(result_enter(r, Want::Variants, true));
   if (!cells) return fail(VS_ERR_ARG, "null argument");
@@ -3858,6 +3996,14 @@ int vs_result_sample_burden_device(vs_result* r, uint64_t* n_regions, uint64_t* 
   *dev_cells = r->d_cells;
   if (n_regions) *n_regions = r->d.Q;
   if (n_cols) *n_cols = r->h_cols.size();
+  return VS_OK;
+}
+
+int vs_result_group_counts_device(vs_result* r, uint64_t* n_rows, uint32_t* n_groups, const void** dev_counts) {
+  VS_TRY(device_matrix_ready(r, dev_counts, kKindGroups, "not a grouped-count result (vs_query_group_counts)"));
+  *dev_counts = r->d_counts;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_groups) *n_groups = r->n_groups;
   return VS_OK;
 }
 

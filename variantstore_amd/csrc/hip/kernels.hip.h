@@ -53,6 +53,8 @@
 // k_find                Index::find batched
 // k_allele_counts       allele counts per row of a type-6 plan over a sample subset (vs_query_allele_counts: no reference
 //  k_count_slow_sites    counterpart; what a caller of type 6 would count on the host from the carrier lists)
+// k_group_counts        the same counts per sample GROUP in one pass over a row's carriers: a label byte per sample in LDS, one packed
+//                       LDS atomic per carrier, rows x groups records stored once (vs_query_group_counts: no reference counterpart)
 // k_sample_burden       the same counts along the other axis: a regions x samples matrix over each region's reported rows
 //  k_burden_split_plan   (vs_query_sample_burden: no reference counterpart); the chunks of the regions too long for one workgroup
 // k_genotype_matrix     what both reduce: table rows x samples, a byte per call, each (row block, column tile) built in LDS and
@@ -72,6 +74,7 @@
 #include "k_sample_coords.hip.h"
 #include "k_digest.hip.h"
 #include "k_counts.hip.h"
+#include "k_group_counts.hip.h"
 #include "k_burden.hip.h"
 #include "k_matrix.hip.h"
 #include "k_ld.hip.h"
