@@ -1376,10 +1376,10 @@ static int launch_ld(vs_index* idx, vs_result* r, const uint8_t* cells, const Sh
 //   shared_rows        k_t6_slow (private copies + the literal duplicate rule, only when the plan counted such regions), k_share_rows2
 //                      unless the expansion writes the rows itself; a column request: the site of every row (k_count_slow_sites)
 //   shared_expand      Lists: k_fill_sites2, the shared rows AND their carrier lists in one launch -- with async_fill k_fill_sites on
-//                      the second stream, with resident lists nothing | shared_counts  Counts: k_allele_counts over the table,
+//                      the second stream, with resident lists nothing | shared_columns  Counts: k_allele_counts over the table,
 //                      Groups: k_group_counts over the table
 //   shared_permute_out an unsorted batch's per-region arrays back in the caller's order
-//   shared_cells       Burden, Matrix, LD, behind the permutation -- the matrix's rows are the regions in the caller's order: k_allele_counts
+//   shared_columns     Burden, Matrix, LD, behind the permutation -- the matrix's rows are the regions in the caller's order: k_allele_counts
 //                      only under a window, k_sample_burden over (region, column tile) pairs and for regions longer than a chunk
 //                      k_burden_split_plan + the SPLIT launch | k_genotype_matrix over (block of table rows, column tile) pairs |
 //                      LD: k_allele_counts over the table, k_genotype_matrix into the temporary, k_ld_band over blocks of table rows
@@ -1802,34 +1802,23 @@ static int shared_expand(SharedCtx& c) {
   if (!c.n_fill) return VS_OK;
   return c.fused ? shared_expand_fused(c) : fill_lists(idx, r->d, true, c.u_site, c.n_fill);
 }
-// Counts, Groups: one launch over the whole table between the result's own pair of events (vs_result_fill_ms).
-static int shared_counts(SharedCtx& c) {
+// A column request's kernels between the result's own pair of events (vs_result_fill_ms).  Counts, Groups: one launch over the whole
+// table.  Burden, Matrix, LD (behind the permutation): a burden filter's counts are inside the pair, and so are the three launches of
+// an LD batch: counts, temporary matrix, band.
+static int shared_columns(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
-  if (!r->d.A) return VS_OK;
+  if (!c.behind_perm && !r->d.A) return VS_OK;
   VS_TRY(result_events(r));
   HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
   if (c.req.kind == ReqKind::Groups) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, r->d_counts);
-  else launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
+  else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD; Burden only under a window: shared_tables gives it counts)
+    launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
-  r->pending = true;
-  c.fill_launches = 1;
-  return VS_OK;
-}
-// Burden, Matrix, LD: the request's kernels between the result's own pair of events (vs_result_fill_ms); a burden filter's counts
-// are inside the pair, and so are the three launches of an LD batch: counts, temporary matrix, band.
-static int shared_cells(SharedCtx& c) {
-  vs_index* idx = c.idx; vs_result* r = c.r;
-  VS_TRY(result_events(r));
-  HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
-  if (c.req.kind == ReqKind::Burden) {
-    if (r->d_counts && r->d.A) launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
-    VS_TRY(launch_burden(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.req, c.scratch));
-  } else if (c.req.kind == ReqKind::LD) {
-    if (r->d.A) launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
+  if (c.req.kind == ReqKind::Burden) VS_TRY(launch_burden(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.req, c.scratch));
+  if (c.req.kind == ReqKind::LD) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_ld(idx, r, c.ld_matrix, c.req));
-  } else VS_TRY(launch_matrix(idx, r, r->d_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+  } else if (c.req.kind == ReqKind::Matrix) VS_TRY(launch_matrix(idx, r, r->d_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
   HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
   r->pending = true;
   c.fill_launches = 1;
@@ -1887,9 +1876,9 @@ static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n,
   VS_TRY(shared_plan_batch(c));
   VS_TRY(shared_tables(c));
   VS_TRY(shared_rows(c));
-  if (!c.behind_perm) VS_TRY(c.lists ? shared_expand(c) : shared_counts(c));
+  if (!c.behind_perm) VS_TRY(c.lists ? shared_expand(c) : shared_columns(c));
   VS_TRY(shared_permute_out(c));
-  if (c.behind_perm) VS_TRY(shared_cells(c));
+  if (c.behind_perm) VS_TRY(shared_columns(c));
   return shared_finish(c);
 }
 

@@ -1,7 +1,7 @@
 // k_counts.hip.h -- allele counts per row of a type-6 plan (vs_query_allele_counts): the carrier expansion replaced by a count.
 // Part of kernels.hip.h (the kernel index is there).
 #pragma once
-#include "k_rows.hip.h"
+#include "k_carriers.hip.h"
 
 namespace vsamd {
 
@@ -43,7 +43,7 @@ __device__ __forceinline__ uint32_t sel_mask(uint32_t sel, bool groups) {
   uint32_t m = 0;
 #pragma unroll
   for (uint32_t j = 0; j < 8; ++j)
-    if ((sel >> j) & 1u) m |= 7u << (groups ? 3 * (j >> 1) + 16 * (j & 1) : 4 * j);
+    if ((sel >> j) & 1u) m |= 7u << gt_shift(j, groups);
   return m;
 }
 __device__ __forceinline__ bool in_set(const uint64_t* s_mask, uint32_t sid) { return (s_mask[sid >> 6] >> (sid & 63)) & 1ull; }
@@ -52,56 +52,31 @@ __device__ __forceinline__ unsigned long long widen(uint32_t v) { return (unsign
 
 // group k of a row (count rcnt, first carrier record gt0, list group / class src): its packed counts
 template <bool SUBSET>
-__device__ __forceinline__ GroupCounts group_counts(const DevImage& im, const uint64_t* s_mask, uint32_t k, uint32_t rcnt, uint64_t gt0, uint32_t src,
-                                                    bool groups, bool explicit_ids, const uint32_t* __restrict__ gt32) {
-  const uint32_t rem = rcnt - 8 * k;                                      // carriers of the row from this group on
-  const uint32_t nsel_all = rem < 8 ? rem : 8u;
+__device__ __forceinline__ GroupCounts group_counts(const DevImage& im, const CarrierForm& f, const uint64_t* s_mask, uint32_t k, uint32_t rcnt, uint64_t gt0,
+                                                    uint32_t src) {
+  const uint32_t nsel_all = group_nsel(rcnt, k);
   const uint64_t g = gt0 + 8ull * k;                                      // carrier record of the group's first entry
-  uint32_t w;
-  if (groups) w = im.gt_groups[g >> 3];                                   // (g is a multiple of 8 in class-row pools)
-  else if (!explicit_ids) w = gt32[g >> 3];
-  else {                                                                  // unpadded pool: a window of the nibble stream
-    uint2 nw;
-    __builtin_memcpy(&nw, gt32 + (g >> 3), 8);
-    w = __builtin_amdgcn_alignbit(nw.y, nw.x, ((uint32_t)g & 7u) * 4);
-  }
-  const uint32_t m0 = groups ? kGroupM0 : kNibM0;
-  if (!SUBSET) {
-    if (explicit_ids && nsel_all < 8) w &= (1u << (4 * nsel_all)) - 1u;   // the run ends inside the window
+  const uint32_t m0 = f.groups ? kGroupM0 : kNibM0;
+  if (!SUBSET) {   // no ids: the word alone
+    uint32_t w = group_word(im, f, g);
+    if (f.explicit_ids && nsel_all < 8) w &= (1u << (4 * nsel_all)) - 1u;   // the run ends inside the window
     return counts_of(w, m0, 0);
   }
   uint32_t id[8];
-  if (explicit_ids) {
-    uint4 ia, ib;
-    __builtin_memcpy(&ia, im.car_sid + g, 16);
-    __builtin_memcpy(&ib, im.car_sid + g + 4, 16);
-    id[0] = ia.x; id[1] = ia.y; id[2] = ia.z; id[3] = ia.w; id[4] = ib.x; id[5] = ib.y; id[6] = ib.z; id[7] = ib.w;
-  } else if (groups) {
-    const uint4 iw = reinterpret_cast<const uint4*>(im.cls_list16)[(uint64_t)src + k];
-    id[0] = iw.x & 0xFFFFu; id[1] = iw.x >> 16; id[2] = iw.y & 0xFFFFu; id[3] = iw.y >> 16;
-    id[4] = iw.z & 0xFFFFu; id[5] = iw.z >> 16; id[6] = iw.w & 0xFFFFu; id[7] = iw.w >> 16;
-  } else {
-    const uint4* lg = reinterpret_cast<const uint4*>(im.cls_list_ids) + 2 * ((uint64_t)src + k);
-    const uint4 ia = lg[0], ib = lg[1];
-    id[0] = ia.x; id[1] = ia.y; id[2] = ia.z; id[3] = ia.w; id[4] = ib.x; id[5] = ib.y; id[6] = ib.z; id[7] = ib.w;
-  }
+  const uint32_t w = group_load(im, f, g, src, k, id);
   uint32_t sel = 0;
 #pragma unroll
   for (uint32_t j = 0; j < 8; ++j)
     if (j < nsel_all && id[j] < im.num_samples && in_set(s_mask, id[j])) sel |= 1u << j;
-  return counts_of(w & sel_mask(sel, groups), m0, __popc(sel));
+  return counts_of(w & sel_mask(sel, f.groups), m0, __popc(sel));
 }
 
-// u_site: the site of every row of the table (k_share_rows2 for the shared rows, k_count_slow_sites for the private rows of the
-// regions under the duplicate rule, which may have dropped some: those rows' own counts say so).  S == NULL: the whole cohort.
+// u_site: the site of every row of the table (row_site).  S == NULL: the whole cohort.
 template <bool SUBSET>
 __global__ void __launch_bounds__(256) k_allele_counts(DevImage im, const VariantRow* __restrict__ rows, const uint32_t* __restrict__ u_site, uint64_t A,
                                                        uint64_t U, const uint64_t* __restrict__ S, uint32_t s_words, uint4* __restrict__ out) {
   extern __shared__ uint64_t s_mask[];   // SUBSET: S, s_words words, shared by the block's waves
-  __shared__ uint32_t s_off[4][kCountRows + 1];
-  __shared__ uint32_t s_src[4][kCountRows];
-  __shared__ uint32_t s_cnt[4][kCountRows];
-  __shared__ uint64_t s_gt0[4][kCountRows];
+  __shared__ FlatRows s_rows;
   __shared__ unsigned long long s_acc[4][2][kCountRows];
   if (SUBSET) {
     for (uint32_t i = threadIdx.x; i < s_words; i += blockDim.x) s_mask[i] = S[i];
@@ -112,34 +87,15 @@ __global__ void __launch_bounds__(256) k_allele_counts(DevImage im, const Varian
   if (r0 >= A) return;
   const uint64_t row = r0 + lane;
   const bool valid = row < A;
-  const bool groups = im.use_bv && im.wpc <= 63;
-  const bool explicit_ids = !im.use_bv;
+  const CarrierForm f = carrier_form(im);
   // ---- the row's parameters ----
-  uint32_t cnt = 0, cls = 0;
-  uint64_t gt0 = 0;
-  if (valid) {
-    const uint32_t g = u_site[row];
-    cnt = im.s_ncar[g];
-    if (row >= U && (rows[row].count_flags & kRowDropped)) cnt = 0;   // dropped by the duplicate rule: reports nothing
-    cls = im.s_class[g];
-    gt0 = im.s_gt0[g];
-  }
-  const bool dense = SUBSET && !explicit_ids && cnt > im.list_max;   // counted by the wave-per-row pass below
-  const uint32_t ng = dense ? 0u : (cnt + 7) / 8;
-  const uint32_t incl = wave_inclusive_scan(ng);
-  const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
-  uint32_t* off = s_off[wid];
-  off[lane] = incl - ng;
-  if (lane == 0) off[kCountRows] = total;
-  s_src[wid][lane] = cls;
-  s_cnt[wid][lane] = cnt;
-  s_gt0[wid][lane] = gt0;
+  RowSite rs{0, 0, 0};
+  if (valid) rs = row_site(im, rows, u_site, row, U);
+  const bool dense = SUBSET && is_dense(im, f, rs.cnt);   // counted by the wave-per-row pass below
   s_acc[wid][0][lane] = 0;
   s_acc[wid][1][lane] = 0;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  const uint32_t* __restrict__ gt32 = reinterpret_cast<const uint32_t*>(im.gt_nibbles);
+  const uint32_t total = flat_publish(s_rows, wid, lane, dense, rs);
+  const uint32_t* off = s_rows.off[wid];
   // ---- the flat pass: one group of 8 carriers per lane and step, kCountDepth steps' loads in flight at a time ----
   for (uint32_t e00 = 0; e00 < total; e00 += 64 * kCountDepth) {
     GroupCounts c[kCountDepth];
@@ -147,13 +103,9 @@ __global__ void __launch_bounds__(256) k_allele_counts(DevImage im, const Varian
 #pragma unroll
     for (uint32_t d = 0; d < kCountDepth; ++d) {
       const uint32_t e = e00 + 64 * d + lane;
-      uint32_t L = 0;
-#pragma unroll
-      for (uint32_t step = 32; step; step >>= 1)
-        if (off[L + step] <= e) L += step;
-      Ls[d] = L;
+      const uint32_t L = Ls[d] = flat_find<kCountRows>(off, e);
       c[d] = GroupCounts{0, 0};
-      if (e < total) c[d] = group_counts<SUBSET>(im, s_mask, e - off[L], s_cnt[wid][L], s_gt0[wid][L], s_src[wid][L], groups, explicit_ids, gt32);
+      if (e < total) c[d] = group_counts<SUBSET>(im, f, s_mask, e - off[L], s_rows.cnt[wid][L], s_rows.gt0[wid][L], s_rows.src[wid][L]);
     }
     // sum per row: segments of equal L are contiguous in a step
 #pragma unroll
@@ -177,30 +129,25 @@ __global__ void __launch_bounds__(256) k_allele_counts(DevImage im, const Varian
   while (dmask) {
     const int t = __builtin_ctzll(dmask);
     dmask &= dmask - 1;
-    const uint32_t c_t = __builtin_amdgcn_readlane(cls, t);
-    const uint64_t gt0_t = wave_bcast64(gt0, t);
-    const uint32_t wpc = im.wpc;
+    const uint32_t c_t = __builtin_amdgcn_readlane(rs.cls, t);
+    const uint64_t gt0_t = wave_bcast64(rs.gt0, t);
     uint32_t base = 0;                 // carriers in the row words before this chunk
     uint32_t a_car = 0, a_hom = 0, a_alt = 0, a_ph = 0;
-    for (uint32_t wb = 0; wb < wpc; wb += 64) {
+    for (uint32_t wb = 0; wb < im.wpc; wb += 64) {
       const uint32_t wi = wb + lane;
-      uint64_t rw = wi < wpc ? im.class_rows[(uint64_t)c_t * wpc + wi] : 0ull;
-      if (wi == 0) rw &= ~1ull;        // bit 0 of the first word is the reference, never a carrier
-      const uint32_t pc = __popcll(rw);
-      const uint32_t pre = wave_inclusive_scan(pc) - pc;
-      uint64_t m = wi < s_words ? rw & s_mask[wi] : 0ull;
+      const ClassChunk ch = class_chunk(im, c_t, wi);
+      uint64_t m = wi < s_words ? ch.rw & s_mask[wi] : 0ull;
       while (m) {
         const int b = __builtin_ctzll(m);
         m &= m - 1;
-        const uint64_t kc = gt0_t + base + pre + __popcll(rw & ((1ull << b) - 1ull));   // carrier record of sample wi * 64 + b
-        const uint32_t gt = groups ? (im.gt_groups[kc >> 3] >> (3 * ((kc & 7) >> 1) + 16 * (kc & 1))) & 7u
-                                   : (gt32[kc >> 3] >> (4 * (kc & 7))) & 7u;
+        const uint64_t kc = gt0_t + base + (ch.incl - ch.pc) + __popcll(ch.rw & ((1ull << b) - 1ull));   // carrier record of sample wi * 64 + b
+        const uint32_t gt = gt_of_record(gt_word(im, f, kc >> 3), kc, f.groups);
         a_car += 1;
         a_ph += gt & 1u;
         a_alt += ((gt >> 1) & 1u) + ((gt >> 2) & 1u);
         a_hom += (gt >> 1) & (gt >> 2) & 1u;
       }
-      base += __builtin_amdgcn_readlane(wave_inclusive_scan(pc), 63);
+      base += __builtin_amdgcn_readlane(ch.incl, 63);
     }
     a_car = wave_inclusive_scan(a_car); a_hom = wave_inclusive_scan(a_hom); a_alt = wave_inclusive_scan(a_alt); a_ph = wave_inclusive_scan(a_ph);
     if (lane == 63) {
@@ -208,12 +155,10 @@ __global__ void __launch_bounds__(256) k_allele_counts(DevImage im, const Varian
       s_acc[wid][1][t] = (unsigned long long)a_alt | ((unsigned long long)a_ph << 32);
     }
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  wave_lds_sync();
   if (!valid) return;
   const unsigned long long a0 = s_acc[wid][0][lane], a1 = s_acc[wid][1][lane];
-  const uint32_t carriers = SUBSET ? (uint32_t)a0 : cnt;
+  const uint32_t carriers = SUBSET ? (uint32_t)a0 : rs.cnt;
   out[row] = uint4{carriers, (uint32_t)a1, (uint32_t)(a0 >> 32), (uint32_t)(a1 >> 32)};
 }
 

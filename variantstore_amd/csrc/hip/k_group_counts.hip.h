@@ -9,11 +9,11 @@ namespace vsamd {
 // out[row * G + g] = {carriers, alt_alleles, hom_alt, phased} of table row `row` over the samples whose label is g: the record
 // k_allele_counts gives with group g as the subset, for all G groups in ONE pass over the row's carriers.
 //
-// One wave owns R consecutive rows (R from G, below).  Every lane gathers a row's site parameters as in k_allele_counts; then
+// One wave owns R consecutive rows (R from G, below).  Every lane gathers a row's site parameters (row_site; the pieces named here
+// are k_carriers.hip.h's); then
 //   flat pass   explicit-id rows and the rows of listed classes (at most list_max carriers): the FLAT list of 8-carrier groups of the
-//               wave's rows (DPP prefix sum over the group counts, a lane finds its row by bisection over the offsets in LDS), a lane
-//               per group: one genotype word (gt_groups | gt_nibbles | an unaligned window of the unpadded explicit-id pool, the run's
-//               end masked by the entry count) and the group's 8 ids (cls_list16 | cls_list_ids | car_sid)
+//               wave's rows (flat_publish, a lane finds its row with flat_find), a lane per group: one genotype word and the group's
+//               8 ids (group_load), the run's end cut by the entry count (group_nsel)
 //   dense pass  a denser class row: the WAVE per row, a lane per 64-bit word of the class row, 64 words a chunk.  A sample's id is its
 //               bit position, its carrier index the prefix popcount -- and a lane's carriers are consecutive, so the index is a counter.
 //               The chunk's genotype words (at most 4096 carriers = 512 words + 1 for the unaligned start) are staged in LDS ONCE with
@@ -56,10 +56,7 @@ __global__ void __launch_bounds__(256) k_group_counts(DevImage im, const Variant
                                                       uint64_t U, const uint64_t* __restrict__ labels, uint32_t label_words, uint32_t G,
                                                       uint4* __restrict__ out) {
   extern __shared__ uint64_t s_label64[];   // label_words words: a label byte per sample id, shared by the block's waves
-  __shared__ uint32_t s_off[4][64 + 1];
-  __shared__ uint32_t s_src[4][64];
-  __shared__ uint32_t s_cnt[4][64];
-  __shared__ uint64_t s_gt0[4][64];
+  __shared__ FlatRows s_rows;
   __shared__ unsigned long long s_acc[4][kGroupCells];
   __shared__ uint32_t s_stage[4][kGroupStageWords];
   for (uint32_t i = threadIdx.x; i < label_words; i += blockDim.x) s_label64[i] = labels[i];
@@ -72,105 +69,58 @@ __global__ void __launch_bounds__(256) k_group_counts(DevImage im, const Variant
   if (r0 >= A) return;
   const uint64_t row = r0 + lane;
   const bool valid = lane < R && row < A;
-  const bool groups = im.use_bv && im.wpc <= 63;
-  const bool explicit_ids = !im.use_bv;
+  const CarrierForm f = carrier_form(im);
   const uint32_t ns = im.num_samples;
   // ---- the row's parameters ----
-  uint32_t cnt = 0, cls = 0;
-  uint64_t gt0 = 0;
-  if (valid) {
-    const uint32_t g = u_site[row];
-    cnt = im.s_ncar[g];
-    if (row >= U && (rows[row].count_flags & kRowDropped)) cnt = 0;   // dropped by the duplicate rule: counts 0 in every group
-    cls = im.s_class[g];
-    gt0 = im.s_gt0[g];
-  }
-  const bool dense = !explicit_ids && cnt > im.list_max;   // counted by the wave-per-row pass below
-  const uint32_t ng = dense ? 0u : (cnt + 7) / 8;
-  const uint32_t incl = wave_inclusive_scan(ng);
-  const uint32_t total = __builtin_amdgcn_readlane(incl, 63);
-  uint32_t* off = s_off[wid];
+  RowSite rs{0, 0, 0};
+  if (valid) rs = row_site(im, rows, u_site, row, U);   // (a dropped row counts 0 in every group)
+  const bool dense = is_dense(im, f, rs.cnt);           // counted by the wave-per-row pass below
   unsigned long long* acc = s_acc[wid];
-  off[lane] = incl - ng;                // (lanes beyond R: no groups, their offsets equal the total)
-  if (lane == 0) off[64] = total;
-  s_src[wid][lane] = cls;
-  s_cnt[wid][lane] = cnt;
-  s_gt0[wid][lane] = gt0;
 #pragma unroll
   for (uint32_t i = 0; i < kGroupCells / 64; ++i) acc[lane + 64 * i] = 0;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  const uint32_t* __restrict__ gt32 = reinterpret_cast<const uint32_t*>(im.gt_nibbles);
+  const uint32_t total = flat_publish(s_rows, wid, lane, dense, rs);   // (lanes beyond R: no groups, their offsets equal the total)
+  const uint32_t* off = s_rows.off[wid];
   // ---- the flat pass: one group of 8 carriers per lane and step ----
   for (uint32_t e0 = 0; e0 < total; e0 += 64) {
     const uint32_t e = e0 + lane;
     if (e >= total) continue;
-    uint32_t L = 0;
-#pragma unroll
-    for (uint32_t step = 32; step; step >>= 1)
-      if (off[L + step] <= e) L += step;
-    const uint32_t k = e - off[L], rcnt = s_cnt[wid][L], src = s_src[wid][L];
-    const uint32_t rem = rcnt - 8 * k, nsel = rem < 8 ? rem : 8u;    // entries of the group that belong to the row
-    const uint64_t g = s_gt0[wid][L] + 8ull * k;                      // carrier record of the group's first entry
-    uint32_t w, id[8];
-    if (explicit_ids) {                                               // unpadded pool: a window of the nibble stream, ids beside it
-      uint2 nw;
-      __builtin_memcpy(&nw, gt32 + (g >> 3), 8);
-      w = __builtin_amdgcn_alignbit(nw.y, nw.x, ((uint32_t)g & 7u) * 4);
-      uint4 ia, ib;
-      __builtin_memcpy(&ia, im.car_sid + g, 16);
-      __builtin_memcpy(&ib, im.car_sid + g + 4, 16);
-      id[0] = ia.x; id[1] = ia.y; id[2] = ia.z; id[3] = ia.w; id[4] = ib.x; id[5] = ib.y; id[6] = ib.z; id[7] = ib.w;
-    } else if (groups) {                                              // (g is a multiple of 8 in class-row pools)
-      w = im.gt_groups[g >> 3];
-      const uint4 iw = reinterpret_cast<const uint4*>(im.cls_list16)[(uint64_t)src + k];
-      id[0] = iw.x & 0xFFFFu; id[1] = iw.x >> 16; id[2] = iw.y & 0xFFFFu; id[3] = iw.y >> 16;
-      id[4] = iw.z & 0xFFFFu; id[5] = iw.z >> 16; id[6] = iw.w & 0xFFFFu; id[7] = iw.w >> 16;
-    } else {
-      w = gt32[g >> 3];
-      const uint4* lg = reinterpret_cast<const uint4*>(im.cls_list_ids) + 2 * ((uint64_t)src + k);
-      const uint4 ia = lg[0], ib = lg[1];
-      id[0] = ia.x; id[1] = ia.y; id[2] = ia.z; id[3] = ia.w; id[4] = ib.x; id[5] = ib.y; id[6] = ib.z; id[7] = ib.w;
-    }
+    const uint32_t L = flat_find<64>(off, e);
+    const uint32_t k = e - off[L], nsel = group_nsel(s_rows.cnt[wid][L], k);
+    const uint64_t g = s_rows.gt0[wid][L] + 8ull * k;                 // carrier record of the group's first entry
+    uint32_t id[8];
+    const uint32_t w = group_load(im, f, g, s_rows.src[wid][L], k, id);
     unsigned long long* racc = acc + ((size_t)L << (gshift + cshift)) + mycopy;
 #pragma unroll
     for (uint32_t j = 0; j < 8; ++j) {
       if (j >= nsel || id[j] >= ns) continue;                         // (beyond the run's end: the next run's records, or padding)
       const uint32_t lab = s_label[id[j]];
       if (lab >= G) continue;
-      const uint32_t gt = (w >> (groups ? 3 * (j >> 1) + 16 * (j & 1) : 4 * j)) & 7u;
-      atomicAdd(racc + ((size_t)lab << cshift), group_packed(gt));
+      atomicAdd(racc + ((size_t)lab << cshift), group_packed(gt_of_slot(w, j, f.groups)));
     }
   }
   // ---- denser classes: the wave per row, a lane per word of the class row, the chunk's genotype words staged in LDS ----
   uint64_t dmask = __ballot(dense);
   uint32_t* stage = s_stage[wid];
-  const uint32_t wpc = im.wpc;
   while (dmask) {
     const int t = __builtin_ctzll(dmask);
     dmask &= dmask - 1;
-    const uint32_t c_t = __builtin_amdgcn_readlane(cls, t);
-    const uint64_t gt0_t = wave_bcast64(gt0, t);
+    const uint32_t c_t = __builtin_amdgcn_readlane(rs.cls, t);
+    const uint64_t gt0_t = wave_bcast64(rs.gt0, t);
     unsigned long long* racc = acc + ((size_t)t << (gshift + cshift)) + mycopy;
     uint64_t first = gt0_t;             // carrier record of the chunk's first carrier
-    for (uint32_t wb = 0; wb < wpc; wb += 64) {
+    for (uint32_t wb = 0; wb < im.wpc; wb += 64) {
       const uint32_t wi = wb + lane;
-      uint64_t rw = wi < wpc ? im.class_rows[(uint64_t)c_t * wpc + wi] : 0ull;
-      if (wi == 0) rw &= ~1ull;         // bit 0 of the first word is the reference, never a carrier
-      const uint32_t pc = __popcll(rw);
-      const uint32_t pin = wave_inclusive_scan(pc);
-      const uint32_t chunk = __builtin_amdgcn_readlane(pin, 63);   // <= 4096
+      const ClassChunk ch = class_chunk(im, c_t, wi);
+      uint64_t rw = ch.rw;
+      const uint32_t chunk = __builtin_amdgcn_readlane(ch.incl, 63);   // <= 4096
       // stage words [first >> 3, (first + chunk + 7) >> 3): at most 513
       const uint64_t w0 = first >> 3;
       const uint32_t nw = (uint32_t)(((first + chunk + 7) >> 3) - w0);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // (the previous chunk's reads are over before it is overwritten)
       __builtin_amdgcn_wave_barrier();
-      for (uint32_t i = lane; i < nw && i < kGroupStageWords; i += 64) stage[i] = groups ? im.gt_groups[w0 + i] : gt32[w0 + i];
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      uint32_t kc = (uint32_t)(first - (w0 << 3)) + (pin - pc);    // the lane's first carrier, relative to the staged words
+      for (uint32_t i = lane; i < nw && i < kGroupStageWords; i += 64) stage[i] = gt_word(im, f, w0 + i);
+      wave_lds_sync();
+      uint32_t kc = (uint32_t)(first - (w0 << 3)) + (ch.incl - ch.pc);   // the lane's first carrier, relative to the staged words
       while (rw) {                                                 // four carriers a round: their label loads are in flight together
         uint32_t lab[4];
 #pragma unroll
@@ -184,18 +134,14 @@ __global__ void __launch_bounds__(256) k_group_counts(DevImage im, const Variant
         for (uint32_t u = 0; u < 4; ++u) {
           if (lab[u] >= G) continue;
           const uint32_t k = kc + u;
-          const uint32_t sw = stage[k >> 3];
-          const uint32_t gt = (sw >> (groups ? 3 * ((k & 7) >> 1) + 16 * (k & 1) : 4 * (k & 7))) & 7u;
-          atomicAdd(racc + ((size_t)lab[u] << cshift), group_packed(gt));
+          atomicAdd(racc + ((size_t)lab[u] << cshift), group_packed(gt_of_record(stage[k >> 3], k, f.groups)));
         }
         kc += 4;
       }
       first += chunk;
     }
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  wave_lds_sync();
   // ---- the wave's R x G records, contiguous in `out`: a 16-byte store per record, consecutive lanes consecutive records ----
   const uint64_t nrow = A - r0 < R ? A - r0 : R;
   const uint32_t ncell = (uint32_t)nrow * G;

@@ -16,13 +16,13 @@ namespace vsamd {
 // is no memset of the matrix and no atomic on it.  The nonzero cells are counted from the same 16-byte words on their way out
 // (bit 3 of a byte says it is a carrier) and added to the batch's total once per workgroup.
 //
-// The rows take their parameters as k_sample_burden's do (u_site -> s_ncar / s_class / s_gt0, a dropped private row has no
-// carriers) and are decoded the same ways, here by the whole workgroup: the listed rows and the rows of explicit-id cohorts as
-// ONE flat list of 8-carrier groups over the block's rows (a prefix sum over the group counts, a thread finds its row by bisection),
-// then the classes denser than list_max a row per wave, a lane per word of the class row.  There a lane's carriers are
-// consecutive genotype records: the word of eight is loaded once and kept while the record index stays inside it.
+// The rows take their parameters and are decoded over k_carriers.hip.h (row_site, group_load, class_chunk), here by
+// the whole workgroup: the listed rows and the rows of explicit-id cohorts as ONE flat list of 8-carrier groups over the block's
+// rows (a prefix sum over the group counts, a thread finds its row by bisection), then the classes denser than list_max a row
+// per wave, a lane per word of the class row.  There a lane's carriers are consecutive genotype records: the word of eight is
+// loaded once and kept while the record index stays inside it.
 //
-// The column of sample id: id - 1 without a subset; with one, the rank of id in S (per-word prefix popcounts behind the mask).
+// The column of a sample id: column_of; with a subset the ranks sit in LDS behind the mask.
 // All LDS is dynamic and carved on 16-byte bounds: tile | SUBSET: mask, ranks | the block's row parameters.
 constexpr uint32_t kMatrixTileCols = 4096;         // default column tile: 16 rows of it are the 64 KiB below
 constexpr uint32_t kMatrixTileBytes = 64 << 10;    // the tile in LDS: with the row parameters a second workgroup fits a CU's 160 KiB
@@ -44,54 +44,26 @@ struct MatrixArgs {
   unsigned long long* total;    // nonzero cells of the matrix
 };
 
-struct MatrixTile { uint8_t* cell; const uint64_t* mask; const uint32_t* rank; uint32_t tile0, tn, tb, num_samples; };
+struct MatrixTile : ColumnTile { uint8_t* cell; uint32_t tb; };   // tb: bytes of a tile row
 
 // one carrier (sample id, 3 genotype bits) of block row r into its byte, if the tile holds its column
 template <bool SUBSET>
 __device__ __forceinline__ void matrix_put(const MatrixTile& t, uint32_t r, uint32_t id, uint32_t gt) {
-  if (id - 1u >= t.num_samples - 1u) return;   // "ref" (id 0) and the padding of a list
-  uint32_t col = id - 1u;
-  if (SUBSET) {
-    const uint64_t mw = t.mask[id >> 6], bit = 1ull << (id & 63);
-    if (!(mw & bit)) return;
-    col = t.rank[id >> 6] + __popcll(mw & (bit - 1ull));
-  }
-  col -= t.tile0;
-  if (col >= t.tn) return;
-  t.cell[r * t.tb + col] = (uint8_t)(0x08u | gt);
+  uint32_t col;
+  if (column_of<SUBSET>(t, id, col)) t.cell[r * t.tb + col] = (uint8_t)(0x08u | gt);
 }
 
 // group k of block row r (count rcnt, first carrier record gt0, list group src): its up to 8 carriers
 template <bool SUBSET>
-__device__ __forceinline__ void matrix_group(const DevImage& im, const MatrixTile& t, uint32_t r, uint32_t k, uint32_t rcnt, uint64_t gt0, uint32_t src,
-                                             bool groups, bool explicit_ids, const uint32_t* __restrict__ gt32) {
-  const uint32_t rem = rcnt - 8 * k;
-  const uint32_t nsel = rem < 8 ? rem : 8u;
+__device__ __forceinline__ void matrix_group(const DevImage& im, const CarrierForm& f, const MatrixTile& t, uint32_t r, uint32_t k, uint32_t rcnt, uint64_t gt0,
+                                             uint32_t src) {
+  const uint32_t nsel = group_nsel(rcnt, k);
   const uint64_t g = gt0 + 8ull * k;
-  uint32_t w;
   uint32_t id[8];
-  if (explicit_ids) {   // unpadded pool: a window of the nibble stream, entries beyond the run belong to the next one
-    uint2 nw;
-    __builtin_memcpy(&nw, gt32 + (g >> 3), 8);
-    w = __builtin_amdgcn_alignbit(nw.y, nw.x, ((uint32_t)g & 7u) * 4);
-    uint4 ia, ib;
-    __builtin_memcpy(&ia, im.car_sid + g, 16);
-    __builtin_memcpy(&ib, im.car_sid + g + 4, 16);
-    id[0] = ia.x; id[1] = ia.y; id[2] = ia.z; id[3] = ia.w; id[4] = ib.x; id[5] = ib.y; id[6] = ib.z; id[7] = ib.w;
-  } else if (groups) {
-    w = im.gt_groups[g >> 3];
-    const uint4 iw = reinterpret_cast<const uint4*>(im.cls_list16)[(uint64_t)src + k];
-    id[0] = iw.x & 0xFFFFu; id[1] = iw.x >> 16; id[2] = iw.y & 0xFFFFu; id[3] = iw.y >> 16;
-    id[4] = iw.z & 0xFFFFu; id[5] = iw.z >> 16; id[6] = iw.w & 0xFFFFu; id[7] = iw.w >> 16;
-  } else {
-    w = gt32[g >> 3];
-    const uint4* lg = reinterpret_cast<const uint4*>(im.cls_list_ids) + 2 * ((uint64_t)src + k);
-    const uint4 ia = lg[0], ib = lg[1];
-    id[0] = ia.x; id[1] = ia.y; id[2] = ia.z; id[3] = ia.w; id[4] = ib.x; id[5] = ib.y; id[6] = ib.z; id[7] = ib.w;
-  }
+  const uint32_t w = group_load(im, f, g, src, k, id);
 #pragma unroll
   for (uint32_t j = 0; j < 8; ++j)
-    if (j < nsel) matrix_put<SUBSET>(t, r, id[j], (w >> (groups ? 3 * (j >> 1) + 16 * (j & 1) : 4 * j)) & 7u);
+    if (j < nsel) matrix_put<SUBSET>(t, r, id[j], gt_of_slot(w, j, f.groups));
 }
 
 template <bool SUBSET>
@@ -134,27 +106,17 @@ __global__ void __launch_bounds__(256) k_genotype_matrix(DevImage im, MatrixArgs
       s_rank[i] = a.S_rank[i];
     }
   if (threadIdx.x == 0) { *s_nd = 0; *s_sum = 0; }
-  const bool groups = im.use_bv && im.wpc <= 63;
-  const bool explicit_ids = !im.use_bv;
-  const uint32_t* __restrict__ gt32 = reinterpret_cast<const uint32_t*>(im.gt_nibbles);
+  const CarrierForm f = carrier_form(im);
   // ---- the parameters of the block's rows: a row per thread ----
-  uint32_t cnt = 0, cls = 0;
-  uint64_t gt0 = 0;
-  if (threadIdx.x < nr) {
-    const uint64_t row = row0 + threadIdx.x;
-    const uint32_t g = a.u_site[row];
-    cnt = im.s_ncar[g];
-    if (row >= a.U && (a.rows[row].count_flags & kRowDropped)) cnt = 0;   // dropped by the duplicate rule: reports nothing
-    cls = im.s_class[g];
-    gt0 = im.s_gt0[g];
-  }
-  const bool dense = !explicit_ids && cnt > im.list_max;
-  const uint32_t ng = dense ? 0u : (cnt + 7) / 8;
+  RowSite rs{0, 0, 0};
+  if (threadIdx.x < nr) rs = row_site(im, a.rows, a.u_site, row0 + threadIdx.x, a.U);
+  const bool dense = is_dense(im, f, rs.cnt);
+  const uint32_t ng = flat_groups(dense, rs.cnt);
   const uint32_t incl = wave_inclusive_scan(ng);
   if (lane == 63) s_wsum[wid] = incl;
-  s_src[threadIdx.x] = cls;
-  s_cnt[threadIdx.x] = cnt;
-  s_gt0[threadIdx.x] = gt0;
+  s_src[threadIdx.x] = rs.cls;
+  s_cnt[threadIdx.x] = rs.cnt;
+  s_gt0[threadIdx.x] = rs.gt0;
   __syncthreads();   // (the tile's zeros, the mask, the waves' sums and s_nd = 0 are in place)
   uint32_t before = 0, total = 0;
 #pragma unroll
@@ -169,11 +131,8 @@ __global__ void __launch_bounds__(256) k_genotype_matrix(DevImage im, MatrixArgs
   __syncthreads();
   // ---- the flat pass: one group of 8 carriers per thread and step ----
   for (uint32_t e = threadIdx.x; e < total; e += 256) {
-    uint32_t L = 0;
-#pragma unroll
-    for (uint32_t step = kMatrixMaxRows / 2; step; step >>= 1)
-      if (s_off[L + step] <= e) L += step;
-    matrix_group<SUBSET>(im, t, L, e - s_off[L], s_cnt[L], s_gt0[L], s_src[L], groups, explicit_ids, gt32);
+    const uint32_t L = flat_find<kMatrixMaxRows>(s_off, e);
+    matrix_group<SUBSET>(im, f, t, L, e - s_off[L], s_cnt[L], s_gt0[L], s_src[L]);
   }
   // ---- denser classes: a row per wave, a lane per word of the class row ----
   const uint32_t nd = *s_nd;
@@ -181,18 +140,14 @@ __global__ void __launch_bounds__(256) k_genotype_matrix(DevImage im, MatrixArgs
     const uint32_t r = s_dense[k];
     const uint32_t c_r = s_src[r];
     const uint64_t gt0_r = s_gt0[r];
-    const uint32_t wpc = im.wpc;
     uint32_t seen = 0;   // carriers in the row words before this round of 64
-    for (uint32_t wb = 0; wb < wpc; wb += 64) {
+    for (uint32_t wb = 0; wb < im.wpc; wb += 64) {
       const uint32_t wi = wb + lane;
-      uint64_t rw = wi < wpc ? im.class_rows[(uint64_t)c_r * wpc + wi] : 0ull;
-      if (wi == 0) rw &= ~1ull;   // bit 0 of the first word is the reference, never a carrier
-      const uint32_t pc = __popcll(rw);
-      const uint32_t inc = wave_inclusive_scan(pc);
-      uint64_t m = rw;
+      const ClassChunk ch = class_chunk(im, c_r, wi);
+      uint64_t m = ch.rw;
       if (SUBSET) {   // the word's columns are rank .. rank + popc(mask): none of them in this tile -> nothing to scatter
         const uint64_t mw = wi < a.s_words ? s_mask[wi] : 0ull;
-        m = rw & mw;
+        m = ch.rw & mw;
         if (m) {
           const uint32_t c0 = s_rank[wi];
           if (c0 >= t.tile0 + t.tn || c0 + __popcll(mw) <= t.tile0) m = 0;
@@ -203,15 +158,14 @@ __global__ void __launch_bounds__(256) k_genotype_matrix(DevImage im, MatrixArgs
       while (m) {
         const int b = __builtin_ctzll(m);
         m &= m - 1;
-        const uint64_t kc = gt0_r + seen + (inc - pc) + __popcll(rw & ((1ull << b) - 1ull));   // carrier record of sample wi * 64 + b
+        const uint64_t kc = gt0_r + seen + (ch.incl - ch.pc) + __popcll(ch.rw & ((1ull << b) - 1ull));   // carrier record of sample wi * 64 + b
         if ((kc >> 3) != have) {
           have = kc >> 3;
-          w = groups ? im.gt_groups[have] : gt32[have];
+          w = gt_word(im, f, have);
         }
-        const uint32_t gt = groups ? (w >> (3 * ((kc & 7) >> 1) + 16 * (kc & 1))) & 7u : (w >> (4 * (kc & 7))) & 7u;
-        matrix_put<SUBSET>(t, r, wi * 64 + (uint32_t)b, gt);
+        matrix_put<SUBSET>(t, r, wi * 64 + (uint32_t)b, gt_of_record(w, kc, f.groups));
       }
-      seen += __builtin_amdgcn_readlane(inc, 63);
+      seen += __builtin_amdgcn_readlane(ch.incl, 63);
     }
   }
   __syncthreads();

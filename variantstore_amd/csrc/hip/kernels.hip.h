@@ -51,6 +51,9 @@
 //  k_pack_seq_regions    flags per region): site range + counts, or pieces + bytes of a sequence; k_bounds_from_records: the
 //                       receiving side (vs_query_expand_site_ranges)
 // k_find                Index::find batched
+// (k_carriers.hip.h)    no kernel: how the four column kernels below read the carriers of a table row -- the three storage forms of a
+//                       group of 8 carriers, a row's site parameters, the flat list of groups, the head of a dense class-row chunk,
+//                       sample id -> column; next to the expansion kernels the one place that knows how a carrier is stored
 // k_allele_counts       allele counts per row of a type-6 plan over a sample subset (vs_query_allele_counts: no reference
 //  k_count_slow_sites    counterpart; what a caller of type 6 would count on the host from the carrier lists)
 // k_group_counts        the same counts per sample GROUP in one pass over a row's carriers: a label byte per sample in LDS, one packed
@@ -73,6 +76,7 @@
 #include "k_points.hip.h"
 #include "k_sample_coords.hip.h"
 #include "k_digest.hip.h"
+#include "k_carriers.hip.h"
 #include "k_counts.hip.h"
 #include "k_group_counts.hip.h"
 #include "k_burden.hip.h"
