@@ -232,6 +232,56 @@ int vs_result_get_group_counts(vs_result* r, uint64_t* n_rows, uint32_t* n_group
 /* The records as they lie in HBM: n_rows x n_groups records of 16 bytes, row-major, valid until vs_result_free.  The engine has
  * synchronised its stream when this returns: the caller needs no event. */
 int vs_result_group_counts_device(vs_result* r, uint64_t* n_rows, uint32_t* n_groups, const void** dev_counts);
+/* Association scan: every row of the type-6 variant table scored against K phenotypes in one pass over its carriers -- "for the
+ * variants in these regions, how does each one go with this trait?" (no reference counterpart: what a caller would get from
+ * vs_query_genotype_matrix, a conversion of the cells to dosages and a matrix product, without the matrix).
+ * The subset S and its n_cols = n columns are the genotype matrix's: the distinct sample ids ascending; sample_ids == NULL: the whole
+ * cohort, ids 1 .. num_samples - 1, and n_ids must be num_samples - 1.  traits[i * n_traits + k] (HOST float32, n_ids x n_traits) is
+ * trait k of sample_ids[i], in whatever order the ids come (NULL ids: of id i + 1); the engine permutes the rows into column order.
+ * d_i(s) = popc(gt & 6) is the dosage of sample s on table row i: 0 for a non-carrier and on a row dropped by the duplicate rule.
+ * scores[i * n_traits + k], a float64, is
+ *   VS_ASSOC_DOT   Sxy = sum over s in S of d_i(s) * y_k(s), accumulated in float64 (every product is exact);
+ *   VS_ASSOC_CHI2  the score test of a linear regression of y_k on the dosage without covariates (for a 0/1 trait the
+ *                  Cochran-Armitage trend test): with the row's own count record over S, Sx = alt_alleles, Sxx = alt_alleles +
+ *                  2 hom_alt, vx = n Sxx - Sx^2 in 64-bit integers, cov = n Sxy - Sx Sy and vy = n Syy - Sy^2 in double,
+ *                  chi2 = ((double)n * cov) * cov / ((double)vx * vy), each operation rounded on its own in this order; 0.0 when
+ *                  vx == 0 or vy <= 0 (a monomorphic or dropped row, a constant trait, n = 1).
+ * The order of a row's additions is fixed by the table's layout, not by the run: the same call gives the same bytes every time,
+ * whichever form the phenotype table takes on the device (option "assoc_lds_max_kib").  The result also holds the count record of
+ * every table row over S (vs_allele_counts, as an LD result does), per trait Sy and Syy as doubles -- summed on the host left to right
+ * in column order from the float32 values --, and the columns' ids.  A batch whose table is empty gives 0 rows and is no error.
+ * `regions` as for vs_query_allele_counts (host or device memory, n >= 1).  Checked on the host before the handle's device is asked
+ * for (a handle opened without a device reports them first and VS_ERR_NO_DEVICE otherwise): n == 0, NULL traits, n_traits == 0 or
+ * n_traits > VS_TRAITS_MAX, an unknown stat, n_ids == 0, NULL sample_ids with n_ids != num_samples - 1 -> VS_ERR_ARG; id 0 ("ref") or
+ * an id >= num_samples -> VS_ERR_UNKNOWN_SAMPLE; a sample listed twice -> VS_ERR_ARG (the message names the id); a value that is not
+ * finite -> VS_ERR_ARG (the message names the sample id and the trait: pass the subset of samples that have a value); a trait name
+ * (trait_names: NULL, or n_traits strings that are copied into the result) with a tab or a newline -> VS_ERR_ARG.  The whole cohort
+ * has no size limit; a subset's bit mask lies in the counting kernel's LDS as for vs_query_allele_counts (more than 393216 sample
+ * ids: VS_ERR_UNSUPPORTED).
+ * rows x n_traits x 8 + rows x 16 bytes are held to option "matrix_max_mib" (default 32 GiB): a larger request is refused with
+ * VS_ERR_ARG once the plan has given the rows and before anything is allocated; the message names rows, traits and bytes.
+ * Every batch size takes the batch pipeline; an association batch is never speculative and leaves the handle's type-6 state as it
+ * was.  The result holds the type-6 per-region arrays and variant table, no carrier arena: vs_result_get_raw / vs_result_get_view
+ * with with_carriers = 0, vs_result_layout (arena and lists 0), vs_result_fill_ms (the count kernel and the scan), vs_result_totals
+ * (n_carriers = the sum of `carriers` over the rows every region reports) and vs_result_format_region
+ * ("Pos\tRef\tAlt\tCarriers\tAC\tHomAlt\tPhased", then a column per trait under its name, or its decimal index without names; one
+ * line per reported, non-dropped row, the cells printed with %.17g) work; with_carriers = 1, vs_result_digest, vs_result_pack_headers /
+ * _pack_regions and vs_comm_allgather_regions* fail with VS_ERR_UNSUPPORTED, the other kinds' getters with VS_ERR_ARG. */
+#define VS_TRAITS_MAX 8u
+#define VS_ASSOC_DOT 0u
+#define VS_ASSOC_CHI2 1u
+int vs_query_assoc_scan(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids,
+                        const float* traits, uint32_t n_traits, uint32_t stat, const char* const* trait_names, vs_result** out);
+/* The cells of an association-scan result copied into page-locked memory owned by the result: scores[i * n_traits + k] of table row
+ * i (vs_result_raw.rows[i]; region q's rows are row_begin[q] .. + row_count[q]); counts[i] its record over S; trait_sum / trait_sumsq
+ * n_traits doubles each; col_ids the n_cols column ids (any but `scores` may be NULL).  VS_ERR_ARG on any other result. */
+int vs_result_get_assoc_scan(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* n_traits, uint32_t* stat,
+                             const uint32_t** col_ids, const double** trait_sum, const double** trait_sumsq,
+                             const vs_allele_counts** counts, const double** scores);
+/* The cells as they lie in HBM: n_rows x n_traits float64, row-major, and the n_rows count records of 16 bytes (dev_counts may be
+ * NULL), valid until vs_result_free.  The engine has synchronised its stream when this returns: the caller needs no event. */
+int vs_result_assoc_scan_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* n_traits, uint32_t* stat,
+                                const void** dev_counts, const void** dev_scores);
 /* Per-sample burden over regions: the counts above along the other axis -- a regions x samples matrix, the input of gene-burden
  * and collapsing tests and of per-sample QC counts (no reference counterpart: what a caller of type 6 would reduce on the host
  * from every carrier list).  Let R(q) be the rows type 6 reports for region q (same order, duplicate rule and region flags; a
@@ -553,8 +603,11 @@ void vs_comm_destroy(vs_comm* c);
  *                     the capacity of its recording walk (tests of that path)
  *   "burden_chunk"    rows of a region one workgroup of the burden kernel walks (vs_query_sample_burden): a region with more is
  *                     split between several, which add to its cells with atomics.  0 (default): 4096; else 64..65536
- *   "matrix_max_mib"  the largest genotype matrix (vs_query_genotype_matrix; also an LD batch's matrix + band and the records of
- *                     vs_query_group_counts), in MiB, a batch may ask for.  0 (default): 32 GiB
+ *   "matrix_max_mib"  the largest genotype matrix (vs_query_genotype_matrix; also an LD batch's matrix + band, the records of
+ *                     vs_query_group_counts and the cells + records of vs_query_assoc_scan), in MiB, a batch may ask for.  0 (default): 32 GiB
+ *   "assoc_lds_max_kib" the largest phenotype table (columns x traits rounded up to 1, 2, 4 or 8, x 4 bytes) the kernel of
+ *                     vs_query_assoc_scan stages in LDS, in KiB; a larger one is read through global memory.  0 (default): 32; else
+ *                     1..128 (small cohorts reach the global form with 1).  The scores are the same bytes in either form
  *   "matrix_tile_cols" columns of a workgroup's tile of the matrix kernel: 0 (default): 4096; else a multiple of 16 in 16..65536
  *                     (small cohorts reach tile boundaries with it)
  * Tuning builds (VS_BUILD_TUNING=1 python -m variantstore_amd.build --force) add "lat_debug", "fill_fused", "fill_chunk",

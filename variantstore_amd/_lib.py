@@ -103,6 +103,14 @@ SYMBOLS = {
     "vs_result_get_group_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)),
                                              C.POINTER(C.POINTER(AlleleCounts))]),
     "vs_result_group_counts_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]),
+    "vs_query_assoc_scan": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_float), C.c_uint32,
+                                      C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(_P)]),
+    "vs_result_get_assoc_scan": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_double)),
+                                           C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(AlleleCounts)),
+                                           C.POINTER(C.POINTER(C.c_double))]),
+    "vs_result_assoc_scan_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "vs_query_sample_burden": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32,
                                          C.POINTER(_P)]),
     "vs_result_get_sample_burden": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint32)),

@@ -279,6 +279,62 @@ class QueryResult:
         _check(self._lib.vs_result_group_counts_device(self._h, C.byref(n), C.byref(g), C.byref(p)), "vs_result_group_counts_device")
         return int(p.value or 0), int(n.value), int(g.value)
 
+    ASSOC_STATS = {"dot": 0, "chi2": 1}   # VS_ASSOC_DOT, VS_ASSOC_CHI2
+
+    def assoc_scan(self):
+        """An association-scan result (VariantStore.assoc_scan) as numpy arrays: `scores` ((A, K) float64: scores[i, k] is table row
+        i against trait k -- the sum of dosage x value under stat "dot", the score test under "chi2"), `counts` (structured as for
+        allele_counts: the count record of every table row over the query's samples), `col_ids` (uint32[n], the sample ids the
+        sums run over, ascending), `trait_sum` and `trait_sumsq` (float64[K]: Sy and Syy over those samples), `trait_names`
+        (list of K strings), `stat`, the table's `rows` and per region `row_begin`, `row_count` and `flags` -- region q's rows are
+        rows[row_begin[q] : row_begin[q] + row_count[q]].  Copies, valid after the result is closed."""
+        a, c = C.c_uint64(), C.c_uint64()
+        k, st = C.c_uint32(), C.c_uint32()
+        cols = C.POINTER(C.c_uint32)()
+        sy, syy, sc = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+        cnt = C.POINTER(_lib.AlleleCounts)()
+        _check(self._lib.vs_result_get_assoc_scan(self._h, C.byref(a), C.byref(c), C.byref(k), C.byref(st), C.byref(cols), C.byref(sy),
+                                                  C.byref(syy), C.byref(cnt), C.byref(sc)), "vs_result_get_assoc_scan")
+        na, nc, nk = int(a.value), int(c.value), int(k.value)
+        if na:
+            scores = np.ctypeslib.as_array(sc, shape=(na * nk,)).reshape(na, nk).copy()
+            counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint8)), shape=(na * 16,)).view(self.COUNT_DTYPE).copy()
+        else:
+            scores, counts = np.zeros((0, nk), np.float64), np.zeros(0, self.COUNT_DTYPE)
+        raw = self.raw(with_carriers=False)
+        names = self.region_text(0).split("\n")[0].split("\t")[7:]   # (the result's own: the header of every region's text)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "flags": raw["region_flags"].copy(), "scores": scores, "counts": counts,
+                "col_ids": np.ctypeslib.as_array(cols, shape=(nc,)).copy(), "trait_sum": np.ctypeslib.as_array(sy, shape=(nk,)).copy(),
+                "trait_sumsq": np.ctypeslib.as_array(syy, shape=(nk,)).copy(), "trait_names": list(names),
+                "stat": "chi2" if st.value == self.ASSOC_STATS["chi2"] else "dot"}
+
+    def region_assoc(self, q):
+        """The rows region q of an association-scan result reports (dropped ones left out): a list of dicts with pos, ref, alt,
+        carriers, alt_alleles, hom_alt, phased and `scores`, which maps each trait's name to its float."""
+        lines = self.region_text(q).split("\n")
+        names = lines[0].split("\t")[7:]
+        out = []
+        for line in lines[1:]:
+            if not line:
+                continue
+            f = line.split("\t")
+            out.append({"pos": int(f[0]), "ref": f[1], "alt": f[2], "carriers": int(f[3]), "alt_alleles": int(f[4]), "hom_alt": int(f[5]),
+                        "phased": int(f[6]), "scores": {n: float(v) for n, v in zip(names, f[7:])}})
+        return out
+
+    def assoc_scan_device(self):
+        """(scores address, counts address, n_rows, n_cols, n_traits, stat) of an association-scan result as it lies in this GPU's
+        memory: n_rows x n_traits float64 cells, row-major, and n_rows count records of four uint32, complete when this returns and
+        valid until the result is closed."""
+        a, c = C.c_uint64(), C.c_uint64()
+        k, st = C.c_uint32(), C.c_uint32()
+        pc, ps = C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_assoc_scan_device(self._h, C.byref(a), C.byref(c), C.byref(k), C.byref(st), C.byref(pc), C.byref(ps)),
+               "vs_result_assoc_scan_device")
+        return (int(ps.value or 0), int(pc.value or 0), int(a.value), int(c.value), int(k.value),
+                "chi2" if st.value == self.ASSOC_STATS["chi2"] else "dot")
+
     BURDEN_DTYPE = np.dtype([("variants", "<u4"), ("alt_alleles", "<u4"), ("hom_alt", "<u4"), ("phased", "<u4")])
 
     def sample_burden(self):
@@ -714,6 +770,39 @@ class VariantStore:
             window = 0
         _check(self._lib.vs_query_ld_band(self._h, ptr, n, ids_ptr, n_ids, window, int(stat) & 0xFFFFFFFF, C.byref(h)),
                "vs_query_ld_band")
+        return QueryResult(self, h)
+
+    def assoc_scan(self, regions, traits, samples=None, stat="dot", trait_names=None) -> QueryResult:
+        """Association scan over regions (vs_query_assoc_scan): every row of the variant table a type-6 batch over `regions`
+        produces against K phenotypes (1 .. 8) in one pass over its carriers, no genotype matrix in between.  `traits`: array-like
+        of shape (n,) or (n, K), float32; row i belongs to samples[i] (names or ids, in any order, each once), or with samples
+        None to sample id i + 1 of the whole cohort.  `stat`: "dot" (the sum of dosage x value, float64) or "chi2" (the score test
+        of a regression of the value on the dosage; for a 0/1 trait the Cochran-Armitage trend test).  Pass residuals to adjust
+        for covariates, and the subset of samples that have a value.  `regions` as for allele_counts.  Read the result with
+        QueryResult.assoc_scan / assoc_scan_device / region_assoc / region_text."""
+        y = np.asarray(traits, dtype=np.float32)
+        if y.ndim == 1:
+            y = y.reshape(-1, 1)
+        if y.ndim != 2:
+            raise ValueError("traits: an array of shape (n,) or (n, K)")
+        y = np.ascontiguousarray(y)
+        if isinstance(stat, str):
+            if stat.lower() not in QueryResult.ASSOC_STATS:
+                raise ValueError(f"stat {stat!r}: 'dot' or 'chi2'")
+            stat = QueryResult.ASSOC_STATS[stat.lower()]
+        arr, ptr, n = _regions_array(regions)
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        if samples is None:
+            n_ids = y.shape[0]
+        elif n_ids != y.shape[0]:
+            raise ValueError(f"traits has {y.shape[0]} rows for {n_ids} samples")
+        names = [str(s) for s in trait_names] if trait_names is not None else None
+        if names is not None and len(names) != y.shape[1]:
+            raise ValueError(f"{len(names)} trait names for {y.shape[1]} traits")
+        name_arr = (C.c_char_p * len(names))(*[s.encode() for s in names]) if names else None
+        h = C.c_void_p()
+        _check(self._lib.vs_query_assoc_scan(self._h, ptr, n, ids_ptr, n_ids, y.ctypes.data_as(C.POINTER(C.c_float)), y.shape[1],
+                                             int(stat) & 0xFFFFFFFF, name_arr, C.byref(h)), "vs_query_assoc_scan")
         return QueryResult(self, h)
 
     def get_sample_var_in_ref(self, regions, sample) -> QueryResult:

@@ -111,10 +111,11 @@ bool dir_exists(const std::string& p) {
 }
 
 struct Args {
-  std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out, samples_file, groups_file;
+  std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out, samples_file, groups_file, pheno_file;
   uint32_t min_ac = 0, max_ac = UINT32_MAX;   // `burden`: the alternate-allele-count window of the rows that count
   uint32_t ld_window = 64;   // `ld`: every row against the next ld_window rows; --dot: dot products instead of r^2
   bool ld_dot = false;
+  bool assoc_chi2 = false;   // `assoc`: the score test instead of the dot products
   uint32_t type = 0, mode = 0;
   uint64_t hops = 0;
   bool have_hops = false;
@@ -793,6 +794,92 @@ int groups_main(const Args& a) {
   return EXIT_SUCCESS;
 }
 
+// `variantstore assoc`: every variant the regions report scored against the phenotypes of a file (vs_query_assoc_scan).  The -P file
+// holds one `sample value [value ...]` line per sample, fields separated by tabs or spaces; its samples are the subset.  A first line
+// `#sample name1 name2 ...` names the traits.  Output as `counts`: "#region <i> <x>:<y>", then the region's text.
+int assoc_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore assoc -p <output-prefix> -r <region> -P <phenotype-file> [--chi2] [-o <outfile>] [--device <n>]\n\n"
+               "        Every variant query type 6 reports in each region against up to 8 phenotypes: the sum of dosage x value over\n"
+               "        the file's samples, or with --chi2 the score test of a regression of the value on the dosage.  The file holds\n"
+               "        one `sample value [value ...]` line per sample; a first line `#sample name1 name2 ...` names the traits.\n";
+  return EXIT_FAILURE;
+}
+
+int assoc_main(const Args& a) {
+  vs_index* idx = nullptr;
+  int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
+  if (rc != VS_OK) die(rc, "load");
+  auto fail_with = [&](const std::string& msg) { error(msg); vs_index_close(idx); return EXIT_FAILURE; };
+  std::ifstream in(a.pheno_file);
+  if (!in) return fail_with("cannot open phenotype file " + a.pheno_file);
+  auto fields_of = [](const std::string& line) {
+    std::vector<std::string> f;
+    for (size_t p = line.find_first_not_of(" \t"); p != std::string::npos;) {
+      const size_t e = line.find_first_of(" \t", p);
+      f.push_back(line.substr(p, e == std::string::npos ? e : e - p));
+      p = e == std::string::npos ? e : line.find_first_not_of(" \t", e);
+    }
+    return f;
+  };
+  std::vector<uint32_t> ids;
+  std::vector<float> traits;
+  std::vector<std::string> names;
+  size_t n_traits = 0, lineno = 0;
+  std::string line;
+  while (std::getline(in, line)) {
+    ++lineno;
+    const std::string at = a.pheno_file + " line " + std::to_string(lineno);
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    const std::vector<std::string> f = fields_of(line);
+    if (f.empty()) continue;
+    if (f[0] == "#sample") {
+      if (!ids.empty() || !names.empty() || f.size() < 2) return fail_with(at + ": a `#sample name ...` line comes first and once");
+      if (f.size() - 1 > VS_TRAITS_MAX) return fail_with(at + ": more than " + std::to_string(VS_TRAITS_MAX) + " traits");
+      names.assign(f.begin() + 1, f.end());
+      n_traits = names.size();
+      continue;
+    }
+    if (f.size() < 2) return fail_with(at + ": no value behind the sample");
+    if (!n_traits) n_traits = f.size() - 1;
+    if (f.size() - 1 != n_traits) return fail_with(at + ": " + std::to_string(f.size() - 1) + " values, " + std::to_string(n_traits) + " expected");
+    if (n_traits > VS_TRAITS_MAX) return fail_with(at + ": more than " + std::to_string(VS_TRAITS_MAX) + " traits");
+    uint32_t sid = 0;
+    if (vs_index_sample_id(idx, f[0].c_str(), &sid) != VS_OK || sid == 0) return fail_with(at + ": Sample not found: " + f[0]);
+    ids.push_back(sid);
+    for (size_t k = 1; k < f.size(); ++k) {
+      char* end = nullptr;
+      const float v = strtof(f[k].c_str(), &end);
+      if (end == f[k].c_str() || *end) return fail_with(at + ": not a number: " + f[k]);
+      traits.push_back(v);
+    }
+  }
+  if (ids.empty()) return fail_with("no samples in " + a.pheno_file);
+  std::vector<const char*> name_ptrs;
+  for (auto& n : names) name_ptrs.push_back(n.c_str());
+  std::vector<vs_region> batch;
+  for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
+  vs_result* res = nullptr;
+  rc = vs_query_assoc_scan(idx, batch.data(), batch.size(), ids.data(), ids.size(), traits.data(), (uint32_t)n_traits, a.assoc_chi2 ? VS_ASSOC_CHI2 : VS_ASSOC_DOT,
+                           names.empty() ? nullptr : name_ptrs.data(), &res);
+  if (rc != VS_OK) die(rc, "assoc");
+  std::ofstream file;
+  if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
+  std::ostream& out = a.outfile.empty() ? std::cout : file;
+  for (size_t i = 0; i < batch.size(); ++i) {
+    const char* text = nullptr;
+    uint64_t len = 0;
+    rc = vs_result_format_region(res, i, &text, &len);
+    if (rc != VS_OK) die(rc, "result");
+    out << "#region " << i << " " << batch[i].x << ":" << batch[i].y << "\n";
+    out.write(text, len);
+  }
+  out.flush();
+  vs_result_free(res);
+  vs_index_close(idx);
+  return EXIT_SUCCESS;
+}
+
 int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
@@ -880,7 +967,7 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "groups") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "groups" || a.cmd == "assoc") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
@@ -888,7 +975,9 @@ int main(int argc, char** argv) {
       else if (a.cmd == "ld" && f == "--dot") a.ld_dot = true;
       else if (f == "-r" || f == "--region") a.region = need(i);
       else if (a.cmd == "groups" && (f == "-G" || f == "--groups")) a.groups_file = need(i);
-      else if (a.cmd != "groups" && (f == "-S" || f == "--samples")) a.samples_file = need(i);
+      else if (a.cmd == "assoc" && (f == "-P" || f == "--phenotypes")) a.pheno_file = need(i);
+      else if (a.cmd == "assoc" && f == "--chi2") a.assoc_chi2 = true;
+      else if (a.cmd != "groups" && a.cmd != "assoc" && (f == "-S" || f == "--samples")) a.samples_file = need(i);
       else if (f == "-o" || f == "--output_file") a.outfile = need(i);
       else if (f == "--device") a.device = atoi(need(i).c_str());
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
@@ -901,6 +990,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "groups") {
     if (a.prefix.empty() || a.region.empty() || a.groups_file.empty()) return groups_usage();
     return groups_main(a);
+  }
+  if (a.cmd == "assoc") {
+    if (a.prefix.empty() || a.region.empty() || a.pheno_file.empty()) return assoc_usage();
+    return assoc_main(a);
   }
   if (a.cmd == "burden") {
     if (a.prefix.empty() || a.region.empty()) return burden_usage();

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -88,6 +89,7 @@ struct EngineOpts {
   uint32_t fill_chunk = 0;      // rows per task of the expansion: 0 = by the batch's shape, else 8 / 16 / 32 / 64
   uint32_t burden_chunk = 0;    // rows one workgroup of the burden kernel walks before a region is split: 0 = kBurdenChunkRows
   uint32_t matrix_max_mib = 0;  // largest genotype matrix a batch may ask for, MiB: 0 = 32 GiB
+  uint32_t assoc_lds_max_kib = 0;   // largest phenotype table k_assoc_scan stages in LDS, KiB: 0 = 32; a larger one is read through global memory
   uint32_t matrix_tile_cols = 0;   // column tile of the matrix kernel: 0 = kMatrixTileCols, else a multiple of 16 in 16..65536
   int fill_mode = 0;            // shared expansion: 0 one launch, 2 split (lists + rows, then the dense sites: what a profiler wants to see apart)
   uint32_t fill_dense_k = 16;   // dense sites per wave of k_fill_dense: 8 / 16 / 32 / 64
@@ -140,6 +142,7 @@ struct vs_index {
   static constexpr int kPlanSlots = 8;
   vs_result* plan_slot_owner[kPlanSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   uint32_t plan_slot_next = 0;
+  uint32_t assoc_lds_raised = 0;   // k_assoc_scan instantiations whose dynamic-LDS limit this handle's device has raised (launch_assoc_form), a bit each
   uint64_t t6_speculated = 0, t6_refused = 0;   // batches submitted without a host wait / of those, refused on the device and redone (vs_index_info)
   uint64_t share_seq = 0;                   // sequence number of the plan's totals mailbox
   uint64_t done_seq = 0;                    // sequence number of the batch completion word
@@ -237,7 +240,7 @@ struct vs_result {
   const VariantRow* raw_rows = nullptr;
   const uint8_t* raw_arena = nullptr;   // NULL: carriers not copied
   int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts;
-                 // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts
+                 // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts; kKindAssoc: association scan
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -246,6 +249,13 @@ struct vs_result {
   uint32_t n_groups = 0;
   std::vector<uint32_t> group_sizes;
   std::vector<std::string> group_names;
+  // association-scan results (vs_query_assoc_scan): table rows x n_traits float64 cells in HBM (row-major) and their page-locked host
+  // copy in cells_pin, the count record of every table row over the subset in d_counts / counts_pin as for a count result, the column
+  // ids h_cols, per trait Sy and Syy over the columns, and the traits' names (empty: the decimal index stands for a trait)
+  double* d_scores = nullptr;
+  uint32_t n_traits = 0, assoc_stat = 0;
+  std::vector<double> trait_sum, trait_sumsq;
+  std::vector<std::string> trait_names;
   // burden results (vs_query_sample_burden): the regions x columns matrix in HBM (16 bytes per cell, row-major), the sum of its
   // `variants` (a device word the kernels add to), the column ids, and the matrix's page-locked host copy
   uint4* d_cells = nullptr;
@@ -280,13 +290,16 @@ constexpr int kKindBurden = 9;   // ... of a burden result: the rows of type 6, 
 constexpr int kKindMatrix = 10;  // ... of a genotype-matrix result: the rows of type 6, a table rows x samples byte matrix instead of carrier lists
 constexpr int kKindLd = 11;      // ... of an LD result: the rows of type 6, a table rows x window band of pair statistics instead of carrier lists
 constexpr int kKindGroups = 12;  // ... of a grouped-count result: the rows of type 6, a count record per row and sample group instead of carrier lists
+constexpr int kKindAssoc = 13;   // ... of an association-scan result: the rows of type 6, a score per row and trait instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups;
+  return r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
   if (r->kind == kKindCounts) return refuse_counts(what);
   if (r->kind == kKindGroups)
     return fail(VS_ERR_UNSUPPORTED, "%s: a grouped-count result holds counts per row and group, no carrier lists (vs_result_get_group_counts)", what);
+  if (r->kind == kKindAssoc)
+    return fail(VS_ERR_UNSUPPORTED, "%s: an association-scan result holds a score per row and trait, no carrier lists (vs_result_get_assoc_scan)", what);
   if (r->kind == kKindLd)
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD result holds a rows x window band of pair statistics, no carrier lists (vs_result_get_ld_band)", what);
   if (r->kind == kKindMatrix)
@@ -809,7 +822,7 @@ struct Slab {
   struct Part { void* ptr; size_t off; void (*set)(void* ptr, uint8_t* at); };
   size_t bytes = 0;
   uint8_t* base = nullptr;
-  Part parts[16];   // (a shared batch registers eleven)
+  Part parts[16];   // (a shared batch registers twelve)
   int n_parts = 0;
   template <typename T> void want(T*& p, size_t count) {
     parts[n_parts++] = Part{&p, bytes, [](void* ptr, uint8_t* at) { *static_cast<T**>(ptr) = reinterpret_cast<T*>(at); }};
@@ -1143,7 +1156,9 @@ static int capture_totals(vs_result* r) {
 // the whole cohort) and its words; for burden and matrix the columns in front of each word of the mask (NULL with the mask) and
 // their number; for burden the window (0 .. UINT32_MAX: every reported row counts, k_allele_counts is not run); for LD the band's
 // window and statistic.  Groups: `mask` is the label table (a byte per sample id, eight to a word), n_cols the number of groups.
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups };
+// Assoc: mask, rank and n_cols as for the matrix; `pheno` is the upload that travels with them -- Sy[8], Syy[8] as doubles, then the
+// phenotype table in column order, [column][Kp] float32 -- of pheno_words 8-byte words; the traits and the statistic.
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1151,6 +1166,9 @@ struct SharedReq {
   const uint32_t* rank = nullptr;
   uint32_t n_cols = 0, min_ac = 0, max_ac = UINT32_MAX;
   uint32_t ld_window = 0, ld_stat = 0;
+  const uint64_t* pheno = nullptr;
+  size_t pheno_words = 0;
+  uint32_t n_traits = 0, assoc_stat = 0;
   bool window() const { return min_ac != 0 || max_ac != UINT32_MAX; }
 };
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
@@ -1252,6 +1270,47 @@ static void launch_group_counts(vs_index* idx, const DevResult& d, const uint32_
   const unsigned blocks = (unsigned)((d.A + per_block - 1) / per_block);
   hipLaunchKernelGGL(k_group_counts, dim3(blocks), dim3(256), (size_t)words * 8, idx->stream, idx->d, (const VariantRow*)d.rows, u_site, d.A, U, d_labels, words,
                      n_groups, out);
+}
+
+// k_assoc_scan over the whole table of an association batch, behind k_allele_counts over the same table (d_pheno: SharedReq::pheno on
+// the device).  The table form: in LDS when it is at most option assoc_lds_max_kib and the workgroup's LDS stays within a CU's.
+template <uint32_t KP, bool SUBSET>
+static int launch_assoc_form(vs_index* idx, const AssocArgs& a, unsigned blocks, bool lds_table, size_t lds) {
+  const void* fn = lds_table ? reinterpret_cast<const void*>(&k_assoc_scan<KP, SUBSET, true>) : reinterpret_cast<const void*>(&k_assoc_scan<KP, SUBSET, false>);
+  // more than the default LDS of a launch: the limit is raised once per instantiation, to all a CU has beside the static part
+  const uint32_t bit = 1u << (4 * (KP == 1 ? 0 : KP == 2 ? 1 : KP == 4 ? 2 : 3) + 2 * SUBSET + lds_table);
+  if (lds + assoc_static_lds(KP) > (48 << 10) && !(idx->assoc_lds_raised & bit)) {
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kAssocLdsPerCu - assoc_static_lds(KP))));
+    idx->assoc_lds_raised |= bit;
+  }
+  if (lds_table) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_assoc_scan<KP, SUBSET, true>), dim3(blocks), dim3(256), lds, idx->stream, idx->d, a);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_assoc_scan<KP, SUBSET, false>), dim3(blocks), dim3(256), lds, idx->stream, idx->d, a);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+static int launch_assoc(vs_index* idx, vs_result* r, const uint32_t* u_site, uint64_t U, const uint64_t* d_mask, const uint32_t* d_rank, const uint64_t* d_pheno,
+                        const SharedReq& q) {
+  const DevResult& d = r->d;
+  const uint32_t kp = assoc_pow2(q.n_traits);
+  AssocArgs a{};
+  a.rows = (const VariantRow*)d.rows; a.u_site = u_site; a.A = d.A; a.U = U;
+  a.S = d_mask; a.S_rank = d_rank; a.s_words = d_mask ? q.words : 0;
+  a.n_cols = q.n_cols; a.K = q.n_traits; a.chi2 = q.assoc_stat == VS_ASSOC_CHI2;
+  a.sums = reinterpret_cast<const double*>(d_pheno);
+  a.table = reinterpret_cast<const float*>(d_pheno + 2 * kAssocTraitsMax);
+  a.counts = r->d_counts; a.out = r->d_scores;
+  const size_t sub = d_mask ? ((size_t)q.words * 8 + 15) / 16 * 16 + ((size_t)q.words * 4 + 15) / 16 * 16 : 0;
+  const size_t table = (size_t)q.n_cols * kp * 4;
+  const size_t cap = (size_t)(idx->opts.assoc_lds_max_kib ? idx->opts.assoc_lds_max_kib : 32) << 10;
+  const bool lds_table = table <= cap && assoc_static_lds(kp) + sub + table <= kAssocLdsPerCu;
+  const size_t lds = sub + (lds_table ? table : 0);
+  const unsigned blocks = (unsigned)((d.A + 4 * kAssocRows - 1) / (4 * kAssocRows));
+  switch (kp) {
+    case 1: return d_mask ? launch_assoc_form<1, true>(idx, a, blocks, lds_table, lds) : launch_assoc_form<1, false>(idx, a, blocks, lds_table, lds);
+    case 2: return d_mask ? launch_assoc_form<2, true>(idx, a, blocks, lds_table, lds) : launch_assoc_form<2, false>(idx, a, blocks, lds_table, lds);
+    case 4: return d_mask ? launch_assoc_form<4, true>(idx, a, blocks, lds_table, lds) : launch_assoc_form<4, false>(idx, a, blocks, lds_table, lds);
+    default: return d_mask ? launch_assoc_form<8, true>(idx, a, blocks, lds_table, lds) : launch_assoc_form<8, false>(idx, a, blocks, lds_table, lds);
+  }
 }
 
 // The burden matrix of a count batch whose per-region arrays are in the caller's order: one workgroup per (region, column tile), and
@@ -1377,7 +1436,7 @@ static int launch_ld(vs_index* idx, vs_result* r, const uint8_t* cells, const Sh
 //                      unless the expansion writes the rows itself; a column request: the site of every row (k_count_slow_sites)
 //   shared_expand      Lists: k_fill_sites2, the shared rows AND their carrier lists in one launch -- with async_fill k_fill_sites on
 //                      the second stream, with resident lists nothing | shared_columns  Counts: k_allele_counts over the table,
-//                      Groups: k_group_counts over the table
+//                      Groups: k_group_counts over the table, Assoc: k_allele_counts, then k_assoc_scan over the table
 //   shared_permute_out an unsorted batch's per-region arrays back in the caller's order
 //   shared_columns     Burden, Matrix, LD, behind the permutation -- the matrix's rows are the regions in the caller's order: k_allele_counts
 //                      only under a window, k_sample_burden over (region, column tile) pairs and for regions longer than a chunk
@@ -1396,7 +1455,7 @@ struct SharedCtx {
   ScratchBufs ld_tmp;   // an LD batch's temporary genotype matrix, apart from the rest: an enqueued batch keeps it only until it has finished
   // the consumer, asked once: Lists -- carrier lists in an arena (the result's or the resident one), may speculate, owns the handle's
   // type-6 hints; else a column request -- no arena, never speculative, hints untouched, the site of EVERY row (u_site).  Burden,
-  // Matrix and LD are consumed behind k_permute_out, Lists, Counts and Groups in front of it
+  // Matrix and LD are consumed behind k_permute_out, Lists, Counts, Groups and Assoc in front of it
   const bool lists, behind_perm;
   // shared_setup: the decisions taken up front
   bool allow_async = false, async_submit = false, sort_first = false, plan_aside = false, resident = false, spec = false;
@@ -1408,6 +1467,7 @@ struct SharedCtx {
   uint64_t want_rows = 0, want_arena = 0;
   uint64_t* d_mask = nullptr;   // a column request over a subset: its bit mask, copied with the regions
   uint32_t* d_rank = nullptr;   // (burden, matrix) the columns in front of each mask word
+  uint64_t* d_pheno = nullptr;  // (assoc) the traits' sums and the phenotype table, copied with them
   // the plan's temporaries (e_prev_c: the arena prefix at E_prev, carried by the same scan -- k_rows.hip.h: ShareMax)
   uint32_t items = 0, ntiles = 0, *e_prev = nullptr, *status = nullptr, *slow_list = nullptr, *coarse = nullptr;
   uint64_t* e_prev_c = nullptr;
@@ -1462,6 +1522,7 @@ static int shared_setup(SharedCtx& c, const vs_region* regions, bool regions_on_
     (void)region_arrays(d, &dreg, n, [&](auto** p, uint64_t k) { sl.want(*p, k); return VS_OK; });
     if (q.mask) sl.want(c.d_mask, q.words);
     if (q.rank) sl.want(c.d_rank, q.words);
+    if (q.pheno) sl.want(c.d_pheno, q.pheno_words);
     VS_TRY(ralloc(r, sl.bytes, &sl.base));
     sl.carve();
   }
@@ -1484,6 +1545,7 @@ static int shared_setup(SharedCtx& c, const vs_region* regions, bool regions_on_
   else HIP_TRY(hipMemsetAsync(dreg, 0, n * 16, c.ps));
   if (c.d_mask) HIP_TRY(hipMemcpyAsync(c.d_mask, q.mask, (size_t)q.words * 8, hipMemcpyHostToDevice, c.ps));
   if (c.d_rank) HIP_TRY(hipMemcpyAsync(c.d_rank, q.rank, (size_t)q.words * 4, hipMemcpyHostToDevice, c.ps));
+  if (c.d_pheno) HIP_TRY(hipMemcpyAsync(c.d_pheno, q.pheno, q.pheno_words * 8, hipMemcpyHostToDevice, c.ps));
   HIP_TRY(hipEventRecord(idx->ev[0], c.ps));
   c.resident = c.lists && idx->opts.resident_lists && idx->res_arena;
   c.items = (uint32_t)((n + (uint64_t)kPlanBlock * kPlanMaxTiles - 1) / ((uint64_t)kPlanBlock * kPlanMaxTiles));
@@ -1621,6 +1683,18 @@ static int group_counts_fit(SharedCtx& c) {
   return fail(VS_ERR_ARG, "grouped counts of %llu rows x %u groups take %llu bytes, more than the limit of %llu MiB (option matrix_max_mib): split the batch",
               (unsigned long long)r->d.A, c.req.n_cols, (unsigned long long)(r->d.A * row_bytes), (unsigned long long)(cap >> 20));
 }
+// The plan's rows are known: an association scan beyond the limit (rows x traits cells of 8 bytes and the rows' count records) is
+// refused here, before they or the table are allocated.
+static int assoc_fits(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  const uint64_t row_bytes = 8ull * c.req.n_traits + 16;
+  if (r->d.A <= cap / row_bytes) return VS_OK;
+  (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+  (void)hipStreamSynchronize(idx->stream);
+  return fail(VS_ERR_ARG, "an association scan of %llu rows x %u traits takes %llu bytes, more than the limit of %llu MiB (option matrix_max_mib): split the batch",
+              (unsigned long long)r->d.A, c.req.n_traits, (unsigned long long)(r->d.A * row_bytes), (unsigned long long)(cap >> 20));
+}
 // The plan's rows are known: a genotype matrix beyond the limit is refused here, before it or the table is allocated.
 // An LD batch: the temporary matrix and the band together, under the same limit.
 static int matrix_fits(SharedCtx& c) {
@@ -1673,6 +1747,12 @@ static int shared_tables(SharedCtx& c) {
       VS_TRY(group_counts_fit(c));
       VS_TRY(ralloc(r, d.A, &d.rows));
       VS_TRY(ralloc(r, (size_t)(d.A * q.n_cols), &r->d_counts));
+      break;
+    case ReqKind::Assoc:
+      VS_TRY(assoc_fits(c));
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      VS_TRY(ralloc(r, (size_t)(d.A * q.n_traits), &r->d_scores));
       break;
     case ReqKind::Burden:
       VS_TRY(ralloc(r, d.A, &d.rows));
@@ -1803,7 +1883,7 @@ static int shared_expand(SharedCtx& c) {
   return c.fused ? shared_expand_fused(c) : fill_lists(idx, r->d, true, c.u_site, c.n_fill);
 }
 // A column request's kernels between the result's own pair of events (vs_result_fill_ms).  Counts, Groups: one launch over the whole
-// table.  Burden, Matrix, LD (behind the permutation): a burden filter's counts are inside the pair, and so are the three launches of
+// table.  Assoc: k_allele_counts over the table, then k_assoc_scan.  Burden, Matrix, LD (behind the permutation): a burden filter's counts are inside the pair, and so are the three launches of
 // an LD batch: counts, temporary matrix, band.
 static int shared_columns(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
@@ -1814,6 +1894,7 @@ static int shared_columns(SharedCtx& c) {
   else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD; Burden only under a window: shared_tables gives it counts)
     launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
   HIP_TRY(hipGetLastError());
+  if (c.req.kind == ReqKind::Assoc) VS_TRY(launch_assoc(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.d_pheno, c.req));
   if (c.req.kind == ReqKind::Burden) VS_TRY(launch_burden(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.req, c.scratch));
   if (c.req.kind == ReqKind::LD) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
@@ -2115,7 +2196,7 @@ static int run_type6(vs_index* idx, const vs_region* regions, uint64_t n, vs_res
   return run_private_batch(idx, regions, n, r, regions_on_device, site_records, 0, nullptr, allow_async);
 }
 
-// A column request (allele counts, burden, genotype matrix, LD band): the plan and the shared rows of type 6, then the request's own kernels
+// A column request (allele counts, grouped counts, association scan, burden, genotype matrix, LD band): the plan and the shared rows of type 6, then the request's own kernels
 // over the rows instead of the expansion -- every batch size, never speculative, no arena (SharedCtx::lists).
 static int run_column_batch(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, const SharedReq& req) {
   return run_type6_shared(idx, regions, n, r, is_device_ptr(regions), nullptr, /*allow_async=*/true, /*may_speculate=*/false, req);
@@ -3089,6 +3170,9 @@ int vs_index_set_option(vs_index* idx, const char* key, int64_t value) {
   } else if (k == "matrix_max_mib") {
     if (value < 0 || value > 0xFFFFFFFFll) return fail(VS_ERR_ARG, "matrix_max_mib takes 0 (default: 32 GiB) or a number of MiB");
     o.matrix_max_mib = (uint32_t)value;
+  } else if (k == "assoc_lds_max_kib") {
+    if (value < 0 || value > 128) return fail(VS_ERR_ARG, "assoc_lds_max_kib takes 0 (default: 32) or 1..128 KiB");
+    o.assoc_lds_max_kib = (uint32_t)value;
   } else if (k == "matrix_tile_cols") {
     if (value != 0 && (value < 16 || value > 65536 || value % 16)) return fail(VS_ERR_ARG, "matrix_tile_cols takes 0 (default) or a multiple of 16 in 16..65536");
     o.matrix_tile_cols = (uint32_t)value;
@@ -3247,6 +3331,74 @@ int vs_query_group_counts(vs_index* idx, const vs_region* regions, uint64_t n, c
     r->n_groups = n_groups;
     r->group_sizes = sizes;
     r->group_names = names;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
+int vs_query_assoc_scan(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, const float* traits, uint32_t n_traits,
+                        uint32_t stat, const char* const* trait_names, vs_result** out) {
+  if (!idx || !out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
+  if (n == 0) return fail(VS_ERR_ARG, "an association batch needs at least one region");
+  if (!traits) return fail(VS_ERR_ARG, "null argument: an association batch takes the samples' phenotype values");
+  if (n_traits == 0 || n_traits > VS_TRAITS_MAX) return fail(VS_ERR_ARG, "%u traits (1 .. %u)", n_traits, VS_TRAITS_MAX);
+  if (stat != VS_ASSOC_DOT && stat != VS_ASSOC_CHI2) return fail(VS_ERR_ARG, "association statistic %u is neither VS_ASSOC_DOT nor VS_ASSOC_CHI2", stat);
+  if (n_ids == 0) return fail(VS_ERR_ARG, "an empty list of samples: phenotypes of nobody");
+  const uint32_t ns = idx->g.num_samples;
+  if (!sample_ids && n_ids != (uint64_t)ns - 1)
+    return fail(VS_ERR_ARG, "without sample ids the phenotypes are the whole cohort's: %llu rows given, %u samples", (unsigned long long)n_ids, ns - 1);
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));   // (VS_ERR_UNKNOWN_SAMPLE: id 0 or an id beyond the cohort)
+  if (sample_ids && cols.size() != n_ids) {   // a sample listed twice: which of its phenotype rows would count?
+    std::vector<uint64_t> seen(mask.size(), 0);
+    for (uint64_t i = 0; i < n_ids; ++i) {
+      const uint32_t id = sample_ids[i];
+      if (seen[id >> 6] >> (id & 63) & 1) return fail(VS_ERR_ARG, "sample id %u is listed twice: a sample has one row of phenotypes", id);
+      seen[id >> 6] |= 1ull << (id & 63);
+    }
+  }
+  for (uint64_t i = 0; i < n_ids; ++i)
+    for (uint32_t k = 0; k < n_traits; ++k)
+      if (!std::isfinite(traits[i * n_traits + k]))
+        return fail(VS_ERR_ARG, "trait %u of sample id %u is not finite: pass the subset of samples that have a value", k, sample_ids ? sample_ids[i] : (uint32_t)i + 1);
+  std::vector<std::string> names;
+  if (trait_names)
+    for (uint32_t k = 0; k < n_traits; ++k) {
+      if (!trait_names[k]) return fail(VS_ERR_ARG, "null name of trait %u", k);
+      names.emplace_back(trait_names[k]);
+      if (names.back().find_first_of("\t\n") != std::string::npos) return fail(VS_ERR_ARG, "the name of trait %u holds a tab or a newline", k);
+    }
+  if (mask.size() * 8 > kCountMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the counting kernel's LDS (the whole cohort has no such limit)", ns);
+  // the upload: Sy[8], Syy[8], then the table in column order, [column][Kp] float32 with the padding zero
+  const uint32_t kp = assoc_pow2(n_traits);
+  const size_t n_cols = cols.size();
+  std::vector<uint64_t> pheno(2 * kAssocTraitsMax + (n_cols * kp * 4 + 7) / 8, 0);
+  float* table = reinterpret_cast<float*>(pheno.data() + 2 * kAssocTraitsMax);
+  for (uint64_t i = 0; i < n_ids; ++i) {
+    size_t col = i;
+    if (sample_ids) {
+      const uint32_t id = sample_ids[i];
+      col = rank[id >> 6] + (size_t)__builtin_popcountll(mask[id >> 6] & ((1ull << (id & 63)) - 1ull));
+    }
+    for (uint32_t k = 0; k < n_traits; ++k) table[col * kp + k] = traits[i * n_traits + k];
+  }
+  std::vector<double> sy(n_traits, 0.0), syy(n_traits, 0.0);   // left to right in column order, from the float32 values
+  for (size_t c = 0; c < n_cols; ++c)
+    for (uint32_t k = 0; k < n_traits; ++k) {
+      const double y = (double)table[c * kp + k];
+      sy[k] += y;
+      syy[k] += y * y;   // (the product of two float32 values is exact in double)
+    }
+  double* sums = reinterpret_cast<double*>(pheno.data());
+  for (uint32_t k = 0; k < n_traits; ++k) { sums[k] = sy[k]; sums[kAssocTraitsMax + k] = syy[k]; }
+  SharedReq req = column_request(ReqKind::Assoc, mask, rank, n_cols);
+  req.pheno = pheno.data(); req.pheno_words = pheno.size(); req.n_traits = n_traits; req.assoc_stat = stat;
+  return make_result(idx, kKindAssoc, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    r->n_traits = n_traits; r->assoc_stat = stat;
+    r->trait_sum = sy; r->trait_sumsq = syy;
+    r->trait_names = names;
     return run_column_batch(idx, regions, n, r, req);
   });
 }
@@ -3606,7 +3758,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
     HIP_TRY(hipStreamSynchronize(idx->stream));
     tmp.release();
     r->n_variants = h[0]; r->n_carriers_kept = h[1]; r->n_bases = h[2];
-    if (r->kind == kKindCounts) {   // the carriers that lie in the subset: the counts of the rows every region reports (dropped rows count 0)
+    if (r->kind == kKindCounts || r->kind == kKindAssoc) {   // the carriers that lie in the subset: the counts of the rows every region reports (dropped rows count 0)
       VS_TRY(fetch_region_meta(r));
       VS_TRY(counts_to_host(r));
       const uint4* c = (const uint4*)r->counts_pin.p;
@@ -3815,6 +3967,41 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
     if (len) *len = out.size();
     return VS_OK;
   }
+  if (r->kind == kKindAssoc) {   // the region's reported rows: the count text's columns, then the K cells
+    VS_TRY(array_to_host(r, r->d_scores, (size_t)(r->d.A * r->n_traits) * sizeof(double), &r->cells_pin, "association scores"));
+    VS_TRY(counts_to_host(r));
+    const VariantRow* rows;
+    if (r->have_headers) rows = r->h_rows.data() + a0;
+    else if (r->raw_rows) rows = r->raw_rows + a0;
+    else {
+      VS_TRY(fetch(idx, r->sl_rows, (const VariantRow*)r->d.rows + a0, (size_t)(a1 - a0)));
+      HIP_TRY(hipStreamSynchronize(idx->stream));
+      rows = r->sl_rows.data();
+    }
+    const uint4* c = (const uint4*)r->counts_pin.p;
+    const double* sc = (const double*)r->cells_pin.p;
+    const uint32_t K = r->n_traits;
+    std::string& out = r->text;
+    out = "Pos\tRef\tAlt\tCarriers\tAC\tHomAlt\tPhased";
+    for (uint32_t k = 0; k < K; ++k) { out += '\t'; out += r->trait_names.empty() ? std::to_string(k) : r->trait_names[k]; }
+    out += '\n';
+    char num[48];
+    for (uint64_t a = a0; a < a1; ++a) {
+      const VariantRow& v = rows[a - a0];
+      if (v.count_flags & kRowDropped) continue;
+      out += std::to_string(v.pos);
+      out += '\t';
+      out.append(idx->seq_chars, v.ref_off, v.ref_len);
+      out += '\t';
+      out.append(idx->seq_chars, v.alt_off, v.alt_len);
+      for (uint32_t f : {c[a].x, c[a].y, c[a].z, c[a].w}) { out += '\t'; out += std::to_string(f); }
+      for (uint32_t k = 0; k < K; ++k) { snprintf(num, sizeof num, "\t%.17g", sc[a * K + k]); out += num; }
+      out += '\n';
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
   if (r->kind == kKindCounts) {   // the region's reported rows with their counts
     VS_TRY(counts_to_host(r));
     const VariantRow* rows;
@@ -3956,6 +4143,25 @@ int vs_result_get_group_counts(vs_result* r, uint64_t* n_rows, uint32_t* n_group
   return VS_OK;
 }
 
+int vs_result_get_assoc_scan(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* n_traits, uint32_t* stat, const uint32_t** col_ids, const double** trait_sum,
+                             const double** trait_sumsq, const vs_allele_counts** counts, const double** scores) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!scores) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindAssoc) return fail(VS_ERR_ARG, "not an association-scan result (vs_query_assoc_scan)");
+  VS_TRY(array_to_host(r, r->d_scores, (size_t)(r->d.A * r->n_traits) * sizeof(double), &r->cells_pin, "association scores"));
+  VS_TRY(counts_to_host(r));
+  *scores = (const double*)r->cells_pin.p;
+  if (counts) *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_traits) *n_traits = r->n_traits;
+  if (stat) *stat = r->assoc_stat;
+  if (col_ids) *col_ids = r->h_cols.data();
+  if (trait_sum) *trait_sum = r->trait_sum.data();
+  if (trait_sumsq) *trait_sumsq = r->trait_sumsq.data();
+  return VS_OK;
+}
+
 int vs_result_get_sample_burden(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, const uint32_t** col_ids, const vs_sample_burden** cells) {
   VS_TRY(result_enter(r, Want::Variants, true));
   if (!cells) return fail(VS_ERR_ARG, "null argument");
@@ -4044,6 +4250,18 @@ int vs_result_ld_band_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, u
   if (n_cols) *n_cols = r->h_cols.size();
   if (window) *window = r->ld_window;
   if (stat) *stat = r->ld_stat;
+  return VS_OK;
+}
+
+int vs_result_assoc_scan_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* n_traits, uint32_t* stat, const void** dev_counts,
+                                const void** dev_scores) {
+  VS_TRY(device_matrix_ready(r, dev_scores, kKindAssoc, "not an association-scan result (vs_query_assoc_scan)"));
+  *dev_scores = r->d_scores;
+  if (dev_counts) *dev_counts = r->d_counts;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_traits) *n_traits = r->n_traits;
+  if (stat) *stat = r->assoc_stat;
   return VS_OK;
 }
 
