@@ -282,6 +282,46 @@ int vs_result_get_assoc_scan(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, u
  * NULL), valid until vs_result_free.  The engine has synchronised its stream when this returns: the caller needs no event. */
 int vs_result_assoc_scan_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* n_traits, uint32_t* stat,
                                 const void** dev_counts, const void** dev_scores);
+/* Per-sample scores: samples x K weighted dosage sums over the rows a batch reports -- "what is each sample's polygenic score under
+ * this score file?", the projection of the samples onto K loadings, the second half of a matrix-free iteration on the genotype matrix
+ * (vs_query_assoc_scan gives G Y: every row against K per-sample vectors; this gives G^T W: every sample against K per-variant
+ * weights).  No reference counterpart: what a caller would get from vs_query_genotype_matrix and a matrix product, without the matrix.
+ * `regions`, the subset S, its n_cols = n columns (the distinct ids ascending; sample_ids == NULL: the whole cohort, ids 1 ..
+ * num_samples - 1, and n_ids must be num_samples - 1) and the dosage d = popc(gt & 6) are vs_query_assoc_scan's.
+ * Weights are keyed by REPORT ORDER.  rep[q] is the number of rows region q reports: the table rows row_begin[q] .. + row_count[q]
+ * whose dropped flag is clear -- the data lines of vs_result_format_region(q), and of the reference's type-6 text.  off[q] is the
+ * exclusive prefix sum of rep in the caller's region order, N the sum of rep.  `weights` is N x n_scores float32, row-major,
+ * 1 <= n_scores <= VS_SCORES_MAX, in host or device memory (told apart as the regions are); entry off[q] + j belongs to the j-th row
+ * region q reports.  A row that several regions report takes part once per report, with that report's weight (the burden's rule).
+ * (Weights cannot be keyed by table row: the private rows of two batches over the same regions need not lie alike.)
+ * The sums are taken in 64-bit fixed point, so that the same call gives the same bytes.  Per column k: M_k = max |w| over its N values;
+ * M_k == 0: f_k = 0; else M_k = m 2^e with 0.5 <= m < 1 (frexp) and f_k = 36 - e.  q = rint((double)w 2^f_k), ties to even, so
+ * |q| <= 2^36.  sums[c * n_scores + k] = the sum over the reports of d(row, column c) q, an int64, exact whatever the order.
+ * scores[c * n_scores + k] = ldexp((double)sums[c * n_scores + k], -f_k).  Weights with |w| >= 2^-12 M_k are represented exactly; any
+ * term is off by at most d 2^(e - 37).
+ * Refused, beside everything vs_query_assoc_scan refuses about regions and ids: n_scores outside 1 .. VS_SCORES_MAX -> VS_ERR_ARG; a
+ * weight that is not finite -> VS_ERR_ARG, the message names the column (host weights are checked on the host before the device is
+ * asked for, device weights by the scale kernel); n_weights != N -> VS_ERR_ARG, the message names both numbers, once the plan has
+ * given rep and before anything further is allocated; N >= 2^26 -> VS_ERR_ARG (below that |sum| <= 2 N 2^36 < 2^63); a score name
+ * (score_names: NULL, or n_scores strings that are copied) with a tab or a newline -> VS_ERR_ARG.  The uploaded weights, the integer
+ * weights per table row (rows x Kp x 8 bytes, Kp = n_scores rounded up to 1, 2, 4 or 8, + 4 bytes a row) and the sums and scores are
+ * held to option "matrix_max_mib": VS_ERR_ARG.  A handle opened without a device reports the host's checks first and
+ * VS_ERR_NO_DEVICE otherwise.  A batch whose table is empty gives all-zero scores over the n columns and is no error.
+ * Every batch size takes the batch pipeline; a score batch is never speculative and leaves the handle's type-6 state as it was.  The
+ * result holds the type-6 per-region arrays and variant table, no carrier arena, as an association result does: vs_result_fill_ms is
+ * the new kernels' own pair of events, vs_result_totals' n_carriers the number of (report, carrier in S) pairs whose report has a
+ * weight that is not zero after quantisation, vs_result_format_region the region's reported rows ("Pos\tRef\tAlt", a line per row:
+ * the rows of the type-6 text without their carriers, which no arena holds).  The other kinds' getters fail with VS_ERR_ARG. */
+#define VS_SCORES_MAX 8u
+int vs_query_sample_scores(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids,
+                           const float* weights, uint64_t n_weights, uint32_t n_scores, const char* const* score_names, vs_result** out);
+/* The cells of a score result copied into page-locked memory owned by the result: sums and scores [n_cols x n_scores], shift the
+ * n_scores values f_k, col_ids the n_cols column ids (any may be NULL but not both sums and scores).  VS_ERR_ARG on any other result. */
+int vs_result_get_sample_scores(vs_result* r, uint64_t* n_cols, uint32_t* n_scores, const uint32_t** col_ids, const int32_t** shift,
+                                const int64_t** sums, const double** scores);
+/* The cells as they lie in HBM: n_cols x n_scores int64 sums and float64 scores, row-major (dev_sums may be NULL), valid until
+ * vs_result_free.  The engine has synchronised its stream when this returns: the caller needs no event. */
+int vs_result_sample_scores_device(vs_result* r, uint64_t* n_cols, uint32_t* n_scores, const void** dev_sums, const void** dev_scores);
 /* Per-sample burden over regions: the counts above along the other axis -- a regions x samples matrix, the input of gene-burden
  * and collapsing tests and of per-sample QC counts (no reference counterpart: what a caller of type 6 would reduce on the host
  * from every carrier list).  Let R(q) be the rows type 6 reports for region q (same order, duplicate rule and region flags; a
@@ -604,10 +644,14 @@ void vs_comm_destroy(vs_comm* c);
  *   "burden_chunk"    rows of a region one workgroup of the burden kernel walks (vs_query_sample_burden): a region with more is
  *                     split between several, which add to its cells with atomics.  0 (default): 4096; else 64..65536
  *   "matrix_max_mib"  the largest genotype matrix (vs_query_genotype_matrix; also an LD batch's matrix + band, the records of
- *                     vs_query_group_counts and the cells + records of vs_query_assoc_scan), in MiB, a batch may ask for.  0 (default): 32 GiB
+ *                     vs_query_group_counts, the cells + records of vs_query_assoc_scan and the buffers of vs_query_sample_scores), in MiB, a batch may ask for.  0 (default): 32 GiB
  *   "assoc_lds_max_kib" the largest phenotype table (columns x traits rounded up to 1, 2, 4 or 8, x 4 bytes) the kernel of
  *                     vs_query_assoc_scan stages in LDS, in KiB; a larger one is read through global memory.  0 (default): 32; else
  *                     1..128 (small cohorts reach the global form with 1).  The scores are the same bytes in either form
+ *   "score_chunk"     table rows one workgroup of the score kernel walks (vs_query_sample_scores).  0 (default): 4096; else 64..65536
+ *   "score_tile_cols" columns of a workgroup's tile of the score kernel: 0 (default): all that 64 KiB of int64 cells hold,
+ *                     65536 / (8 Kp); else a multiple of 16 in 16..65536, held to that (small cohorts reach tile boundaries with it).
+ *                     The sums are the same integers under every setting of the two
  *   "matrix_tile_cols" columns of a workgroup's tile of the matrix kernel: 0 (default): 4096; else a multiple of 16 in 16..65536
  *                     (small cohorts reach tile boundaries with it)
  * Tuning builds (VS_BUILD_TUNING=1 python -m variantstore_amd.build --force) add "lat_debug", "fill_fused", "fill_chunk",

@@ -335,6 +335,39 @@ class QueryResult:
         return (int(ps.value or 0), int(pc.value or 0), int(a.value), int(c.value), int(k.value),
                 "chi2" if st.value == self.ASSOC_STATS["chi2"] else "dot")
 
+    def sample_scores(self):
+        """A per-sample score result (VariantStore.sample_scores) as numpy arrays: `scores` ((n, K) float64: scores[c, k] is the
+        sum over the reported rows of dosage x weight k for the sample of column c), `sums` ((n, K) int64: the same sums in fixed
+        point, exact) and `shift` (int32[K]: scores = ldexp(sums, -shift)), `col_ids` (uint32[n], the sample ids of the columns,
+        ascending) and their `names`, `score_names` (list of K strings), the table's `rows` and per region `row_begin`,
+        `row_count` and `flags`.  Copies, valid after the result is closed."""
+        c, k = C.c_uint64(), C.c_uint32()
+        cols = C.POINTER(C.c_uint32)()
+        sh = C.POINTER(C.c_int32)()
+        su = C.POINTER(C.c_int64)()
+        sc = C.POINTER(C.c_double)()
+        _check(self._lib.vs_result_get_sample_scores(self._h, C.byref(c), C.byref(k), C.byref(cols), C.byref(sh), C.byref(su), C.byref(sc)),
+               "vs_result_get_sample_scores")
+        nc, nk = int(c.value), int(k.value)
+        raw = self.raw(with_carriers=False)
+        col_ids = np.ctypeslib.as_array(cols, shape=(nc,)).copy()
+        given = getattr(self, "score_names", None)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "flags": raw["region_flags"].copy(), "col_ids": col_ids, "names": [self._store.sample_name(int(i)) for i in col_ids],
+                "shift": np.ctypeslib.as_array(sh, shape=(nk,)).copy(),
+                "sums": np.ctypeslib.as_array(su, shape=(nc * nk,)).reshape(nc, nk).copy(),
+                "scores": np.ctypeslib.as_array(sc, shape=(nc * nk,)).reshape(nc, nk).copy(),
+                "score_names": list(given) if given else [str(i) for i in range(nk)]}
+
+    def sample_scores_device(self):
+        """(scores address, sums address, n_cols, n_scores) of a per-sample score result as it lies in this GPU's memory:
+        n_cols x n_scores float64 scores and int64 sums, row-major, complete when this returns and valid until the result is closed."""
+        c, k = C.c_uint64(), C.c_uint32()
+        pu, ps = C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_sample_scores_device(self._h, C.byref(c), C.byref(k), C.byref(pu), C.byref(ps)),
+               "vs_result_sample_scores_device")
+        return int(ps.value or 0), int(pu.value or 0), int(c.value), int(k.value)
+
     BURDEN_DTYPE = np.dtype([("variants", "<u4"), ("alt_alleles", "<u4"), ("hom_alt", "<u4"), ("phased", "<u4")])
 
     def sample_burden(self):
@@ -804,6 +837,85 @@ class VariantStore:
         _check(self._lib.vs_query_assoc_scan(self._h, ptr, n, ids_ptr, n_ids, y.ctypes.data_as(C.POINTER(C.c_float)), y.shape[1],
                                              int(stat) & 0xFFFFFFFF, name_arr, C.byref(h)), "vs_query_assoc_scan")
         return QueryResult(self, h)
+
+    def sample_scores(self, regions, weights, samples=None, score_names=None) -> QueryResult:
+        """Per-sample scores over regions (vs_query_sample_scores): for every sample of `samples` (names or ids, each once; None:
+        the whole cohort) K weighted sums of its dosages over the rows a type-6 batch over `regions` reports -- a polygenic score
+        per weight column, no genotype matrix in between.  `weights` is either an array-like of shape (N,) or (N, K), float32
+        (or a DeviceArray of N x K float32 in this GPU's memory, with `score_names` or K = 1), in REPORT order: region after region
+        as given, within a region the rows it reports (the data lines of region_text), a row of weights per reported row; or a
+        mapping {(pos, ref, alt): value or K values} with ref / alt as the texts print them.  For a mapping an allele_counts batch
+        over the regions is run first to learn the reported rows; rows without a key weigh 0, and the keys that matched no row
+        come back as `result.unmatched`.  The sums are taken in 64-bit fixed point (the weights of a column are quantised to
+        2^-36 of the column's largest): the same call gives the same bytes.  Read the result with QueryResult.sample_scores /
+        sample_scores_device."""
+        names = [str(s) for s in score_names] if score_names is not None else None
+        unmatched = None
+        keep = None
+        if isinstance(weights, dict):
+            weights, unmatched = self._weights_from_mapping(regions, weights)
+        if isinstance(weights, DeviceArray):
+            k = len(names) if names is not None else 1
+            if weights.n % k:
+                raise ValueError(f"{weights.n} device weights are no whole number of rows of {k}")
+            w_ptr, n_w = C.c_void_p(weights.ptr), weights.n // k
+        else:
+            w = np.asarray(weights, dtype=np.float32)
+            if w.ndim == 1:
+                w = w.reshape(-1, 1)
+            if w.ndim != 2:
+                raise ValueError("weights: an array of shape (N,) or (N, K), or a mapping")
+            keep = w = np.ascontiguousarray(w)
+            k = w.shape[1]
+            w_ptr, n_w = C.c_void_p(w.ctypes.data if w.size else None), w.shape[0]
+        if names is not None and len(names) != k:
+            raise ValueError(f"{len(names)} score names for {k} weight columns")
+        arr, ptr, n = _regions_array(regions)
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        if samples is None:
+            if getattr(self, "_cohort", None) is None:
+                self._cohort = self.info().num_samples - 1
+            n_ids = self._cohort
+        name_arr = (C.c_char_p * len(names))(*[s.encode() for s in names]) if names else None
+        h = C.c_void_p()
+        _check(self._lib.vs_query_sample_scores(self._h, ptr, n, ids_ptr, n_ids, w_ptr, n_w, k, name_arr, C.byref(h)), "vs_query_sample_scores")
+        del keep
+        res = QueryResult(self, h)
+        res.score_names = names
+        res.unmatched = unmatched
+        return res
+
+    def _weights_from_mapping(self, regions, mapping):
+        """The (N, K) float32 array in report order of a {(pos, ref, alt): value(s)} mapping, and the keys that matched no row."""
+        table, k = {}, None
+        for key, v in mapping.items():
+            vals = np.atleast_1d(np.asarray(v, dtype=np.float32))
+            if vals.ndim != 1 or (k is not None and vals.shape[0] != k):
+                raise ValueError(f"weights of {key!r}: every key takes the same number of values")
+            k = vals.shape[0]
+            table[(int(key[0]), str(key[1]), str(key[2]))] = vals
+        if k is None:
+            raise ValueError("an empty mapping of weights")
+        counts = self.allele_counts(regions)
+        try:
+            n_regions = counts.totals()[0]
+            rows, seen = [], set()
+            for q in range(n_regions):
+                for line in counts.region_text(q).split("\n")[1:]:
+                    if not line:
+                        continue
+                    f = line.split("\t")
+                    key = (int(f[0]), f[1], f[2])
+                    rows.append(key)
+        finally:
+            counts.close()
+        w = np.zeros((len(rows), k), np.float32)
+        for i, key in enumerate(rows):
+            v = table.get(key)
+            if v is not None:
+                w[i] = v
+                seen.add(key)
+        return w, [key for key in table if key not in seen]
 
     def get_sample_var_in_ref(self, regions, sample) -> QueryResult:
         """Query type 4 for one sample over a batch of regions (query.h:618-729)."""

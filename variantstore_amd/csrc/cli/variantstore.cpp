@@ -43,6 +43,7 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <unordered_map>
 #include <vector>
 #include "variantstore_hip.h"
 
@@ -111,7 +112,7 @@ bool dir_exists(const std::string& p) {
 }
 
 struct Args {
-  std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out, samples_file, groups_file, pheno_file;
+  std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out, samples_file, groups_file, pheno_file, weights_file;
   uint32_t min_ac = 0, max_ac = UINT32_MAX;   // `burden`: the alternate-allele-count window of the rows that count
   uint32_t ld_window = 64;   // `ld`: every row against the next ld_window rows; --dot: dot products instead of r^2
   bool ld_dot = false;
@@ -880,6 +881,150 @@ int assoc_main(const Args& a) {
   return EXIT_SUCCESS;
 }
 
+// `variantstore score`: per-sample scores of the variants the regions report under the weights of a file (vs_query_sample_scores).  The
+// -W file holds one `pos ref alt weight [weight ...]` line per variant, fields separated by tabs or spaces, pos / ref / alt as query type
+// 6 prints them; a first line `#pos ref alt name1 name2 ...` names the scores.  A count batch over the regions gives the reported rows,
+// every one takes the weights of its key (none: 0), then the score batch runs over the same regions.  Output: `Sample\t<names>`, then a
+// line per sample.
+int score_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore score -p <output-prefix> -r <region> -W <weights-file> [-S <samples-file>] [-o <outfile>] [--device <n>]\n\n"
+               "        For every sample (of the file: one name per line; default: the whole cohort) up to 8 weighted sums of its dosages\n"
+               "        over the variants query type 6 reports in the regions.  The weights file holds one `pos ref alt weight [weight ...]`\n"
+               "        line per variant; a first line `#pos ref alt name1 name2 ...` names the scores.\n";
+  return EXIT_FAILURE;
+}
+
+int score_main(const Args& a) {
+  vs_index* idx = nullptr;
+  int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
+  if (rc != VS_OK) die(rc, "load");
+  auto fail_with = [&](const std::string& msg) { error(msg); vs_index_close(idx); return EXIT_FAILURE; };
+  std::ifstream in(a.weights_file);
+  if (!in) return fail_with("cannot open weights file " + a.weights_file);
+  auto fields_of = [](const std::string& line) {
+    std::vector<std::string> f;
+    for (size_t p = line.find_first_not_of(" \t"); p != std::string::npos;) {
+      const size_t e = line.find_first_of(" \t", p);
+      f.push_back(line.substr(p, e == std::string::npos ? e : e - p));
+      p = e == std::string::npos ? e : line.find_first_not_of(" \t", e);
+    }
+    return f;
+  };
+  std::unordered_map<std::string, size_t> key_row;   // "pos\tref\talt" -> its row of `table`
+  std::vector<float> table;
+  std::vector<std::string> names;
+  size_t K = 0, lineno = 0;
+  std::string line;
+  while (std::getline(in, line)) {
+    ++lineno;
+    const std::string at = a.weights_file + " line " + std::to_string(lineno);
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    const std::vector<std::string> f = fields_of(line);
+    if (f.empty()) continue;
+    if (f[0] == "#pos") {
+      if (!key_row.empty() || !names.empty() || f.size() < 4) return fail_with(at + ": a `#pos ref alt name ...` line comes first and once");
+      if (f.size() - 3 > VS_SCORES_MAX) return fail_with(at + ": more than " + std::to_string(VS_SCORES_MAX) + " values");
+      names.assign(f.begin() + 3, f.end());
+      K = names.size();
+      continue;
+    }
+    if (f.size() < 4) return fail_with(at + ": malformed line, `pos ref alt weight [weight ...]` expected");
+    char* end = nullptr;
+    const unsigned long long pos = strtoull(f[0].c_str(), &end, 10);
+    if (end == f[0].c_str() || *end) return fail_with(at + ": malformed line, not a position: " + f[0]);
+    if (!K) K = f.size() - 3;
+    if (f.size() - 3 != K) return fail_with(at + ": " + std::to_string(f.size() - 3) + " values, " + std::to_string(K) + " expected");
+    if (K > VS_SCORES_MAX) return fail_with(at + ": more than " + std::to_string(VS_SCORES_MAX) + " values");
+    auto allele = [](const std::string& x) { return x == "-" || x == "." ? std::string() : x; };   // (an empty allele, as the texts print a deletion's)
+    const std::string key = std::to_string(pos) + "\t" + allele(f[1]) + "\t" + allele(f[2]);
+    if (!key_row.emplace(key, table.size() / K).second) return fail_with(at + ": the variant is listed twice: " + f[0] + " " + f[1] + " " + f[2]);
+    for (size_t k = 3; k < f.size(); ++k) {
+      end = nullptr;
+      const float v = strtof(f[k].c_str(), &end);
+      if (end == f[k].c_str() || *end) return fail_with(at + ": not a number: " + f[k]);
+      table.push_back(v);
+    }
+  }
+  if (key_row.empty()) return fail_with("no variants in " + a.weights_file);
+  std::vector<uint32_t> ids;
+  if (!a.samples_file.empty()) {
+    std::ifstream sin(a.samples_file);
+    if (!sin) return fail_with("cannot open sample file " + a.samples_file);
+    while (std::getline(sin, line)) {
+      if (!line.empty() && line.back() == '\r') line.pop_back();
+      if (line.empty()) continue;
+      uint32_t sid = 0;
+      if (vs_index_sample_id(idx, line.c_str(), &sid) != VS_OK || sid == 0) return fail_with("Sample not found: " + line);
+      ids.push_back(sid);
+    }
+    if (ids.empty()) return fail_with("no sample names in " + a.samples_file);
+  }
+  vs_index_info info{};
+  rc = vs_index_get_info(idx, &info);
+  if (rc != VS_OK) die(rc, "info");
+  std::vector<vs_region> batch;
+  for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
+  // the reported rows, region after region: a count batch's text
+  vs_result* cres = nullptr;
+  rc = vs_query_allele_counts(idx, batch.data(), batch.size(), nullptr, 0, &cres);
+  if (rc != VS_OK) die(rc, "score");
+  std::vector<float> weights;
+  std::vector<uint8_t> matched(key_row.size(), 0);
+  for (size_t i = 0; i < batch.size(); ++i) {
+    const char* text = nullptr;
+    uint64_t len = 0;
+    rc = vs_result_format_region(cres, i, &text, &len);
+    if (rc != VS_OK) die(rc, "result");
+    const std::string t(text, len);
+    for (size_t p = t.find('\n'); p != std::string::npos && p + 1 < t.size();) {   // (the first line is the header)
+      const size_t b = p + 1, e = t.find('\n', b);
+      size_t tab = b;
+      for (int k = 0; k < 3 && tab != std::string::npos; ++k) tab = t.find('\t', tab + (k ? 1 : 0));
+      const auto it = key_row.find(t.substr(b, (tab == std::string::npos || tab > e ? e : tab) - b));
+      if (it == key_row.end()) weights.insert(weights.end(), K, 0.0f);
+      else {
+        weights.insert(weights.end(), table.begin() + it->second * K, table.begin() + (it->second + 1) * K);
+        matched[it->second] = 1;
+      }
+      p = e;
+    }
+  }
+  vs_result_free(cres);
+  size_t unmatched = 0;
+  for (uint8_t m : matched) unmatched += !m;
+  if (unmatched) std::cerr << "warning: " << unmatched << " of " << matched.size() << " variants of " << a.weights_file << " matched no reported row\n";
+  std::vector<const char*> name_ptrs;
+  for (auto& n : names) name_ptrs.push_back(n.c_str());
+  vs_result* res = nullptr;
+  rc = vs_query_sample_scores(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.empty() ? info.num_samples - 1 : ids.size(), weights.data(),
+                              weights.size() / K, (uint32_t)K, names.empty() ? nullptr : name_ptrs.data(), &res);
+  if (rc != VS_OK) die(rc, "score");
+  uint64_t n_cols = 0;
+  uint32_t n_scores = 0;
+  const uint32_t* cols = nullptr;
+  const double* sc = nullptr;
+  rc = vs_result_get_sample_scores(res, &n_cols, &n_scores, &cols, nullptr, nullptr, &sc);
+  if (rc != VS_OK) die(rc, "result");
+  std::ofstream file;
+  if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
+  std::ostream& out = a.outfile.empty() ? std::cout : file;
+  out << "Sample";
+  for (uint32_t k = 0; k < n_scores; ++k) out << '\t' << (names.empty() ? std::to_string(k) : names[k]);
+  out << '\n';
+  char num[48];
+  for (uint64_t c = 0; c < n_cols; ++c) {
+    const char* nm = vs_index_sample_name(idx, cols[c]);
+    out << (nm ? nm : "?");
+    for (uint32_t k = 0; k < n_scores; ++k) { snprintf(num, sizeof num, "\t%.17g", sc[c * n_scores + k]); out << num; }
+    out << '\n';
+  }
+  out.flush();
+  vs_result_free(res);
+  vs_index_close(idx);
+  return EXIT_SUCCESS;
+}
+
 int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
@@ -967,7 +1112,7 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "groups" || a.cmd == "assoc") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "score") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
@@ -977,6 +1122,7 @@ int main(int argc, char** argv) {
       else if (a.cmd == "groups" && (f == "-G" || f == "--groups")) a.groups_file = need(i);
       else if (a.cmd == "assoc" && (f == "-P" || f == "--phenotypes")) a.pheno_file = need(i);
       else if (a.cmd == "assoc" && f == "--chi2") a.assoc_chi2 = true;
+      else if (a.cmd == "score" && (f == "-W" || f == "--weights")) a.weights_file = need(i);
       else if (a.cmd != "groups" && a.cmd != "assoc" && (f == "-S" || f == "--samples")) a.samples_file = need(i);
       else if (f == "-o" || f == "--output_file") a.outfile = need(i);
       else if (f == "--device") a.device = atoi(need(i).c_str());
@@ -994,6 +1140,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "assoc") {
     if (a.prefix.empty() || a.region.empty() || a.pheno_file.empty()) return assoc_usage();
     return assoc_main(a);
+  }
+  if (a.cmd == "score") {
+    if (a.prefix.empty() || a.region.empty() || a.weights_file.empty()) return score_usage();
+    return score_main(a);
   }
   if (a.cmd == "burden") {
     if (a.prefix.empty() || a.region.empty()) return burden_usage();

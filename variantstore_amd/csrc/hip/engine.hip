@@ -90,6 +90,8 @@ struct EngineOpts {
   uint32_t burden_chunk = 0;    // rows one workgroup of the burden kernel walks before a region is split: 0 = kBurdenChunkRows
   uint32_t matrix_max_mib = 0;  // largest genotype matrix a batch may ask for, MiB: 0 = 32 GiB
   uint32_t assoc_lds_max_kib = 0;   // largest phenotype table k_assoc_scan stages in LDS, KiB: 0 = 32; a larger one is read through global memory
+  uint32_t score_chunk = 0;     // table rows one workgroup of k_sample_scores walks: 0 = kScoreChunkRows, else 64..65536
+  uint32_t score_tile_cols = 0; // column tile of k_sample_scores: 0 = all a 64 KiB tile holds, 65536 / (8 Kp); else a multiple of 16, held to that
   uint32_t matrix_tile_cols = 0;   // column tile of the matrix kernel: 0 = kMatrixTileCols, else a multiple of 16 in 16..65536
   int fill_mode = 0;            // shared expansion: 0 one launch, 2 split (lists + rows, then the dense sites: what a profiler wants to see apart)
   uint32_t fill_dense_k = 16;   // dense sites per wave of k_fill_dense: 8 / 16 / 32 / 64
@@ -240,7 +242,8 @@ struct vs_result {
   const VariantRow* raw_rows = nullptr;
   const uint8_t* raw_arena = nullptr;   // NULL: carriers not copied
   int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts;
-                 // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts; kKindAssoc: association scan
+                 // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts; kKindAssoc: association scan;
+                 // kKindScores: per-sample scores
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -256,6 +259,15 @@ struct vs_result {
   uint32_t n_traits = 0, assoc_stat = 0;
   std::vector<double> trait_sum, trait_sumsq;
   std::vector<std::string> trait_names;
+  // score results (vs_query_sample_scores): columns x n_scores int64 sums in HBM (row-major) with the float64 scores formed from
+  // them right behind (d_score_out), both copied to cells_pin in one piece; the kernels' words (largest |w| per column, the
+  // pair count of vs_result_totals); f_k per column and the scores' names (empty: the decimal index stands for a score)
+  long long* d_sums = nullptr;
+  double* d_score_out = nullptr;
+  ScoreMeta* d_score_meta = nullptr;
+  uint32_t n_scores = 0;
+  std::vector<int32_t> score_shift;
+  std::vector<std::string> score_names;
   // burden results (vs_query_sample_burden): the regions x columns matrix in HBM (16 bytes per cell, row-major), the sum of its
   // `variants` (a device word the kernels add to), the column ids, and the matrix's page-locked host copy
   uint4* d_cells = nullptr;
@@ -291,8 +303,10 @@ constexpr int kKindMatrix = 10;  // ... of a genotype-matrix result: the rows of
 constexpr int kKindLd = 11;      // ... of an LD result: the rows of type 6, a table rows x window band of pair statistics instead of carrier lists
 constexpr int kKindGroups = 12;  // ... of a grouped-count result: the rows of type 6, a count record per row and sample group instead of carrier lists
 constexpr int kKindAssoc = 13;   // ... of an association-scan result: the rows of type 6, a score per row and trait instead of carrier lists
+constexpr int kKindScores = 14;  // ... of a per-sample score result: the rows of type 6, a columns x scores matrix of weighted dosage sums instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc;
+  return r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
+         r->kind == kKindScores;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
   if (r->kind == kKindCounts) return refuse_counts(what);
@@ -300,6 +314,8 @@ static int refuse_no_lists(const vs_result* r, const char* what) {
     return fail(VS_ERR_UNSUPPORTED, "%s: a grouped-count result holds counts per row and group, no carrier lists (vs_result_get_group_counts)", what);
   if (r->kind == kKindAssoc)
     return fail(VS_ERR_UNSUPPORTED, "%s: an association-scan result holds a score per row and trait, no carrier lists (vs_result_get_assoc_scan)", what);
+  if (r->kind == kKindScores)
+    return fail(VS_ERR_UNSUPPORTED, "%s: a per-sample score result holds a score per sample and weight column, no carrier lists (vs_result_get_sample_scores)", what);
   if (r->kind == kKindLd)
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD result holds a rows x window band of pair statistics, no carrier lists (vs_result_get_ld_band)", what);
   if (r->kind == kKindMatrix)
@@ -1158,7 +1174,9 @@ static int capture_totals(vs_result* r) {
 // window and statistic.  Groups: `mask` is the label table (a byte per sample id, eight to a word), n_cols the number of groups.
 // Assoc: mask, rank and n_cols as for the matrix; `pheno` is the upload that travels with them -- Sy[8], Syy[8] as doubles, then the
 // phenotype table in column order, [column][Kp] float32 -- of pheno_words 8-byte words; the traits and the statistic.
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc };
+// Scores: mask, rank and n_cols as for the matrix; `weights` (host or device memory, weights_on_device) are n_weights x n_scores
+// float32 in report order; score_max_bits: per column the largest |w| as a float pattern, formed on the host from host weights.
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1169,6 +1187,10 @@ struct SharedReq {
   const uint64_t* pheno = nullptr;
   size_t pheno_words = 0;
   uint32_t n_traits = 0, assoc_stat = 0;
+  const float* weights = nullptr;
+  uint64_t n_weights = 0;
+  uint32_t n_scores = 0, score_max_bits[kScoresMax] = {0, 0, 0, 0, 0, 0, 0, 0};
+  bool weights_on_device = false;
   bool window() const { return min_ac != 0 || max_ac != UINT32_MAX; }
 };
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
@@ -1438,7 +1460,7 @@ static int launch_ld(vs_index* idx, vs_result* r, const uint8_t* cells, const Sh
 //                      the second stream, with resident lists nothing | shared_columns  Counts: k_allele_counts over the table,
 //                      Groups: k_group_counts over the table, Assoc: k_allele_counts, then k_assoc_scan over the table
 //   shared_permute_out an unsorted batch's per-region arrays back in the caller's order
-//   shared_columns     Burden, Matrix, LD, behind the permutation -- the matrix's rows are the regions in the caller's order: k_allele_counts
+//   shared_columns     Burden, Matrix, LD, Scores, behind the permutation -- the matrix's rows are the regions in the caller's order: k_allele_counts
 //                      only under a window, k_sample_burden over (region, column tile) pairs and for regions longer than a chunk
 //                      k_burden_split_plan + the SPLIT launch | k_genotype_matrix over (block of table rows, column tile) pairs |
 //                      LD: k_allele_counts over the table, k_genotype_matrix into the temporary, k_ld_band over blocks of table rows
@@ -1455,7 +1477,7 @@ struct SharedCtx {
   ScratchBufs ld_tmp;   // an LD batch's temporary genotype matrix, apart from the rest: an enqueued batch keeps it only until it has finished
   // the consumer, asked once: Lists -- carrier lists in an arena (the result's or the resident one), may speculate, owns the handle's
   // type-6 hints; else a column request -- no arena, never speculative, hints untouched, the site of EVERY row (u_site).  Burden,
-  // Matrix and LD are consumed behind k_permute_out, Lists, Counts, Groups and Assoc in front of it
+  // Matrix, LD and Scores are consumed behind k_permute_out, Lists, Counts, Groups and Assoc in front of it
   const bool lists, behind_perm;
   // shared_setup: the decisions taken up front
   bool allow_async = false, async_submit = false, sort_first = false, plan_aside = false, resident = false, spec = false;
@@ -1485,7 +1507,7 @@ struct SharedCtx {
   uint8_t* ld_matrix = nullptr; // shared_tables: the temporary genotype matrix of an LD batch (ld_tmp)
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -1754,6 +1776,10 @@ static int shared_tables(SharedCtx& c) {
       VS_TRY(ralloc(r, d.A, &r->d_counts));
       VS_TRY(ralloc(r, (size_t)(d.A * q.n_traits), &r->d_scores));
       break;
+    case ReqKind::Scores:   // (the sums and what they are formed from wait for the number of reports: launch_scores)
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(ralloc(r, 1, &r->d_score_meta));
+      break;
     case ReqKind::Burden:
       VS_TRY(ralloc(r, d.A, &d.rows));
       if (q.window()) VS_TRY(ralloc(r, d.A, &r->d_counts));   // (the filter's input, made only under a window)
@@ -1884,7 +1910,8 @@ static int shared_expand(SharedCtx& c) {
 }
 // A column request's kernels between the result's own pair of events (vs_result_fill_ms).  Counts, Groups: one launch over the whole
 // table.  Assoc: k_allele_counts over the table, then k_assoc_scan.  Burden, Matrix, LD (behind the permutation): a burden filter's counts are inside the pair, and so are the three launches of
-// an LD batch: counts, temporary matrix, band.
+// an LD batch: counts, temporary matrix, band.  Scores (behind the permutation): launch_scores, with its one host wait inside the pair.
+static int launch_scores(SharedCtx& c);
 static int shared_columns(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
   if (!c.behind_perm && !r->d.A) return VS_OK;
@@ -1895,6 +1922,7 @@ static int shared_columns(SharedCtx& c) {
     launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
   HIP_TRY(hipGetLastError());
   if (c.req.kind == ReqKind::Assoc) VS_TRY(launch_assoc(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.d_pheno, c.req));
+  if (c.req.kind == ReqKind::Scores) VS_TRY(launch_scores(c));
   if (c.req.kind == ReqKind::Burden) VS_TRY(launch_burden(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.req, c.scratch));
   if (c.req.kind == ReqKind::LD) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
@@ -1903,6 +1931,106 @@ static int shared_columns(SharedCtx& c) {
   HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
   r->pending = true;
   c.fill_launches = 1;
+  return VS_OK;
+}
+
+// A score batch behind the permutation (the per-region arrays are in the caller's order).  The reports' offsets and -- for weights in
+// device memory -- their scale come back in ONE host wait (the batch is never speculative); the number of reports is held against
+// n_weights before anything else is allocated.  Then the integer weights per table row, the walk, the scores.
+template <uint32_t KP>
+static int launch_score_walk(vs_index* idx, const ScoreArgs& a, unsigned blocks, size_t lds) {
+  const bool sub = a.S != nullptr;
+  const void* fn = sub ? reinterpret_cast<const void*>(&k_sample_scores<KP, true>) : reinterpret_cast<const void*>(&k_sample_scores<KP, false>);
+  if (lds > (40 << 10)) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   // (beside 6 KiB of static LDS)
+  if (sub) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sample_scores<KP, true>), dim3(blocks), dim3(256), lds, idx->stream, idx->d, a);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sample_scores<KP, false>), dim3(blocks), dim3(256), lds, idx->stream, idx->d, a);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+static int launch_scores(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  const SharedReq& q = c.req;
+  const uint32_t K = q.n_scores, kp = score_pow2(K);
+  uint64_t* off = nullptr;
+  VS_TRY(dev_alloc(idx, (d.Q + 1) * 8, (void**)&off, &c.scratch.bufs));
+  HIP_TRY(hipMemsetAsync(r->d_score_meta, 0, sizeof(ScoreMeta), idx->stream));
+  hipLaunchKernelGGL(k_score_offsets, dim3(1), dim3(kScoreOffBlock), 0, idx->stream, (const uint64_t*)d.var_count, d.Q, off);
+  if (q.weights_on_device && q.n_weights)
+    hipLaunchKernelGGL(k_score_scale, dim3((unsigned)std::min<uint64_t>((q.n_weights + 255) / 256, 1024)), dim3(256), 0, idx->stream, q.weights, q.n_weights, K,
+                       r->d_score_meta);
+  HIP_TRY(hipGetLastError());
+  uint64_t N = 0;
+  ScoreMeta hm{};
+  HIP_TRY(hipMemcpyAsync(&N, off + d.Q, 8, hipMemcpyDeviceToHost, idx->stream));
+  HIP_TRY(hipMemcpyAsync(&hm, r->d_score_meta, sizeof(ScoreMeta), hipMemcpyDeviceToHost, idx->stream));
+  HIP_TRY(hipStreamSynchronize(idx->stream));
+  if (N != q.n_weights)
+    return fail(VS_ERR_ARG, "%llu rows of weights for the %llu rows the regions report: one row of weights per reported row, in report order",
+                (unsigned long long)q.n_weights, (unsigned long long)N);
+  if (N >= kScoreMaxReports)
+    return fail(VS_ERR_ARG, "%llu reported rows: a score batch takes fewer than 2^26 (the 64-bit sums could overflow beyond): split the batch", (unsigned long long)N);
+  if (hm.nonfinite) return fail(VS_ERR_ARG, "weight column %d holds a value that is not finite", __builtin_ctz(hm.nonfinite));
+  ScoreShift sh{};
+  r->score_shift.assign(K, 0);
+  for (uint32_t k = 0; k < K; ++k) {
+    const uint32_t bits = q.weights_on_device ? hm.max_bits[k] : q.score_max_bits[k];
+    float m;
+    memcpy(&m, &bits, 4);
+    int e = 0;
+    if (bits) { (void)std::frexp((double)m, &e); sh.f[k] = (int32_t)kScoreShift - e; }
+    r->score_shift[k] = sh.f[k];
+  }
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  const uint64_t cells = (uint64_t)q.n_cols * K;
+  const uint64_t need = (q.weights_on_device ? 0 : N * K * 4) + d.A * (8ull * kp + 4) + cells * 16;
+  if (need > cap)
+    return fail(VS_ERR_ARG, "a score batch of %llu reports x %u scores over %llu rows and %u columns takes %llu bytes, more than the limit of %llu MiB (option matrix_max_mib): split the batch",
+                (unsigned long long)N, K, (unsigned long long)d.A, q.n_cols, (unsigned long long)need, (unsigned long long)(cap >> 20));
+  VS_TRY(ralloc(r, (size_t)cells * 2, &r->d_sums));
+  r->d_score_out = reinterpret_cast<double*>(r->d_sums + cells);
+  HIP_TRY(hipMemsetAsync(r->d_sums, 0, cells * 8, idx->stream));
+  if (N && d.A) {
+    const float* dw = q.weights;
+    if (!q.weights_on_device) {
+      float* up = nullptr;
+      VS_TRY(dev_alloc(idx, N * K * 4, (void**)&up, &c.scratch.bufs));
+      HIP_TRY(hipMemcpyAsync(up, q.weights, N * K * 4, hipMemcpyHostToDevice, idx->stream));
+      dw = up;
+    }
+    long long* wq = nullptr;
+    const size_t wq_bytes = (size_t)d.A * kp * 8;
+    VS_TRY(dev_alloc(idx, wq_bytes + (size_t)d.A * 4, (void**)&wq, &c.scratch.bufs));
+    HIP_TRY(hipMemsetAsync(wq, 0, wq_bytes + (size_t)d.A * 4, idx->stream));
+    uint32_t* wn = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(wq) + wq_bytes);
+    ScoreWeightArgs wa{};
+    wa.rows = (const VariantRow*)d.rows; wa.var_begin = d.var_begin; wa.q_nvar = d.q_nvar; wa.off = off; wa.Q = d.Q; wa.N = N;
+    wa.w = dw; wa.K = K; wa.KP = kp; wa.shift = sh; wa.wq = wq; wa.wn = wn;
+    hipLaunchKernelGGL(k_score_weights, dim3((unsigned)std::min<uint64_t>((d.Q + 3) / 4, 8192)), dim3(256), 0, idx->stream, wa);
+    HIP_TRY(hipGetLastError());
+    ScoreArgs a{};
+    a.rows = (const VariantRow*)d.rows; a.u_site = c.u_site; a.A = d.A; a.U = c.U;
+    a.S = c.d_mask; a.S_rank = c.d_rank; a.s_words = c.d_mask ? q.words : 0;
+    a.n_cols = q.n_cols; a.K = K;
+    const uint32_t tile_max = kScoreTileBytes / (8 * kp);
+    a.tile_cols = std::min<uint32_t>(q.n_cols, idx->opts.score_tile_cols ? std::min(idx->opts.score_tile_cols, tile_max) : tile_max);
+    a.n_tiles = (q.n_cols + a.tile_cols - 1) / a.tile_cols;
+    a.chunk_rows = idx->opts.score_chunk ? idx->opts.score_chunk : kScoreChunkRows;
+    a.wq = wq; a.wn = wn; a.sums = reinterpret_cast<unsigned long long*>(r->d_sums); a.meta = r->d_score_meta;
+    const uint64_t chunks = (d.A + a.chunk_rows - 1) / a.chunk_rows;
+    if (chunks * a.n_tiles > 0x7FFFFFFFull)
+      return fail(VS_ERR_ARG, "batch too large for one launch (%llu row chunks x %u column tiles)", (unsigned long long)chunks, a.n_tiles);
+    const size_t lds = (size_t)a.tile_cols * kp * 8 + (size_t)a.s_words * 12;
+    const unsigned blocks = (unsigned)(chunks * a.n_tiles);
+    switch (kp) {
+      case 1: VS_TRY(launch_score_walk<1>(idx, a, blocks, lds)); break;
+      case 2: VS_TRY(launch_score_walk<2>(idx, a, blocks, lds)); break;
+      case 4: VS_TRY(launch_score_walk<4>(idx, a, blocks, lds)); break;
+      default: VS_TRY(launch_score_walk<8>(idx, a, blocks, lds)); break;
+    }
+  }
+  hipLaunchKernelGGL(k_score_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, idx->stream, (const long long*)r->d_sums, cells, K, sh, r->d_score_out);
+  HIP_TRY(hipGetLastError());
   return VS_OK;
 }
 
@@ -3173,6 +3301,12 @@ int vs_index_set_option(vs_index* idx, const char* key, int64_t value) {
   } else if (k == "assoc_lds_max_kib") {
     if (value < 0 || value > 128) return fail(VS_ERR_ARG, "assoc_lds_max_kib takes 0 (default: 32) or 1..128 KiB");
     o.assoc_lds_max_kib = (uint32_t)value;
+  } else if (k == "score_chunk") {
+    if (value != 0 && (value < 64 || value > 65536)) return fail(VS_ERR_ARG, "score_chunk takes 0 (default: %u) or 64..65536 rows", kScoreChunkRows);
+    o.score_chunk = (uint32_t)value;
+  } else if (k == "score_tile_cols") {
+    if (value != 0 && (value < 16 || value > 65536 || value % 16)) return fail(VS_ERR_ARG, "score_tile_cols takes 0 (default) or a multiple of 16 in 16..65536");
+    o.score_tile_cols = (uint32_t)value;
   } else if (k == "matrix_tile_cols") {
     if (value != 0 && (value < 16 || value > 65536 || value % 16)) return fail(VS_ERR_ARG, "matrix_tile_cols takes 0 (default) or a multiple of 16 in 16..65536");
     o.matrix_tile_cols = (uint32_t)value;
@@ -3399,6 +3533,59 @@ int vs_query_assoc_scan(vs_index* idx, const vs_region* regions, uint64_t n, con
     r->n_traits = n_traits; r->assoc_stat = stat;
     r->trait_sum = sy; r->trait_sumsq = syy;
     r->trait_names = names;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
+int vs_query_sample_scores(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, const float* weights, uint64_t n_weights,
+                           uint32_t n_scores, const char* const* score_names, vs_result** out) {
+  if (!idx || !out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
+  if (n == 0) return fail(VS_ERR_ARG, "a score batch needs at least one region");
+  if (n_scores == 0 || n_scores > VS_SCORES_MAX) return fail(VS_ERR_ARG, "%u scores (1 .. %u)", n_scores, VS_SCORES_MAX);
+  if (!weights && n_weights) return fail(VS_ERR_ARG, "null argument: a score batch takes a row of weights per reported row");
+  if (n_ids == 0) return fail(VS_ERR_ARG, "an empty list of samples: scores of nobody");
+  const uint32_t ns = idx->g.num_samples;
+  if (!sample_ids && n_ids != (uint64_t)ns - 1)
+    return fail(VS_ERR_ARG, "without sample ids the scores are the whole cohort's: %llu ids announced, %u samples", (unsigned long long)n_ids, ns - 1);
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));   // (VS_ERR_UNKNOWN_SAMPLE: id 0 or an id beyond the cohort)
+  if (sample_ids && cols.size() != n_ids) {
+    std::vector<uint64_t> seen(mask.size(), 0);
+    for (uint64_t i = 0; i < n_ids; ++i) {
+      const uint32_t id = sample_ids[i];
+      if (seen[id >> 6] >> (id & 63) & 1) return fail(VS_ERR_ARG, "sample id %u is listed twice: a sample has one row of scores", id);
+      seen[id >> 6] |= 1ull << (id & 63);
+    }
+  }
+  std::vector<std::string> names;
+  if (score_names)
+    for (uint32_t k = 0; k < n_scores; ++k) {
+      if (!score_names[k]) return fail(VS_ERR_ARG, "null name of score %u", k);
+      names.emplace_back(score_names[k]);
+      if (names.back().find_first_of("\t\n") != std::string::npos) return fail(VS_ERR_ARG, "the name of score %u holds a tab or a newline", k);
+    }
+  if (n_weights >= kScoreMaxReports)
+    return fail(VS_ERR_ARG, "%llu rows of weights: a score batch takes fewer than 2^26 reported rows (the 64-bit sums could overflow beyond): split the batch",
+                (unsigned long long)n_weights);
+  SharedReq req = column_request(ReqKind::Scores, mask, rank, cols.size());
+  req.weights = weights; req.n_weights = n_weights; req.n_scores = n_scores;
+  req.weights_on_device = weights && is_device_ptr(weights);
+  if (!req.weights_on_device)   // host weights: finite, and the largest |w| per column, before the device is asked
+    for (uint64_t i = 0; i < n_weights; ++i)
+      for (uint32_t k = 0; k < n_scores; ++k) {
+        uint32_t b;
+        memcpy(&b, weights + i * n_scores + k, 4);
+        b &= 0x7FFFFFFFu;
+        if (b >= 0x7F800000u) return fail(VS_ERR_ARG, "weight column %u holds a value that is not finite (row %llu)", k, (unsigned long long)i);
+        if (b > req.score_max_bits[k]) req.score_max_bits[k] = b;
+      }
+  if (mask.size() * 8 > kCountMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the score kernel's LDS (the whole cohort has no such limit)", ns);
+  return make_result(idx, kKindScores, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    r->n_scores = n_scores;
+    r->score_names = names;
     return run_column_batch(idx, regions, n, r, req);
   });
 }
@@ -3767,6 +3954,13 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
         for (uint64_t a = r->h_var_begin[q], e = a + r->h_nvar[q]; a < e; ++a) nc += c[a].x;
       r->n_carriers_kept = nc;
     }
+    if (r->kind == kKindScores) {   // the (report, carrier in S) pairs whose report has a nonzero weight: the walk's own word
+      VS_TRY(result_ready(r));
+      uint64_t nc = 0;
+      HIP_TRY(hipMemcpyAsync(&nc, &r->d_score_meta->n_pairs, 8, hipMemcpyDeviceToHost, idx->stream));
+      HIP_TRY(hipStreamSynchronize(idx->stream));
+      r->n_carriers_kept = nc;
+    }
     if (r->kind == kKindGroups) {   // the same over every group: a carrier in no group counts nowhere
       VS_TRY(fetch_region_meta(r));
       VS_TRY(counts_to_host(r));
@@ -4002,6 +4196,31 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
     if (len) *len = out.size();
     return VS_OK;
   }
+  if (r->kind == kKindScores) {   // the region's reported rows -- the rows the weights are keyed by, in report order
+    const VariantRow* rows;
+    if (r->have_headers) rows = r->h_rows.data() + a0;
+    else if (r->raw_rows) rows = r->raw_rows + a0;
+    else {
+      VS_TRY(fetch(idx, r->sl_rows, (const VariantRow*)r->d.rows + a0, (size_t)(a1 - a0)));
+      HIP_TRY(hipStreamSynchronize(idx->stream));
+      rows = r->sl_rows.data();
+    }
+    std::string& out = r->text;
+    out = "Pos\tRef\tAlt\n";
+    for (uint64_t a = a0; a < a1; ++a) {
+      const VariantRow& v = rows[a - a0];
+      if (v.count_flags & kRowDropped) continue;
+      out += std::to_string(v.pos);
+      out += '\t';
+      out.append(idx->seq_chars, v.ref_off, v.ref_len);
+      out += '\t';
+      out.append(idx->seq_chars, v.alt_off, v.alt_len);
+      out += '\n';
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
   if (r->kind == kKindCounts) {   // the region's reported rows with their counts
     VS_TRY(counts_to_host(r));
     const VariantRow* rows;
@@ -4162,6 +4381,22 @@ int vs_result_get_assoc_scan(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, u
   return VS_OK;
 }
 
+int vs_result_get_sample_scores(vs_result* r, uint64_t* n_cols, uint32_t* n_scores, const uint32_t** col_ids, const int32_t** shift, const int64_t** sums,
+                                const double** scores) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!sums && !scores) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindScores) return fail(VS_ERR_ARG, "not a per-sample score result (vs_query_sample_scores)");
+  const size_t cells = r->h_cols.size() * r->n_scores;
+  VS_TRY(array_to_host(r, r->d_sums, cells * 16, &r->cells_pin, "per-sample scores"));
+  if (sums) *sums = (const int64_t*)r->cells_pin.p;
+  if (scores) *scores = (const double*)((const int64_t*)r->cells_pin.p + cells);
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_scores) *n_scores = r->n_scores;
+  if (col_ids) *col_ids = r->h_cols.data();
+  if (shift) *shift = r->score_shift.data();
+  return VS_OK;
+}
+
 int vs_result_get_sample_burden(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, const uint32_t** col_ids, const vs_sample_burden** cells) {
   VS_TRY(result_enter(r, Want::Variants, true));
   if (!cells) return fail(VS_ERR_ARG, "null argument");
@@ -4262,6 +4497,15 @@ int vs_result_assoc_scan_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols
   if (n_cols) *n_cols = r->h_cols.size();
   if (n_traits) *n_traits = r->n_traits;
   if (stat) *stat = r->assoc_stat;
+  return VS_OK;
+}
+
+int vs_result_sample_scores_device(vs_result* r, uint64_t* n_cols, uint32_t* n_scores, const void** dev_sums, const void** dev_scores) {
+  VS_TRY(device_matrix_ready(r, dev_scores, kKindScores, "not a per-sample score result (vs_query_sample_scores)"));
+  *dev_scores = r->d_score_out;
+  if (dev_sums) *dev_sums = r->d_sums;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_scores) *n_scores = r->n_scores;
   return VS_OK;
 }
 

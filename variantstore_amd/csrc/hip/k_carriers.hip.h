@@ -1,4 +1,4 @@
-// k_carriers.hip.h -- how a column kernel (k_counts, k_group_counts, k_assoc, k_burden, k_matrix) reads the carriers of the rows of a type-6
+// k_carriers.hip.h -- how a column kernel (k_counts, k_group_counts, k_assoc, k_scores, k_burden, k_matrix) reads the carriers of the rows of a type-6
 // table: the one place, next to the expansion kernels, that knows how a carrier is stored.  No kernels here.
 // Part of kernels.hip.h (the kernel index is there).
 #pragma once

@@ -51,7 +51,7 @@
 //  k_pack_seq_regions    flags per region): site range + counts, or pieces + bytes of a sequence; k_bounds_from_records: the
 //                       receiving side (vs_query_expand_site_ranges)
 // k_find                Index::find batched
-// (k_carriers.hip.h)    no kernel: how the five column kernels below read the carriers of a table row -- the three storage forms of a
+// (k_carriers.hip.h)    no kernel: how the six column kernels below read the carriers of a table row -- the three storage forms of a
 //                       group of 8 carriers, a row's site parameters, the flat list of groups, the head of a dense class-row chunk,
 //                       sample id -> column; next to the expansion kernels the one place that knows how a carrier is stored
 // k_allele_counts       allele counts per row of a type-6 plan over a sample subset (vs_query_allele_counts: no reference
@@ -61,6 +61,11 @@
 // k_assoc_scan          every row scored against K phenotypes in one pass over its carriers: the carrier's K float32 values from a table
 //                       in LDS or L2, dosage x value summed in float64 in an order the table's layout fixes (segmented lane scans, no
 //                       floating-point atomic), rows x K cells stored once (vs_query_assoc_scan: no reference counterpart)
+// k_sample_scores       the transpose of that product: samples x K weighted dosage sums over the rows a batch reports, the weights
+//  k_score_scale         keyed by report order and quantised to 64-bit integers once per column (k_score_scale, k_score_offsets,
+//  k_score_offsets       k_score_weights), a (row chunk, column tile) per workgroup with the tile as int64 in LDS, integer atomics only:
+//  k_score_weights       every sum exact and order-free; k_score_finish forms the float64 scores (vs_query_sample_scores: no reference
+//  k_score_finish        counterpart)
 // k_sample_burden       the same counts along the other axis: a regions x samples matrix over each region's reported rows
 //  k_burden_split_plan   (vs_query_sample_burden: no reference counterpart); the chunks of the regions too long for one workgroup
 // k_genotype_matrix     what both reduce: table rows x samples, a byte per call, each (row block, column tile) built in LDS and
@@ -83,6 +88,7 @@
 #include "k_counts.hip.h"
 #include "k_group_counts.hip.h"
 #include "k_assoc.hip.h"
+#include "k_scores.hip.h"
 #include "k_burden.hip.h"
 #include "k_matrix.hip.h"
 #include "k_ld.hip.h"
