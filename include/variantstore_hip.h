@@ -443,6 +443,52 @@ int vs_result_get_ld_band(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint
  * The engine has synchronised its stream when this returns: the caller needs no event. */
 int vs_result_ld_band_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* window, uint32_t* stat, const void** dev_counts,
                              const void** dev_band);
+/* Sample Gram matrix / GRM over regions: D^T D, the samples x samples product of the dosages -- what a GRM, kinship, IBS-type sharing
+ * and the PCA of a cohort start from, and the one product of the dosage matrix the other column queries leave out (D Y:
+ * vs_query_assoc_scan, D^T W: vs_query_sample_scores, the band of D D^T: vs_query_ld_band; no reference counterpart).  T, its rows, S
+ * and its n columns are those of vs_query_genotype_matrix over the same regions and sample_ids; A is the number of rows of T and
+ * d_v(s) = popcount(cell & 6) the dosage of table row v in column s.  Each table row counts once, however many regions report it;
+ * a row the duplicate rule dropped has an all-zero matrix row and an all-zero count record and adds nothing to any sum.
+ *   VS_GRAM_DOT   gram[i * n + j] = sum over v of d_v(i) * d_v(j), int64, exact: the full symmetric matrix, the diagonal sum d^2;
+ *                 and from the rows' count records over S (ac_v = alt_alleles of row v): col_weighted[i] = s_i = sum ac_v d_v(i)
+ *                 (int64), C = sum ac_v^2, H = sum ac_v (2 n - ac_v)
+ *   VS_GRAM_GRM   the same and VanRaden's first GRM, Z Z^T / 2 sum p (1 - p) with Z = D - 2 p and p_v = ac_v / 2 n, from exact
+ *                 integers: num_ij = n^2 gram_ij - n (s_i + s_j) + C in 128-bit integers, grm[i * n + j] = (double)(2 num_ij) /
+ *                 (double)H as float64 -- each conversion rounds once, to nearest even, one division follows -- and 0.0 when
+ *                 H == 0 (every row monomorphic in S, no rows, n = 1 gives num = 0 everywhere)
+ * Nothing floating-point is ever summed, and the integer sums are formed with integer atomics: the same call gives the same bytes.
+ * C and H are 64-bit sums: 4 A n^2 must stay below 2^63.
+ * `regions` and `sample_ids` as for vs_query_genotype_matrix.  Checked on the host, in this order, before the handle's device is
+ * asked for (a handle opened without a device reports them first and VS_ERR_NO_DEVICE otherwise): n == 0, sample_ids == NULL with
+ * n_ids != 0, non-NULL sample_ids with n_ids == 0, stat neither VS_GRAM_DOT nor VS_GRAM_GRM -> VS_ERR_ARG; id 0 or id >=
+ * num_samples -> VS_ERR_UNKNOWN_SAMPLE.  The products are formed from a temporary genotype matrix (rows x row_pitch bytes, not part
+ * of the result: it goes back to the handle's pool as an LD batch's does); the matrix and the n x n cells -- 8 bytes each, 16
+ * under VS_GRAM_GRM -- together may not exceed option "matrix_max_mib" MiB (default 32 GiB): beyond it the call is refused with
+ * VS_ERR_ARG once the plan has given the rows and before anything is allocated; the message names rows, columns and bytes.
+ * Option "gram_chunk": the table rows one workgroup of the product kernel sums before it adds its partial sums to the matrix,
+ * 64 .. 65536; 0 (default): by the batch's shape -- the multiple of 128 rows that gives about 256 workgroups over all pairs of
+ * 128-column tiles, at least 256 rows.  The sums are the same integers under every setting.
+ * Every batch size takes the batch pipeline; a Gram batch is never speculative and leaves the handle's type-6 state as it was.  The
+ * result holds the type-6 per-region arrays and variant table, no carrier arena, the counts and the matrices: vs_result_get_raw /
+ * vs_result_get_view with with_carriers = 0, vs_result_layout (arena and lists 0), vs_result_fill_ms (the batch's own kernels) and
+ * vs_result_totals (n_carriers = the nonzero cells of the temporary matrix) work; vs_result_format_region fails with
+ * VS_ERR_UNSUPPORTED (one matrix over the whole batch: there is no text per region), and so do with_carriers = 1, vs_result_digest,
+ * vs_result_pack_headers / _pack_regions and vs_comm_allgather_regions*; the other vs_result_get_* accessors fail with VS_ERR_ARG. */
+#define VS_GRAM_DOT 0u
+#define VS_GRAM_GRM 1u
+int vs_query_sample_gram(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t stat,
+                         vs_result** out);
+/* A Gram result copied into page-locked memory owned by the result: gram[i * n_cols + j], grm[i * n_cols + j] (NULL under
+ * VS_GRAM_DOT), col_weighted[i], C and H, counts[v] the count record of table row v over S, col_ids[c] the sample id of column c.
+ * Every out-pointer but `gram` may be NULL.  VS_ERR_ARG on any other result. */
+int vs_result_get_sample_gram(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const uint32_t** col_ids,
+                              const vs_allele_counts** counts, const int64_t** gram, const double** grm, const int64_t** col_weighted,
+                              int64_t* C, int64_t* H);
+/* The same as it lies in HBM, valid until vs_result_free: n_cols x n_cols int64, n_cols x n_cols float64 (NULL under VS_GRAM_DOT),
+ * n_cols int64 with C and H right behind them, n_rows count records of 16 bytes.  The engine has synchronised its stream when this
+ * returns: the caller needs no event. */
+int vs_result_sample_gram_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const void** dev_counts,
+                                 const void** dev_gram, const void** dev_grm, const void** dev_col_weighted);
 
 /* host view of a sequence result: region i is chars[seq_begin[i] .. seq_begin[i+1]) */
 int vs_result_get_sequences(vs_result* r, uint64_t* n_regions, const uint8_t** region_flags, const uint64_t** seq_begin,
@@ -649,6 +695,8 @@ void vs_comm_destroy(vs_comm* c);
  *                     vs_query_assoc_scan stages in LDS, in KiB; a larger one is read through global memory.  0 (default): 32; else
  *                     1..128 (small cohorts reach the global form with 1).  The scores are the same bytes in either form
  *   "score_chunk"     table rows one workgroup of the score kernel walks (vs_query_sample_scores).  0 (default): 4096; else 64..65536
+ *   "gram_chunk"      table rows one workgroup of the Gram kernel sums (vs_query_sample_gram).  0 (default): by the batch's shape,
+ *                     about 256 workgroups; else 64..65536.  The sums are the same integers under every setting
  *   "score_tile_cols" columns of a workgroup's tile of the score kernel: 0 (default): all that 64 KiB of int64 cells hold,
  *                     65536 / (8 Kp); else a multiple of 16 in 16..65536, held to that (small cohorts reach tile boundaries with it).
  *                     The sums are the same integers under every setting of the two

@@ -486,6 +486,51 @@ class QueryResult:
             out.append({"a": (int(pa), ra, aa), "b": (int(pb), rb, ab), "value": int(v) if dot else float(v)})
         return out
 
+    GRAM_STATS = {"dot": 0, "grm": 1}   # VS_GRAM_DOT, VS_GRAM_GRM
+
+    def sample_gram(self):
+        """A Gram result (VariantStore.sample_gram) as numpy arrays: `gram` ((n, n) int64: gram[i, j] = the sum over the table rows of
+        the dosage products of columns i and j; symmetric, the diagonal the sum of squares), `grm` ((n, n) float64 under stat "grm":
+        VanRaden's first GRM formed from exact integers; None under "dot"), `col_weighted` (int64[n]: s_i = the sum of a row's
+        alt_alleles over the samples times the row's dosage in column i), `C` and `H` (Python ints: the sums of ac^2 and of
+        ac (2 n - ac) over the rows), `counts` (structured as for allele_counts: the count record of every table row over the
+        query's samples), `columns` (uint32[n], the sample ids), `stat`, the table's `rows` and per region `row_begin` and
+        `row_count`.  Copies, valid after the result is closed."""
+        a, c = C.c_uint64(), C.c_uint64()
+        st = C.c_uint32()
+        cols = C.POINTER(C.c_uint32)()
+        cnt = C.POINTER(_lib.AlleleCounts)()
+        pg, ps = C.POINTER(C.c_int64)(), C.POINTER(C.c_int64)()
+        pd = C.POINTER(C.c_double)()
+        cc, hh = C.c_int64(), C.c_int64()
+        _check(self._lib.vs_result_get_sample_gram(self._h, C.byref(a), C.byref(c), C.byref(st), C.byref(cols), C.byref(cnt), C.byref(pg),
+                                                   C.byref(pd), C.byref(ps), C.byref(cc), C.byref(hh)), "vs_result_get_sample_gram")
+        na, nc = int(a.value), int(c.value)
+        stat = "grm" if st.value == self.GRAM_STATS["grm"] else "dot"
+        gram = np.ctypeslib.as_array(pg, shape=(nc, nc)).copy()
+        grm = np.ctypeslib.as_array(pd, shape=(nc, nc)).copy() if stat == "grm" else None
+        colw = np.ctypeslib.as_array(ps, shape=(nc,)).copy()
+        if na:
+            counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint8)), shape=(na * 16,)).view(self.COUNT_DTYPE).copy()
+        else:
+            counts = np.zeros(0, self.COUNT_DTYPE)
+        raw = self.raw(with_carriers=False)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "columns": np.ctypeslib.as_array(cols, shape=(nc,)).copy(), "stat": stat, "counts": counts, "gram": gram, "grm": grm,
+                "col_weighted": colw, "C": int(cc.value), "H": int(hh.value)}
+
+    def sample_gram_device(self):
+        """(gram address, grm address, col_weighted address, counts address, n_rows, n_cols, stat) of a Gram result as it lies in
+        this GPU's memory: n_cols x n_cols int64, n_cols x n_cols float64 (0 under "dot"), n_cols int64 with C and H right behind
+        them, n_rows count records of four uint32; complete when this returns and valid until the result is closed."""
+        a, c = C.c_uint64(), C.c_uint64()
+        st = C.c_uint32()
+        pc, pg, pd, ps = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_sample_gram_device(self._h, C.byref(a), C.byref(c), C.byref(st), C.byref(pc), C.byref(pg), C.byref(pd),
+                                                      C.byref(ps)), "vs_result_sample_gram_device")
+        return (int(pg.value or 0), int(pd.value or 0), int(ps.value or 0), int(pc.value or 0), int(a.value), int(c.value),
+                "grm" if st.value == self.GRAM_STATS["grm"] else "dot")
+
     def region_variants(self, q) -> List[Variant]:
         out = []
         for line in self.region_text(q).split("\n")[1:]:
@@ -803,6 +848,21 @@ class VariantStore:
             window = 0
         _check(self._lib.vs_query_ld_band(self._h, ptr, n, ids_ptr, n_ids, window, int(stat) & 0xFFFFFFFF, C.byref(h)),
                "vs_query_ld_band")
+        return QueryResult(self, h)
+
+    def sample_gram(self, regions, samples=None, stat="dot") -> QueryResult:
+        """Sample Gram matrix over regions (vs_query_sample_gram): D^T D, the samples x samples products of the dosages over every
+        row of the variant table a type-6 batch over `regions` produces, for `samples` (names or ids, taken as a set; None: the
+        whole cohort).  `stat`: "dot" (the exact int64 products) or "grm" (the same and VanRaden's first GRM as float64, formed
+        from exact integers).  `regions` as for allele_counts.  Read the result with QueryResult.sample_gram / sample_gram_device."""
+        arr, ptr, n = _regions_array(regions)
+        h = C.c_void_p()
+        if isinstance(stat, str):
+            if stat.lower() not in QueryResult.GRAM_STATS:
+                raise ValueError(f"stat {stat!r}: 'dot' or 'grm'")
+            stat = QueryResult.GRAM_STATS[stat.lower()]
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        _check(self._lib.vs_query_sample_gram(self._h, ptr, n, ids_ptr, n_ids, int(stat) & 0xFFFFFFFF, C.byref(h)), "vs_query_sample_gram")
         return QueryResult(self, h)
 
     def assoc_scan(self, regions, traits, samples=None, stat="dot", trait_names=None) -> QueryResult:

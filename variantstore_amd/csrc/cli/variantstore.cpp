@@ -116,6 +116,7 @@ struct Args {
   uint32_t min_ac = 0, max_ac = UINT32_MAX;   // `burden`: the alternate-allele-count window of the rows that count
   uint32_t ld_window = 64;   // `ld`: every row against the next ld_window rows; --dot: dot products instead of r^2
   bool ld_dot = false;
+  bool gram_grm = false;      // `gram`: the GRM (float64) instead of the dosage products (int64)
   bool assoc_chi2 = false;   // `assoc`: the score test instead of the dot products
   uint32_t type = 0, mode = 0;
   uint64_t hops = 0;
@@ -1025,6 +1026,76 @@ int score_main(const Args& a) {
   return EXIT_SUCCESS;
 }
 
+// `variantstore gram`: the samples x samples Gram matrix of the regions' variant table (vs_query_sample_gram), or with --grm the GRM
+// formed from it.  Output: a header line of the sample names, then one line per sample -- its name and its row of the matrix.
+int gram_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore gram -p <output-prefix> -r <region> [-S <sample-name-file>] [--grm] [-o <outfile>] [--device <n>]\n\n"
+               "        For every pair of samples (of the whole cohort or of those named in the file) the sum, over the variants query\n"
+               "        type 6 reports in the regions (each once), of the product of their alternate-allele dosages; with --grm the\n"
+               "        genomic relationship matrix (VanRaden's first form) computed from those sums.\n";
+  return EXIT_FAILURE;
+}
+
+int gram_main(const Args& a) {
+  vs_index* idx = nullptr;
+  int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
+  if (rc != VS_OK) die(rc, "load");
+  std::vector<uint32_t> ids;
+  if (!a.samples_file.empty()) {
+    std::ifstream in(a.samples_file);
+    if (!in) { error("cannot open sample file " + a.samples_file); vs_index_close(idx); return EXIT_FAILURE; }
+    std::string line;
+    while (std::getline(in, line)) {
+      if (!line.empty() && line.back() == '\r') line.pop_back();
+      if (line.empty()) continue;
+      uint32_t sid = 0;
+      if (vs_index_sample_id(idx, line.c_str(), &sid) != VS_OK || sid == 0) {
+        error("Sample not found: " + line);
+        vs_index_close(idx);
+        return EXIT_FAILURE;
+      }
+      ids.push_back(sid);
+    }
+    if (ids.empty()) { error("no sample names in " + a.samples_file); vs_index_close(idx); return EXIT_FAILURE; }
+  }
+  std::vector<vs_region> batch;
+  for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
+  vs_result* res = nullptr;
+  rc = vs_query_sample_gram(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.gram_grm ? VS_GRAM_GRM : VS_GRAM_DOT, &res);
+  if (rc != VS_OK) die(rc, "gram");
+  uint64_t n_cols = 0;
+  const uint32_t* cols = nullptr;
+  const int64_t* gram = nullptr;
+  const double* grm = nullptr;
+  rc = vs_result_get_sample_gram(res, nullptr, &n_cols, nullptr, &cols, nullptr, &gram, &grm, nullptr, nullptr, nullptr);
+  if (rc != VS_OK) die(rc, "gram");
+  std::ofstream file;
+  if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
+  std::ostream& out = a.outfile.empty() ? std::cout : file;
+  out << "Sample";
+  for (uint64_t c = 0; c < n_cols; ++c) {
+    const char* nm = vs_index_sample_name(idx, cols[c]);
+    out << '\t' << (nm ? nm : "?");
+  }
+  out << '\n';
+  char num[48];
+  for (uint64_t i = 0; i < n_cols; ++i) {
+    const char* nm = vs_index_sample_name(idx, cols[i]);
+    out << (nm ? nm : "?");
+    for (uint64_t j = 0; j < n_cols; ++j) {
+      if (a.gram_grm) snprintf(num, sizeof num, "\t%.17g", grm[i * n_cols + j]);
+      else snprintf(num, sizeof num, "\t%lld", (long long)gram[i * n_cols + j]);
+      out << num;
+    }
+    out << '\n';
+  }
+  out.flush();
+  vs_result_free(res);
+  vs_index_close(idx);
+  return EXIT_SUCCESS;
+}
+
 int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
@@ -1112,12 +1183,13 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "score") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "score" || a.cmd == "gram") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "ld" && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "ld" && f == "--dot") a.ld_dot = true;
+      else if (a.cmd == "gram" && f == "--grm") a.gram_grm = true;
       else if (f == "-r" || f == "--region") a.region = need(i);
       else if (a.cmd == "groups" && (f == "-G" || f == "--groups")) a.groups_file = need(i);
       else if (a.cmd == "assoc" && (f == "-P" || f == "--phenotypes")) a.pheno_file = need(i);
@@ -1156,6 +1228,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "ld") {
     if (a.prefix.empty() || a.region.empty()) return ld_usage();
     return counts_main(a, /*burden=*/false, /*genotypes=*/false, /*ld=*/true);
+  }
+  if (a.cmd == "gram") {
+    if (a.prefix.empty() || a.region.empty()) return gram_usage();
+    return gram_main(a);
   }
   if (a.cmd == "construct") {
     if (a.ref.empty() || a.vcf.empty() || a.prefix.empty()) return usage();
