@@ -76,6 +76,64 @@ def write_random_cohort(dirpath, seed, ref_len=4000, n_rows=120, n_samples=6, sa
     return fasta, vcf, sample_names
 
 
+SAT_REF_LEN = 20_000
+
+
+def write_saturated_cohort(dirpath, n_samples, seed, rows=150, two_alt=True, extremes=False):
+    """FASTA + VCF (sat.fa, sat.vcf) of `rows` rows 120 - 129 bases apart (SNPs, 6 % insertions, 6 % deletions, 3 % two-ALT rows, a
+    tenth of the carriers' calls moved on to 1|1, 1/0 or 1/1): row k is carried by all but k / 8 % 6 samples when k % 8 == 0 (rows 0,
+    48, 96, 144: by every sample), else by a share of the samples drawn from [0.75, 0.99]; rows 4, 20, 36, ... keep only their
+    carriers among samples 1..2015 (1,500 - 2,000 of them: dense at every threshold, and no carrier in the upper half of the row).
+    VariantStore.synthetic caps an allele's frequency at 0.5, so rows like these exist only as VCF text.
+
+    The options draw no random number, so the defaults and the rows they leave alone are the same bytes whatever they are:
+      two_alt=False   the two-ALT records are written as SNPs of their first ALT
+      extremes=True   the calls of rows 1..6 (single-ALT then) are overwritten: everybody 1/1, 1|1, 0|1, 1/0; everybody a carrier
+                      but sample 1; everybody but the last sample."""
+    rng = np.random.default_rng(seed)
+    ref = "".join(BASES[i] for i in rng.integers(0, 4, size=SAT_REF_LEN))
+    names = [f"S{i + 1:05d}" for i in range(n_samples)]
+    one_alt = np.array(["0|0", "1|0", "0|1", "1|1", "1/0", "1/1"])
+    two_alt_calls = np.array(["0|0", "1|0", "0|2", "2|1", "1|1", "2/2"])
+    fasta, vcf = os.path.join(dirpath, "sat.fa"), os.path.join(dirpath, "sat.vcf")
+    with open(fasta, "w") as f:
+        f.write(">c1 saturated\n")
+        for i in range(0, SAT_REF_LEN, 60):
+            f.write(ref[i:i + 60] + "\n")
+    with open(vcf, "w") as f:
+        f.write("##fileformat=VCFv4.1\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n")
+        f.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join(names) + "\n")
+        p = 100
+        for k in range(rows):
+            p += int(rng.integers(120, 130))
+            r0, t, calls = ref[p - 1], rng.random(), one_alt
+            if t < 0.06:
+                refa, alt = r0, r0 + "".join(BASES[i] for i in rng.integers(0, 4, size=int(rng.integers(1, 5))))
+            elif t < 0.12:
+                refa, alt = ref[p - 1:p + int(rng.integers(1, 5))], r0
+            else:
+                others = [b for b in BASES if b != r0]
+                refa, alt = r0, others[int(rng.integers(0, 3))]
+                if t < 0.15 and two_alt and not (extremes and 1 <= k <= 6):
+                    alt, calls = alt + "," + [b for b in others if b != alt][0], two_alt_calls
+            if k % 8 == 0:
+                carrier = np.ones(n_samples, bool)
+                carrier[rng.choice(n_samples, size=(k // 8) % 6, replace=False)] = False
+            else:
+                carrier = rng.random(n_samples) < rng.uniform(0.75, 0.99)
+                if k % 16 == 4:
+                    carrier[2015:] = False                            # ids 1..2015 only: nothing for the second half of a row
+            call = np.where(carrier, rng.integers(1, 4, size=n_samples), 0)
+            call[carrier & (rng.random(n_samples) < 0.1)] += 2        # calls 1..3 -> 3..5: still carriers
+            if extremes and 1 <= k <= 4:
+                call[:] = (5, 3, 2, 4)[k - 1]                         # 1/1, 1|1, 0|1, 1/0
+            elif extremes and k in (5, 6):
+                call = np.where(call == 0, 1 + np.arange(n_samples) % 5, call)
+                call[0 if k == 5 else n_samples - 1] = 0
+            f.write(f"c1\t{p}\t.\t{refa}\t{alt}\t99\t.\t.\tGT\t" + "\t".join(calls[call]) + "\n")
+    return fasta, vcf
+
+
 def random_regions(rng, ref_len, n, max_len=600):
     """Random regions plus the edge shapes the reference's driver can be handed."""
     out = []

@@ -8,7 +8,7 @@ Two cohorts per width:
   spread     VariantStore.synthetic with af_exponent 3.5: listed, medium and dense variants together.  (3.5, not 2.5: at these
              widths the rarest allele of 2.5 still has ~26 carriers, and VS_LIST_MAX=0 is to send rows of 1..8 carriers through the
              row paths.)
-  saturated  VCF text written here (seed 4400 + S): the synthetic generator caps an allele's frequency at 0.5 -- at most ~76 % of the
+  saturated  VCF text of helpers.write_saturated_cohort (seed 4400 + S): the synthetic generator caps an allele's frequency at 0.5 -- at most ~76 % of the
              samples carry a variant -- so rows carried by 75 - 99 % of the samples, and every eighth row by all but 0..5 of them, are
              written out and opened with from_vcf."""
 import os
@@ -16,7 +16,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import BASES
+from helpers import write_saturated_cohort
 from oracle.oracle import Oracle
 from test_gpu_allele_counts import _check_texts
 from test_gpu_genotype_matrix import _check as _check_matrix, _parse as _parse_matrix
@@ -31,7 +31,6 @@ WIDTHS = [3968, 4031, 4032, 4095]       # wpc 63 / 63 / 64 / 64; last row word: 
 SPREAD_SEED = {3968: 611, 4031: 612, 4032: 613, 4095: 614}
 SPREAD_KW = dict(ref_length=60_000, num_variants=300, first_pos=100, frac_ins=0.06, frac_del=0.06, frac_multi=0.03, max_indel=4,
                  af_exponent=3.5)
-SAT_ROWS, SAT_REF_LEN = 150, 20_000
 
 
 class _Memo:
@@ -51,56 +50,12 @@ class _Memo:
         return self._t4[(x, y, sample)]
 
 
-def _write_saturated_cohort(dirpath, n_samples, seed):
-    """FASTA + VCF of SAT_ROWS rows 120 - 129 bases apart (SNPs, 6 % insertions, 6 % deletions, 3 % two-ALT rows, a tenth of the
-    carriers' calls moved on to 1|1, 1/0 or 1/1): row k is carried by all but k / 8 % 6 samples when k % 8 == 0 (rows 0, 48, 96,
-    144: by every sample), else by a share of the samples drawn from [0.75, 0.99]; rows 4, 20, 36, ... keep only their carriers among
-    samples 1..2015 (1,500 - 2,000 of them: dense at every threshold, and no carrier in the upper half of the row)."""
-    rng = np.random.default_rng(seed)
-    ref = "".join(BASES[i] for i in rng.integers(0, 4, size=SAT_REF_LEN))
-    names = [f"S{i + 1:05d}" for i in range(n_samples)]
-    one_alt = np.array(["0|0", "1|0", "0|1", "1|1", "1/0", "1/1"])
-    two_alt = np.array(["0|0", "1|0", "0|2", "2|1", "1|1", "2/2"])
-    fasta, vcf = os.path.join(dirpath, "sat.fa"), os.path.join(dirpath, "sat.vcf")
-    with open(fasta, "w") as f:
-        f.write(">c1 saturated\n")
-        for i in range(0, SAT_REF_LEN, 60):
-            f.write(ref[i:i + 60] + "\n")
-    with open(vcf, "w") as f:
-        f.write("##fileformat=VCFv4.1\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n")
-        f.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join(names) + "\n")
-        p = 100
-        for k in range(SAT_ROWS):
-            p += int(rng.integers(120, 130))
-            r0, t, calls = ref[p - 1], rng.random(), one_alt
-            if t < 0.06:
-                refa, alt = r0, r0 + "".join(BASES[i] for i in rng.integers(0, 4, size=int(rng.integers(1, 5))))
-            elif t < 0.12:
-                refa, alt = ref[p - 1:p + int(rng.integers(1, 5))], r0
-            else:
-                others = [b for b in BASES if b != r0]
-                refa, alt = r0, others[int(rng.integers(0, 3))]
-                if t < 0.15:
-                    alt, calls = alt + "," + [b for b in others if b != alt][0], two_alt
-            if k % 8 == 0:
-                carrier = np.ones(n_samples, bool)
-                carrier[rng.choice(n_samples, size=(k // 8) % 6, replace=False)] = False
-            else:
-                carrier = rng.random(n_samples) < rng.uniform(0.75, 0.99)
-                if k % 16 == 4:
-                    carrier[2015:] = False                            # ids 1..2015 only: nothing for the second half of a row
-            call = np.where(carrier, rng.integers(1, 4, size=n_samples), 0)
-            call[carrier & (rng.random(n_samples) < 0.1)] += 2        # calls 1..3 -> 3..5: still carriers
-            f.write(f"c1\t{p}\t.\t{refa}\t{alt}\t99\t.\t.\tGT\t" + "\t".join(calls[call]) + "\n")
-    return fasta, vcf
-
-
 def _open(n_samples, profile, tmp_path):
     """(store, memoised oracle) of one cohort, after the asserts every case makes about its width."""
     if profile == "spread":
         vs = VariantStore.synthetic(device=0, num_samples=n_samples, seed=SPREAD_SEED[n_samples], **SPREAD_KW)
     else:
-        fasta, vcf = _write_saturated_cohort(str(tmp_path), n_samples, 4400 + n_samples)
+        fasta, vcf = write_saturated_cohort(str(tmp_path), n_samples, 4400 + n_samples)
         vs = VariantStore.from_vcf(fasta, vcf, device=0)
     info = vs.info()
     assert info.num_samples - 1 == n_samples and info.use_bit_vector

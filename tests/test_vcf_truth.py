@@ -12,7 +12,7 @@ import random
 import pytest
 
 import vcf_truth as vt
-from helpers import write_random_cohort
+from helpers import SAT_REF_LEN, write_random_cohort, write_saturated_cohort
 from oracle.oracle import Oracle
 from variantstore_amd import VariantStore
 
@@ -87,6 +87,78 @@ def test_oracle_on_the_constructed_graph_matches_the_vcf_text(seed, kw, tmp_path
         assert orc.query_sample_from_ref(x, y, smp)[1] == want, (x, y, smp)
     if seed == 204:
         assert vs.info().use_bit_vector == 0
+
+
+def _text_oracle_regions(tx, seed):
+    """About 80 regions whose ends are midpoints between records: random spans of 1 .. 12 gaps, the whole reference, a region
+    between two neighbouring records, one before the first record, one behind the last, empty ones."""
+    edges = tx.midpoints(SAT_REF_LEN)
+    rng = random.Random(seed)
+    out = [(1, SAT_REF_LEN + 1), (edges[10], edges[11]), (1, edges[0]), (edges[-2] + 40, SAT_REF_LEN + 1), (edges[5], edges[5]),
+           (edges[7] - 3, edges[7] + 3)]
+    while len(out) < 80:
+        a = rng.randrange(len(edges) - 1)
+        out.append((edges[a], edges[min(len(edges) - 1, a + rng.randint(1, 12))]))
+    return out
+
+
+@pytest.mark.parametrize("n_samples", [63, 64, 200])
+def test_text_oracle_equals_the_oracle_on_a_saturated_cohort(n_samples, tmp_path):
+    """TextOracle (the VCF text alone) and Oracle (the graph the constructor built) return equal (n, early_out, text) on every
+    region the text answers; a region that ends inside a record's span is refused.  When a GPU test against TextOracle fails,
+    this test says which side is wrong."""
+    fasta, vcf = write_saturated_cohort(str(tmp_path), n_samples, 4400 + n_samples, two_alt=False, extremes=True)
+    tx = vt.TextOracle(vcf)
+    assert len(tx.rows) == len(tx.recs) == 150
+    ns = n_samples
+    assert tx.rows[1].count("(1/1) ") == ns and tx.rows[2].count("(1|1) ") == ns and tx.rows[3].count("(0|1) ") == ns
+    assert tx.rows[4].count("(1/0) ") == ns and tx.rows[5].count(") ") == ns - 1 and tx.rows[6].count(") ") == ns - 1
+    assert "S00001(" not in tx.rows[5] and f"S{ns:05d}(" not in tx.rows[6] and f"S{ns:05d}(" in tx.rows[5]
+    vs = VariantStore.from_vcf(fasta, vcf, device=-1)
+    plain = os.path.join(tmp_path, "sat.plain")
+    vs.export_plain(plain)
+    orc = Oracle(plain)
+    regions = _text_oracle_regions(tx, n_samples)
+    seen = set()
+    for x, y in regions:
+        want = orc.get_var_in_ref(x, y)
+        assert tx.get_var_in_ref(x, y) == want, (x, y)
+        seen.add((want[0] > 0, want[1]))
+    assert seen == {(True, False), (False, True)}     # regions with rows and early-outs, and nothing else
+    assert tx.get_var_in_ref(1, SAT_REF_LEN + 1)[0] == 150
+    pos, ref = tx.recs[20][0], tx.recs[20][1]
+    for bad in (pos, pos + len(ref), pos - 1 - 7, pos + len(ref) + 7):
+        with pytest.raises(ValueError):
+            tx.get_var_in_ref(1, bad)
+        with pytest.raises(ValueError):
+            tx.get_var_in_ref(bad, SAT_REF_LEN + 1)
+    tx.get_var_in_ref(1, pos - 1 - 8)                  # the nearest ends that are answered
+    tx.get_var_in_ref(pos + len(ref) + 8, SAT_REF_LEN + 1)
+    vs.close()
+
+
+def test_saturated_writer_options_leave_the_other_rows_alone(tmp_path):
+    """two_alt and extremes draw no random number: every line they do not rewrite is the default's, byte for byte."""
+    lines = {}
+    for key, kw in (("default", {}), ("snp", dict(two_alt=False)), ("both", dict(two_alt=False, extremes=True)), ("ext", dict(extremes=True))):
+        d = os.path.join(tmp_path, key)
+        os.makedirs(d)
+        _fa, vcf = write_saturated_cohort(d, 64, 4464, **kw)
+        with open(vcf) as f:
+            lines[key] = f.read().split("\n")
+    multi = [i for i, l in enumerate(lines["default"]) if not l.startswith("#") and l and "," in l.split("\t")[4]]
+    assert multi and not any("," in l.split("\t")[4] for l in lines["snp"] if l and not l.startswith("#"))
+    first = next(i for i, l in enumerate(lines["default"]) if l.startswith("c1"))
+    extreme = set(range(first + 1, first + 7))
+    for i, l in enumerate(lines["default"]):
+        if i not in multi:
+            assert lines["snp"][i] == l
+        if i not in extreme:
+            assert lines["ext"][i] == l and lines["both"][i] == lines["snp"][i]
+    short = os.path.join(tmp_path, "short")
+    os.makedirs(short)
+    with open(write_saturated_cohort(short, 64, 4464, rows=12)[1]) as f:
+        assert f.read().split("\n")[:-1] == lines["default"][:first + 12]
 
 
 @pytest.mark.gpu

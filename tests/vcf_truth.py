@@ -154,3 +154,52 @@ def sample_sequence(ref, names, recs, sample, x, y):
             at = hi
     pieces.append(ref[at - 1:y - 1])
     return "".join(pieces)
+
+
+class TextOracle:
+    """What oracle.oracle.Oracle.get_var_in_ref returns -- (n, early_out, text) -- worked out from the VCF text alone (read_vcf and
+    expected_type6_rows: no constructor, no graph), for a cohort every record of which is isolated and predicted.
+
+    It answers only regions [x, y) whose two ends lie at least MARGIN bases from every record's span (_span): such a region
+    reports exactly the records whose span lies inside it, in position order, and the rule for what a region's edge includes never
+    enters.  Any other region raises ValueError.  early_out is the reference's is_empty(): with both ends that far from every
+    vertex boundary it holds exactly when no record lies inside.  The answers are kept, as the GPU tests' _Memo keeps them."""
+    MARGIN = 8
+    HEADER = "Pos\tRef\tAlt\tSamples\n"
+
+    def __init__(self, vcf_path):
+        self.names, self.recs = read_vcf(vcf_path)
+        assert isolated_records(self.recs) == list(range(len(self.recs))), "a record is not isolated"
+        exp = expected_type6_rows(self.names, self.recs)
+        assert [i for i, _t in exp] == list(range(len(self.recs))), "a record is not predicted from the text"
+        self.rows = [t for _i, t in exp]
+        self.spans = [_span(r) for r in self.recs]
+        assert all(a[1] < b[0] for a, b in zip(self.spans, self.spans[1:])), "the records are not in position order"
+        self._memo = {}
+
+    def _clear(self, p):
+        return all(p <= lo - self.MARGIN or p >= hi + self.MARGIN for lo, hi in self.spans)
+
+    def inside(self, x, y):
+        """The records (indexes) that region [x, y) reports."""
+        if not (self._clear(x) and self._clear(y)):
+            raise ValueError(f"region {x}:{y} ends within {self.MARGIN} bases of a record: not answered from the text")
+        return [i for i, (lo, hi) in enumerate(self.spans) if x < lo and hi < y]
+
+    def get_var_in_ref(self, x, y):
+        if (x, y) not in self._memo:
+            hit = self.inside(x, y)
+            self._memo[(x, y)] = (len(hit), not hit, self.HEADER + "".join(self.rows[i] for i in hit))
+        return self._memo[(x, y)]
+
+    def midpoints(self, ref_length):
+        edges = gap_midpoints(self.recs, ref_length)
+        assert all(self._clear(p) for p in edges)
+        return edges
+
+
+def gap_midpoints(recs, ref_length):
+    """Region ends that lie in the gaps of position-ordered records: edges[0] in front of the first record, edges[k] between
+    records k - 1 and k, edges[len(recs)] = ref_length + 1 behind the last one.  [edges[i], edges[j]) reports records i .. j - 1."""
+    spans = [_span(r) for r in recs]
+    return [spans[0][0] // 2] + [(a[1] + b[0]) // 2 for a, b in zip(spans, spans[1:])] + [ref_length + 1]
