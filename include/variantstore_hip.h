@@ -489,6 +489,63 @@ int vs_result_get_sample_gram(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, 
  * returns: the caller needs no event. */
 int vs_result_sample_gram_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const void** dev_counts,
                                  const void** dev_gram, const void** dev_grm, const void** dev_col_weighted);
+/* Pairwise IBS counts and KING kinship over regions: for every pair of samples how often both are heterozygous, how often they are
+ * opposite homozygotes (IBS0) and how often they agree (IBS2) -- what KING and `plink2 --make-king-table` start from to say who is
+ * related to whom and which samples are duplicates (no reference counterpart).  These are counts of genotype STATES: they cannot be
+ * recovered from the Gram matrix of vs_query_sample_gram, one cell of which mixes het x het, het x hom and hom x hom.
+ * T, its A rows, the column set S and its n columns are those of vs_query_genotype_matrix over the same regions and sample_ids.
+ * The dosage is d_v(s) = popcount(cell & 6).  Each table row counts once, however many regions report it.  For a row v let
+ *   h_v(s) = [d_v(s) == 1],   a_v(s) = [d_v(s) == 2],   c_v(s) = [d_v(s) > 0].
+ * Three primitive matrices are accumulated; they are int64, n x n, full and symmetric:
+ *   het_het[i * n + j]      = sum over v of h_v(i) h_v(j)
+ *   hom_hom[i * n + j]      = sum over v of a_v(i) a_v(j)
+ *   carrier_both[i * n + j] = sum over v of c_v(i) c_v(j)
+ * Their diagonals are the per-sample totals nh_i, na_i and nc_i = nh_i + na_i.
+ * A row the duplicate rule dropped (bit 31 of its count_flags) has an all-zero matrix row: it adds nothing to the primitives and is
+ * not a site.  n_used = A - dropped rows.
+ * From the primitives, in exact int64:
+ *   ibs0[i * n + j] = na_i + na_j - 2 hom_hom - (carrier_both - het_het - hom_hom)     the opposite homozygotes, {0, 2}
+ *   ibs2[i * n + j] = n_used - nc_i - nc_j + carrier_both + het_het + hom_hom           equal dosage, 0/0 included
+ *   ibs1            = n_used - ibs0 - ibs2                                               not stored
+ *   VS_IBS_COUNTS   the five matrices above and n_used
+ *   VS_IBS_KING     the same and king[i * n + j] = (double)(het_het - 2 ibs0) / (double)(nh_i + nh_j) as float64, 0.0 where
+ *                   nh_i + nh_j == 0: the KING-robust between-family estimator, in the form with the sum of the two het counts in
+ *                   the denominator; the diagonal is 0.5 wherever nh_i > 0.  Numerator and denominator are integers below 2^53:
+ *                   each converts exactly and one division follows
+ * Nothing floating-point is ever summed, and the integer sums are formed with integer atomics: the same call gives the same bytes.
+ * `regions` and `sample_ids` as for vs_query_genotype_matrix.  Checked on the host, in this order, before the handle's device is
+ * asked for (a handle opened without a device reports them first and VS_ERR_NO_DEVICE otherwise): n == 0, sample_ids == NULL with
+ * n_ids != 0, non-NULL sample_ids with n_ids == 0, stat neither VS_IBS_COUNTS nor VS_IBS_KING -> VS_ERR_ARG; id 0 or id >=
+ * num_samples -> VS_ERR_UNKNOWN_SAMPLE.  The products are formed from a temporary genotype matrix (rows x row_pitch bytes, not part
+ * of the result: it goes back to the handle's pool as an LD or Gram batch's does); the matrix and the n x n cells -- 40 bytes each,
+ * 48 under VS_IBS_KING -- together may not exceed option "matrix_max_mib" MiB (default 32 GiB): beyond it the call is refused with
+ * VS_ERR_ARG once the plan has given the rows and before anything is allocated; the message names rows, columns and bytes.
+ * Option "ibs_chunk": the table rows one workgroup of the product kernel sums before it adds its partial sums to the matrices,
+ * 64 .. 65536; 0 (default): by the batch's shape -- the multiple of 128 rows that gives about 128 workgroups over all pairs of
+ * 128-column tiles, at least 256 rows, the table's rows spread evenly over the chunks.  The sums are the same integers under every
+ * setting.
+ * Every batch size takes the batch pipeline; an IBS batch is never speculative and leaves the handle's type-6 state as it was.  The
+ * result holds the type-6 per-region arrays and variant table, no carrier arena, the counts and the matrices: vs_result_get_raw /
+ * vs_result_get_view with with_carriers = 0, vs_result_layout (arena and lists 0), vs_result_fill_ms (the batch's own kernels) and
+ * vs_result_totals (n_carriers = the nonzero cells of the temporary matrix) work; vs_result_format_region fails with
+ * VS_ERR_UNSUPPORTED (matrices over the whole batch: there is no text per region), and so do with_carriers = 1, vs_result_digest,
+ * vs_result_pack_headers / _pack_regions and vs_comm_allgather_regions*; the other vs_result_get_* accessors fail with VS_ERR_ARG. */
+#define VS_IBS_COUNTS 0u
+#define VS_IBS_KING 1u
+int vs_query_sample_ibs(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t stat,
+                        vs_result** out);
+/* An IBS result copied into page-locked memory owned by the result: the five matrices [i * n_cols + j], king (NULL under
+ * VS_IBS_COUNTS), n_used, counts[v] the count record of table row v over S, col_ids[c] the sample id of column c.
+ * Every out-pointer but `het_het` may be NULL.  VS_ERR_ARG on any other result. */
+int vs_result_get_sample_ibs(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const uint32_t** col_ids,
+                             const vs_allele_counts** counts, const int64_t** het_het, const int64_t** hom_hom, const int64_t** carrier_both,
+                             const int64_t** ibs0, const int64_t** ibs2, const double** king, int64_t* n_used);
+/* The same as it lies in HBM, valid until vs_result_free: dev_matrices is five n_cols x n_cols int64 matrices one behind the other
+ * -- het_het, hom_hom, carrier_both, ibs0, ibs2 -- with n_used (one int64) right behind them; dev_king n_cols x n_cols float64 (NULL
+ * under VS_IBS_COUNTS); n_rows count records of 16 bytes.  The engine has synchronised its stream when this returns: the caller
+ * needs no event. */
+int vs_result_sample_ibs_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const void** dev_counts,
+                                const void** dev_matrices, const void** dev_king);
 
 /* host view of a sequence result: region i is chars[seq_begin[i] .. seq_begin[i+1]) */
 int vs_result_get_sequences(vs_result* r, uint64_t* n_regions, const uint8_t** region_flags, const uint64_t** seq_begin,
@@ -697,6 +754,8 @@ void vs_comm_destroy(vs_comm* c);
  *   "score_chunk"     table rows one workgroup of the score kernel walks (vs_query_sample_scores).  0 (default): 4096; else 64..65536
  *   "gram_chunk"      table rows one workgroup of the Gram kernel sums (vs_query_sample_gram).  0 (default): by the batch's shape,
  *                     about 256 workgroups; else 64..65536.  The sums are the same integers under every setting
+ *   "ibs_chunk"       table rows one workgroup of the IBS kernel sums (vs_query_sample_ibs).  0 (default): by the batch's shape,
+ *                     about 128 workgroups; else 64..65536.  The sums are the same integers under every setting
  *   "score_tile_cols" columns of a workgroup's tile of the score kernel: 0 (default): all that 64 KiB of int64 cells hold,
  *                     65536 / (8 Kp); else a multiple of 16 in 16..65536, held to that (small cohorts reach tile boundaries with it).
  *                     The sums are the same integers under every setting of the two

@@ -531,6 +531,55 @@ class QueryResult:
         return (int(pg.value or 0), int(pd.value or 0), int(ps.value or 0), int(pc.value or 0), int(a.value), int(c.value),
                 "grm" if st.value == self.GRAM_STATS["grm"] else "dot")
 
+    IBS_STATS = {"counts": 0, "king": 1}   # VS_IBS_COUNTS, VS_IBS_KING
+
+    def sample_ibs(self):
+        """An IBS result (VariantStore.sample_ibs) as numpy arrays.  (n, n) int64, symmetric, counted over the table rows the
+        duplicate rule kept: `het_het` (both heterozygous), `hom_hom` (both hom-alt), `carrier_both` (both carriers), `ibs0`
+        (opposite homozygotes), `ibs2` (equal dosage, 0/0 included) and `ibs1` = n_used - ibs0 - ibs2, derived here; `n_used` (a
+        Python int: the table's rows minus those the duplicate rule dropped), `het` (int64[n]: the diagonal of het_het, a sample's
+        heterozygous calls), `king` ((n, n) float64 under stat "king": (het_het - 2 ibs0) / (het_i + het_j), 0.0 where the
+        denominator is 0; None under "counts"), `counts` (structured as for allele_counts: the count record of every table row over
+        the query's samples), `columns` (uint32[n], the sample ids), `stat`, the table's `rows` and per region `row_begin` and
+        `row_count`.  Copies, valid after the result is closed."""
+        a, c = C.c_uint64(), C.c_uint64()
+        st = C.c_uint32()
+        cols = C.POINTER(C.c_uint32)()
+        cnt = C.POINTER(_lib.AlleleCounts)()
+        pm = [C.POINTER(C.c_int64)() for _ in range(5)]
+        pk = C.POINTER(C.c_double)()
+        nu = C.c_int64()
+        _check(self._lib.vs_result_get_sample_ibs(self._h, C.byref(a), C.byref(c), C.byref(st), C.byref(cols), C.byref(cnt), C.byref(pm[0]),
+                                                  C.byref(pm[1]), C.byref(pm[2]), C.byref(pm[3]), C.byref(pm[4]), C.byref(pk), C.byref(nu)),
+               "vs_result_get_sample_ibs")
+        na, nc = int(a.value), int(c.value)
+        stat = "king" if st.value == self.IBS_STATS["king"] else "counts"
+        hh, aa, cb, ibs0, ibs2 = (np.ctypeslib.as_array(p, shape=(nc, nc)).copy() for p in pm)
+        king = np.ctypeslib.as_array(pk, shape=(nc, nc)).copy() if stat == "king" else None
+        if na:
+            counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint8)), shape=(na * 16,)).view(self.COUNT_DTYPE).copy()
+        else:
+            counts = np.zeros(0, self.COUNT_DTYPE)
+        raw = self.raw(with_carriers=False)
+        n_used = int(nu.value)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "columns": np.ctypeslib.as_array(cols, shape=(nc,)).copy(), "stat": stat, "counts": counts, "het_het": hh, "hom_hom": aa,
+                "carrier_both": cb, "ibs0": ibs0, "ibs1": n_used - ibs0 - ibs2, "ibs2": ibs2, "n_used": n_used, "het": np.diagonal(hh).copy(),
+                "king": king}
+
+    def sample_ibs_device(self):
+        """(matrices address, king address, counts address, n_rows, n_cols, stat) of an IBS result as it lies in this GPU's memory:
+        five n_cols x n_cols int64 matrices one behind the other -- het_het, hom_hom, carrier_both, ibs0, ibs2 -- with n_used (one
+        int64) right behind them, n_cols x n_cols float64 (0 under "counts"), n_rows count records of four uint32; complete when
+        this returns and valid until the result is closed."""
+        a, c = C.c_uint64(), C.c_uint64()
+        st = C.c_uint32()
+        pc, pm, pk = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_sample_ibs_device(self._h, C.byref(a), C.byref(c), C.byref(st), C.byref(pc), C.byref(pm), C.byref(pk)),
+               "vs_result_sample_ibs_device")
+        return (int(pm.value or 0), int(pk.value or 0), int(pc.value or 0), int(a.value), int(c.value),
+                "king" if st.value == self.IBS_STATS["king"] else "counts")
+
     def region_variants(self, q) -> List[Variant]:
         out = []
         for line in self.region_text(q).split("\n")[1:]:
@@ -863,6 +912,22 @@ class VariantStore:
             stat = QueryResult.GRAM_STATS[stat.lower()]
         ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
         _check(self._lib.vs_query_sample_gram(self._h, ptr, n, ids_ptr, n_ids, int(stat) & 0xFFFFFFFF, C.byref(h)), "vs_query_sample_gram")
+        return QueryResult(self, h)
+
+    def sample_ibs(self, regions, samples=None, stat="counts") -> QueryResult:
+        """Pairwise IBS counts over regions (vs_query_sample_ibs): for every pair of `samples` (names or ids, taken as a set; None:
+        the whole cohort) how often, over the rows of the variant table a type-6 batch over `regions` produces, both are
+        heterozygous, both hom-alt, both carriers, opposite homozygotes (IBS0) and equal (IBS2) -- exact int64.  `stat`: "counts"
+        or "king" (the same and the KING-robust kinship as float64, formed from exact integers).  `regions` as for allele_counts.
+        Read the result with QueryResult.sample_ibs / sample_ibs_device."""
+        arr, ptr, n = _regions_array(regions)
+        h = C.c_void_p()
+        if isinstance(stat, str):
+            if stat.lower() not in QueryResult.IBS_STATS:
+                raise ValueError(f"stat {stat!r}: 'counts' or 'king'")
+            stat = QueryResult.IBS_STATS[stat.lower()]
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        _check(self._lib.vs_query_sample_ibs(self._h, ptr, n, ids_ptr, n_ids, int(stat) & 0xFFFFFFFF, C.byref(h)), "vs_query_sample_ibs")
         return QueryResult(self, h)
 
     def assoc_scan(self, regions, traits, samples=None, stat="dot", trait_names=None) -> QueryResult:

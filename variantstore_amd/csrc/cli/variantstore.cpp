@@ -32,6 +32,7 @@
 #include <signal.h>
 #include <unistd.h>
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -117,6 +118,9 @@ struct Args {
   uint32_t ld_window = 64;   // `ld`: every row against the next ld_window rows; --dot: dot products instead of r^2
   bool ld_dot = false;
   bool gram_grm = false;      // `gram`: the GRM (float64) instead of the dosage products (int64)
+  bool ibs_king = false;      // `ibs`: the kinship column beside the counts; --min-kinship X: only pairs with kinship >= X (implies --king)
+  bool ibs_have_min = false;
+  double ibs_min_kinship = 0.0;
   bool assoc_chi2 = false;   // `assoc`: the score test instead of the dot products
   uint32_t type = 0, mode = 0;
   uint64_t hops = 0;
@@ -1026,6 +1030,23 @@ int score_main(const Args& a) {
   return EXIT_SUCCESS;
 }
 
+// The ids of the samples named in a file, one name a line (`gram`, `ibs`): false, with the error reported, when the file cannot be
+// read, names nobody or names a sample the index does not have.
+bool read_sample_ids(vs_index* idx, const std::string& path, std::vector<uint32_t>& ids) {
+  std::ifstream in(path);
+  if (!in) { error("cannot open sample file " + path); return false; }
+  std::string line;
+  while (std::getline(in, line)) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty()) continue;
+    uint32_t sid = 0;
+    if (vs_index_sample_id(idx, line.c_str(), &sid) != VS_OK || sid == 0) { error("Sample not found: " + line); return false; }
+    ids.push_back(sid);
+  }
+  if (ids.empty()) { error("no sample names in " + path); return false; }
+  return true;
+}
+
 // `variantstore gram`: the samples x samples Gram matrix of the regions' variant table (vs_query_sample_gram), or with --grm the GRM
 // formed from it.  Output: a header line of the sample names, then one line per sample -- its name and its row of the matrix.
 int gram_usage() {
@@ -1042,23 +1063,7 @@ int gram_main(const Args& a) {
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
   if (rc != VS_OK) die(rc, "load");
   std::vector<uint32_t> ids;
-  if (!a.samples_file.empty()) {
-    std::ifstream in(a.samples_file);
-    if (!in) { error("cannot open sample file " + a.samples_file); vs_index_close(idx); return EXIT_FAILURE; }
-    std::string line;
-    while (std::getline(in, line)) {
-      if (!line.empty() && line.back() == '\r') line.pop_back();
-      if (line.empty()) continue;
-      uint32_t sid = 0;
-      if (vs_index_sample_id(idx, line.c_str(), &sid) != VS_OK || sid == 0) {
-        error("Sample not found: " + line);
-        vs_index_close(idx);
-        return EXIT_FAILURE;
-      }
-      ids.push_back(sid);
-    }
-    if (ids.empty()) { error("no sample names in " + a.samples_file); vs_index_close(idx); return EXIT_FAILURE; }
-  }
+  if (!a.samples_file.empty() && !read_sample_ids(idx, a.samples_file, ids)) { vs_index_close(idx); return EXIT_FAILURE; }
   std::vector<vs_region> batch;
   for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
   vs_result* res = nullptr;
@@ -1089,6 +1094,61 @@ int gram_main(const Args& a) {
       out << num;
     }
     out << '\n';
+  }
+  out.flush();
+  vs_result_free(res);
+  vs_index_close(idx);
+  return EXIT_SUCCESS;
+}
+
+// `variantstore ibs`: the pairwise genotype-state counts of the regions' variant table (vs_query_sample_ibs) as a pair table, what
+// users of KING's .kin0 expect: a header line, then one line per pair i < j in column order.
+int ibs_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore ibs -p <output-prefix> -r <region> [-S <sample-name-file>] [--king] [--min-kinship <x>] [-o <outfile>] [--device <n>]\n\n"
+               "        For every pair of samples (of the whole cohort or of those named in the file), over the variants query type 6\n"
+               "        reports in the regions (each once): N, the variants counted; HetHet, both heterozygous; IBS0, opposite\n"
+               "        homozygotes; IBS1; IBS2, equal genotypes.  With --king the KING-robust kinship as a last column; with\n"
+               "        --min-kinship <x> (implies --king) only the pairs whose kinship is at least x.\n";
+  return EXIT_FAILURE;
+}
+
+int ibs_main(const Args& a) {
+  vs_index* idx = nullptr;
+  int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
+  if (rc != VS_OK) die(rc, "load");
+  std::vector<uint32_t> ids;
+  if (!a.samples_file.empty() && !read_sample_ids(idx, a.samples_file, ids)) { vs_index_close(idx); return EXIT_FAILURE; }
+  std::vector<vs_region> batch;
+  for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
+  const bool king = a.ibs_king || a.ibs_have_min;
+  vs_result* res = nullptr;
+  rc = vs_query_sample_ibs(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), king ? VS_IBS_KING : VS_IBS_COUNTS, &res);
+  if (rc != VS_OK) die(rc, "ibs");
+  uint64_t n = 0;
+  const uint32_t* cols = nullptr;
+  const int64_t *hh = nullptr, *ibs0 = nullptr, *ibs2 = nullptr;
+  const double* kin = nullptr;
+  int64_t n_used = 0;
+  rc = vs_result_get_sample_ibs(res, nullptr, &n, nullptr, &cols, nullptr, &hh, nullptr, nullptr, &ibs0, &ibs2, &kin, &n_used);
+  if (rc != VS_OK) die(rc, "ibs");
+  std::ofstream file;
+  if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
+  std::ostream& out = a.outfile.empty() ? std::cout : file;
+  out << "ID1\tID2\tN\tHetHet\tIBS0\tIBS1\tIBS2" << (king ? "\tKinship" : "") << '\n';
+  char num[160];
+  for (uint64_t i = 0; i < n; ++i) {
+    const char* ni = vs_index_sample_name(idx, cols[i]);
+    for (uint64_t j = i + 1; j < n; ++j) {
+      const uint64_t c = i * n + j;
+      if (a.ibs_have_min && !(kin[c] >= a.ibs_min_kinship)) continue;
+      const char* nj = vs_index_sample_name(idx, cols[j]);
+      snprintf(num, sizeof num, "\t%lld\t%lld\t%lld\t%lld\t%lld", (long long)n_used, (long long)hh[c], (long long)ibs0[c],
+               (long long)(n_used - ibs0[c] - ibs2[c]), (long long)ibs2[c]);
+      out << (ni ? ni : "?") << '\t' << (nj ? nj : "?") << num;
+      if (king) { snprintf(num, sizeof num, "\t%.17g", kin[c]); out << num; }
+      out << '\n';
+    }
   }
   out.flush();
   vs_result_free(res);
@@ -1183,13 +1243,21 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "score" || a.cmd == "gram") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "score" || a.cmd == "gram" || a.cmd == "ibs") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "ld" && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "ld" && f == "--dot") a.ld_dot = true;
       else if (a.cmd == "gram" && f == "--grm") a.gram_grm = true;
+      else if (a.cmd == "ibs" && f == "--king") a.ibs_king = true;
+      else if (a.cmd == "ibs" && f == "--min-kinship") {
+        const std::string v = need(i);
+        char* end = nullptr;
+        a.ibs_min_kinship = strtod(v.c_str(), &end);
+        if (v.empty() || *end != '\0' || std::isnan(a.ibs_min_kinship)) { std::cerr << "--min-kinship takes a number, not '" << v << "'\n"; return ibs_usage(); }
+        a.ibs_have_min = true;
+      }
       else if (f == "-r" || f == "--region") a.region = need(i);
       else if (a.cmd == "groups" && (f == "-G" || f == "--groups")) a.groups_file = need(i);
       else if (a.cmd == "assoc" && (f == "-P" || f == "--phenotypes")) a.pheno_file = need(i);
@@ -1232,6 +1300,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "gram") {
     if (a.prefix.empty() || a.region.empty()) return gram_usage();
     return gram_main(a);
+  }
+  if (a.cmd == "ibs") {
+    if (a.prefix.empty() || a.region.empty()) return ibs_usage();
+    return ibs_main(a);
   }
   if (a.cmd == "construct") {
     if (a.ref.empty() || a.vcf.empty() || a.prefix.empty()) return usage();

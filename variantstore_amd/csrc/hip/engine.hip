@@ -93,6 +93,7 @@ struct EngineOpts {
   uint32_t score_chunk = 0;     // table rows one workgroup of k_sample_scores walks: 0 = kScoreChunkRows, else 64..65536
   uint32_t score_tile_cols = 0; // column tile of k_sample_scores: 0 = all a 64 KiB tile holds, 65536 / (8 Kp); else a multiple of 16, held to that
   uint32_t gram_chunk = 0;      // table rows one workgroup of k_sample_gram sums: 0 = by the batch's shape (gram_chunk_rows), else 64..65536
+  uint32_t ibs_chunk = 0;       // table rows one workgroup of k_sample_ibs sums: 0 = by the batch's shape (ibs_chunk_rows), else 64..65536
   uint32_t matrix_tile_cols = 0;   // column tile of the matrix kernel: 0 = kMatrixTileCols, else a multiple of 16 in 16..65536
   int fill_mode = 0;            // shared expansion: 0 one launch, 2 split (lists + rows, then the dense sites: what a profiler wants to see apart)
   uint32_t fill_dense_k = 16;   // dense sites per wave of k_fill_dense: 8 / 16 / 32 / 64
@@ -244,7 +245,7 @@ struct vs_result {
   const uint8_t* raw_arena = nullptr;   // NULL: carriers not copied
   int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts;
                  // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts; kKindAssoc: association scan;
-                 // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM
+                 // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM; kKindIbs: pairwise IBS counts / KING kinship
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -293,6 +294,12 @@ struct vs_result {
   long long* d_gram = nullptr;
   size_t gram_grm_off = 0, gram_words = 0;
   uint32_t gram_stat = 0;
+  // IBS results (vs_query_sample_ibs): one buffer of 8-byte words in HBM -- het_het, hom_hom, carrier_both, ibs0, ibs2 ([n x n] int64
+  // each), n_used, the nonzero cells of the (temporary) genotype matrix (d_cell_total, two words), then from ibs_king_off on king
+  // [n x n] float64 under VS_IBS_KING -- copied to cells_pin in one piece; counts and column ids as for a Gram result
+  long long* d_ibs = nullptr;
+  size_t ibs_king_off = 0, ibs_words = 0;
+  uint32_t ibs_stat = 0;
   // sequence results (query types 2 and 3)
   DevSeqResult sq{};
   uint64_t seq_bytes = 0;
@@ -312,8 +319,9 @@ constexpr int kKindGroups = 12;  // ... of a grouped-count result: the rows of t
 constexpr int kKindAssoc = 13;   // ... of an association-scan result: the rows of type 6, a score per row and trait instead of carrier lists
 constexpr int kKindScores = 14;  // ... of a per-sample score result: the rows of type 6, a columns x scores matrix of weighted dosage sums instead of carrier lists
 constexpr int kKindGram = 15;    // ... of a Gram result: the rows of type 6, a samples x samples matrix of dosage products instead of carrier lists
+constexpr int kKindIbs = 16;     // ... of an IBS result: the rows of type 6, samples x samples matrices of genotype-state counts instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
+  return r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
          r->kind == kKindScores;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
@@ -326,6 +334,8 @@ static int refuse_no_lists(const vs_result* r, const char* what) {
     return fail(VS_ERR_UNSUPPORTED, "%s: a per-sample score result holds a score per sample and weight column, no carrier lists (vs_result_get_sample_scores)", what);
   if (r->kind == kKindGram)
     return fail(VS_ERR_UNSUPPORTED, "%s: a Gram result holds a samples x samples matrix of dosage products, no carrier lists (vs_result_get_sample_gram)", what);
+  if (r->kind == kKindIbs)
+    return fail(VS_ERR_UNSUPPORTED, "%s: an IBS result holds samples x samples matrices of genotype-state counts, no carrier lists (vs_result_get_sample_ibs)", what);
   if (r->kind == kKindLd)
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD result holds a rows x window band of pair statistics, no carrier lists (vs_result_get_ld_band)", what);
   if (r->kind == kKindMatrix)
@@ -1186,15 +1196,15 @@ static int capture_totals(vs_result* r) {
 // phenotype table in column order, [column][Kp] float32 -- of pheno_words 8-byte words; the traits and the statistic.
 // Scores: mask, rank and n_cols as for the matrix; `weights` (host or device memory, weights_on_device) are n_weights x n_scores
 // float32 in report order; score_max_bits: per column the largest |w| as a float pattern, formed on the host from host weights.
-// Gram: mask, rank and n_cols as for the matrix; the statistic.
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram };
+// Gram, Ibs: mask, rank and n_cols as for the matrix; the statistic.
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
   uint32_t words = 0;
   const uint32_t* rank = nullptr;
   uint32_t n_cols = 0, min_ac = 0, max_ac = UINT32_MAX;
-  uint32_t ld_window = 0, ld_stat = 0, gram_stat = 0;
+  uint32_t ld_window = 0, ld_stat = 0, gram_stat = 0, ibs_stat = 0;
   const uint64_t* pheno = nullptr;
   size_t pheno_words = 0;
   uint32_t n_traits = 0, assoc_stat = 0;
@@ -1498,9 +1508,57 @@ static int launch_gram(vs_index* idx, vs_result* r, const uint8_t* cells, const 
   return VS_OK;
 }
 
+// Table rows per workgroup of k_sample_ibs.  Option ibs_chunk, or by the batch's shape as gram_chunk_rows: the chunk that gives about
+// kIbsBlocksWanted workgroups over all tile pairs, a multiple of kGramK, at least 2 kGramK and at most kIbsChunkMax -- and then the
+// table's rows spread evenly over that number of chunks, so that the last chunk is not a short one the others wait for.
+static uint32_t ibs_chunk_rows(const vs_index* idx, uint64_t A, uint32_t n_pairs) {
+  if (idx->opts.ibs_chunk) return idx->opts.ibs_chunk;
+  const uint64_t per = (A * n_pairs + kIbsBlocksWanted - 1) / kIbsBlocksWanted;
+  const uint64_t rows = std::min<uint64_t>(kIbsChunkMax, std::max<uint64_t>(2 * kGramK, (per + kGramK - 1) / kGramK * kGramK));
+  const uint64_t chunks = (A + rows - 1) / rows;
+  return (uint32_t)std::max<uint64_t>(2 * kGramK, ((A + chunks - 1) / chunks + kGramK - 1) / kGramK * kGramK);
+}
+
+// The IBS matrices of a batch from its temporary genotype matrix: the three primitives and n_used cleared, k_ibs_n_used over the
+// table's rows, k_sample_ibs over (tile pair, row chunk), k_ibs_finish over the cells.  (launch_matrix, in front of this, has
+// cleared and filled d_cell_total.)
+static int launch_ibs(vs_index* idx, vs_result* r, const uint8_t* cells, uint64_t U, const SharedReq& iq) {
+  const DevResult& d = r->d;
+  const uint64_t n = iq.n_cols, nn = n * n;
+  const bool king = iq.ibs_stat == VS_IBS_KING;
+  if (!d.A) {   // an empty table: all-zero matrices, n_used = 0
+    HIP_TRY(hipMemsetAsync(r->d_ibs, 0, (size_t)(5 * nn + 1) * 8, idx->stream));
+    if (king) HIP_TRY(hipMemsetAsync(r->d_ibs + r->ibs_king_off, 0, (size_t)nn * 8, idx->stream));
+    return VS_OK;
+  }
+  HIP_TRY(hipMemsetAsync(r->d_ibs, 0, (size_t)(3 * nn) * 8, idx->stream));
+  HIP_TRY(hipMemsetAsync(r->d_ibs + 5 * nn, 0, 8, idx->stream));
+  IbsArgs a{};
+  a.m.cells = cells; a.m.A = d.A; a.m.pitch = (uint32_t)r->mx_pitch; a.m.n_cols = iq.n_cols;
+  a.m.n_tiles = (iq.n_cols + kGramTile - 1) / kGramTile;
+  const uint64_t pairs = (uint64_t)a.m.n_tiles * (a.m.n_tiles + 1) / 2;
+  if (pairs > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu tile pairs)", (unsigned long long)pairs);
+  a.m.n_pairs = (uint32_t)pairs;
+  a.m.chunk = ibs_chunk_rows(idx, d.A, a.m.n_pairs);
+  a.rows = (const VariantRow*)d.rows; a.U = U;
+  a.het_het = reinterpret_cast<unsigned long long*>(r->d_ibs);
+  a.ibs0 = r->d_ibs + 3 * nn;
+  a.n_used = reinterpret_cast<unsigned long long*>(r->d_ibs + 5 * nn);
+  a.king = king ? reinterpret_cast<double*>(r->d_ibs + r->ibs_king_off) : nullptr;
+  const uint64_t chunks = (d.A + a.m.chunk - 1) / a.m.chunk, blocks = chunks * pairs;
+  const uint64_t ublocks = std::min<uint64_t>((d.A + 1023) / 1024, 1024), fblocks = (nn + 255) / 256;
+  if (blocks > 0x7FFFFFFFull || fblocks > 0x7FFFFFFFull)
+    return fail(VS_ERR_ARG, "batch too large for one launch (%llu row chunks x %llu tile pairs)", (unsigned long long)chunks, (unsigned long long)pairs);
+  hipLaunchKernelGGL(k_ibs_n_used, dim3((unsigned)ublocks), dim3(256), 0, idx->stream, a);
+  hipLaunchKernelGGL(k_sample_ibs, dim3((unsigned)blocks), dim3(256), kGramLds, idx->stream, a);
+  hipLaunchKernelGGL(k_ibs_finish, dim3((unsigned)fblocks), dim3(256), 0, idx->stream, a);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Query type 6 over a batch whose regions SHARE rows and carrier lists (every batch of more than 64 regions unless option
-// share_lists is 0), and every count, grouped-count, burden, genotype-matrix, LD and Gram batch: the same plan and rows, another consumer (SharedReq).
+// share_lists is 0), and every count, grouped-count, burden, genotype-matrix, LD, Gram and IBS batch: the same plan and rows, another consumer (SharedReq).
 // Like the private-row batches further down it runs as stages over a context, each a function that reads only what the
 // stages before it left in the SharedCtx:
 //   shared_setup       per-region arrays, regions / mask / ranks on the device, the decisions taken up front, the plan's temporaries
@@ -1521,7 +1579,8 @@ static int launch_gram(vs_index* idx, vs_result* r, const uint8_t* cells, const 
 //                      only under a window, k_sample_burden over (region, column tile) pairs and for regions longer than a chunk
 //                      k_burden_split_plan + the SPLIT launch | k_genotype_matrix over (block of table rows, column tile) pairs |
 //                      LD: k_allele_counts over the table, k_genotype_matrix into the temporary, k_ld_band over blocks of table rows |
-//                      Gram: the same two, then k_sample_gram, k_gram_moments and (GRM) k_gram_finish (launch_gram)
+//                      Gram: the same two, then k_sample_gram, k_gram_moments and (GRM) k_gram_finish (launch_gram) |
+//                      Ibs: the same two, then k_ibs_n_used, k_sample_ibs and k_ibs_finish (launch_ibs)
 //   shared_finish      enqueued: the completion event | synchronous: k_post_done, a word in mapped host memory, the host spins on it
 // A column request is never speculative, has no arena, and leaves the handle's type-6 state (size hints, sort hint) as it found
 // it: count batches interleaved with type-6 batches change none of theirs.
@@ -1532,7 +1591,7 @@ struct SharedCtx {
   uint64_t n;
   const SharedReq& req;
   ScratchBufs scratch;
-  ScratchBufs ld_tmp;   // an LD or Gram batch's temporary genotype matrix, apart from the rest: an enqueued batch keeps it only until it has finished
+  ScratchBufs ld_tmp;   // an LD, Gram or IBS batch's temporary genotype matrix, apart from the rest: an enqueued batch keeps it only until it has finished
   // the consumer, asked once: Lists -- carrier lists in an arena (the result's or the resident one), may speculate, owns the handle's
   // type-6 hints; else a column request -- no arena, never speculative, hints untouched, the site of EVERY row (u_site).  Burden,
   // Matrix, LD and Scores are consumed behind k_permute_out, Lists, Counts, Groups and Assoc in front of it
@@ -1565,7 +1624,7 @@ struct SharedCtx {
   uint8_t* ld_matrix = nullptr; // shared_tables: the temporary genotype matrix of an LD batch (ld_tmp)
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -1808,6 +1867,21 @@ static int gram_fits(SharedCtx& c) {
               (unsigned long long)(r->d.A * r->mx_pitch + cell_bytes), (unsigned long long)(r->d.A * r->mx_pitch), (unsigned long long)cell_bytes, c.req.n_cols,
               c.req.n_cols, (unsigned long long)(cap >> 20));
 }
+// An IBS batch: the temporary matrix and the n x n cells -- five int64 matrices, 40 bytes a cell, 48 under VS_IBS_KING -- together,
+// under the same limit.
+static int ibs_fits(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  r->mx_pitch = ((uint64_t)c.req.n_cols + 15) & ~15ull;
+  const uint64_t n = c.req.n_cols, cell_bytes = n * n * (c.req.ibs_stat == VS_IBS_KING ? 48ull : 40ull);
+  if (cell_bytes <= cap && r->d.A <= (cap - cell_bytes) / r->mx_pitch) return VS_OK;
+  (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+  (void)hipStreamSynchronize(idx->stream);
+  return fail(VS_ERR_ARG, "IBS matrices of %llu rows x %u columns take %llu bytes (%llu of the genotype matrix they are formed from, %llu of the %u x %u cells), "
+              "more than the limit of %llu MiB (option matrix_max_mib): split the batch or the samples", (unsigned long long)r->d.A, c.req.n_cols,
+              (unsigned long long)(r->d.A * r->mx_pitch + cell_bytes), (unsigned long long)(r->d.A * r->mx_pitch), (unsigned long long)cell_bytes, c.req.n_cols,
+              c.req.n_cols, (unsigned long long)(cap >> 20));
+}
 // Reads the totals (*pt) or the speculation.  Leaves U / n_slow / n_runs, the result's sizes and bookkeeping, a speculative batch
 // registered with its slot, what the request's kind allocates, and the form of the rows and the expansion (n_fill .. lean).
 static int shared_tables(SharedCtx& c) {
@@ -1886,6 +1960,19 @@ static int shared_tables(SharedCtx& c) {
       VS_TRY(ralloc(r, r->gram_words, &r->d_gram));
       r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_gram + head);
       r->gram_stat = q.gram_stat;
+      break;
+    }
+    case ReqKind::Ibs: {   // (the matrix kernel's count of nonzero cells lives behind n_used)
+      VS_TRY(ibs_fits(c));
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(dev_alloc(idx, (size_t)(d.A * r->mx_pitch), (void**)&c.ld_matrix, &c.ld_tmp.bufs));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      const size_t nn = (size_t)q.n_cols * q.n_cols, head = 5 * nn + 1;
+      r->ibs_king_off = head + 2;
+      r->ibs_words = r->ibs_king_off + (q.ibs_stat == VS_IBS_KING ? nn : 0);
+      VS_TRY(ralloc(r, r->ibs_words, &r->d_ibs));
+      r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_ibs + head);
+      r->ibs_stat = q.ibs_stat;
       break;
     }
   }
@@ -2003,7 +2090,7 @@ static int shared_columns(SharedCtx& c) {
   VS_TRY(result_events(r));
   HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
   if (c.req.kind == ReqKind::Groups) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, r->d_counts);
-  else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD, Gram; Burden only under a window: shared_tables gives it counts)
+  else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD, Gram, Ibs; Burden only under a window: shared_tables gives it counts)
     launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
   HIP_TRY(hipGetLastError());
   if (c.req.kind == ReqKind::Assoc) VS_TRY(launch_assoc(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.d_pheno, c.req));
@@ -2015,6 +2102,9 @@ static int shared_columns(SharedCtx& c) {
   } else if (c.req.kind == ReqKind::Gram) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_gram(idx, r, c.ld_matrix, c.req));
+  } else if (c.req.kind == ReqKind::Ibs) {
+    VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+    VS_TRY(launch_ibs(idx, r, c.ld_matrix, c.U, c.req));
   } else if (c.req.kind == ReqKind::Matrix) VS_TRY(launch_matrix(idx, r, r->d_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
   HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
   r->pending = true;
@@ -3395,6 +3485,9 @@ int vs_index_set_option(vs_index* idx, const char* key, int64_t value) {
   } else if (k == "gram_chunk") {
     if (value != 0 && (value < 64 || value > kGramChunkMax)) return fail(VS_ERR_ARG, "gram_chunk takes 0 (default: by the batch's shape) or 64..%u rows", kGramChunkMax);
     o.gram_chunk = (uint32_t)value;
+  } else if (k == "ibs_chunk") {
+    if (value != 0 && (value < 64 || value > kIbsChunkMax)) return fail(VS_ERR_ARG, "ibs_chunk takes 0 (default: by the batch's shape) or 64..%u rows", kIbsChunkMax);
+    o.ibs_chunk = (uint32_t)value;
   } else if (k == "score_tile_cols") {
     if (value != 0 && (value < 16 || value > 65536 || value % 16)) return fail(VS_ERR_ARG, "score_tile_cols takes 0 (default) or a multiple of 16 in 16..65536");
     o.score_tile_cols = (uint32_t)value;
@@ -3750,6 +3843,22 @@ int vs_query_sample_gram(vs_index* idx, const vs_region* regions, uint64_t n, co
   });
 }
 
+int vs_query_sample_ibs(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t stat, vs_result** out) {
+  VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "an IBS"));
+  if (stat != VS_IBS_COUNTS && stat != VS_IBS_KING) return fail(VS_ERR_ARG, "IBS statistic %u is neither VS_IBS_COUNTS nor VS_IBS_KING", stat);
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));
+  if (mask.size() * 8 > kMatrixMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", idx->g.num_samples);
+  SharedReq req = column_request(ReqKind::Ibs, mask, rank, cols.size());
+  req.ibs_stat = stat;
+  return make_result(idx, kKindIbs, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
 int vs_query_sample_var_in_ref(vs_index* idx, const vs_region* regions, uint64_t n, uint32_t sample_id, vs_result** out) {
   if (!out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
   VS_TRY(query_handle(idx));
@@ -4078,7 +4187,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
         for (uint64_t a = r->h_var_begin[q] * G, e = a + r->h_nvar[q] * G; a < e; ++a) nc += c[a].x;
       r->n_carriers_kept = nc;
     }
-    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGram) {   // (LD, Gram: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
+    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGram || r->kind == kKindIbs) {   // (LD, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
       VS_TRY(result_ready(r));
       uint64_t nc = 0;
       HIP_TRY(hipMemcpyAsync(&nc, r->d_cell_total, 8, hipMemcpyDeviceToHost, idx->stream));
@@ -4111,6 +4220,8 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
   }
   if (r->kind == kKindGram)
     return fail(VS_ERR_UNSUPPORTED, "a Gram result holds one samples x samples matrix over the whole batch, no text per region (vs_result_get_sample_gram)");
+  if (r->kind == kKindIbs)
+    return fail(VS_ERR_UNSUPPORTED, "an IBS result holds samples x samples matrices over the whole batch, no text per region (vs_result_get_sample_ibs)");
   VS_TRY(fetch_region_meta(r));
   if (q >= r->d.Q) return fail(VS_ERR_ARG, "region %llu out of range", (unsigned long long)q);
   vs_index* idx = r->idx;
@@ -4630,6 +4741,43 @@ int vs_result_sample_gram_device(vs_result* r, uint64_t* n_rows, uint64_t* n_col
   if (n_rows) *n_rows = r->d.A;
   if (n_cols) *n_cols = nc;
   if (stat) *stat = r->gram_stat;
+  return VS_OK;
+}
+
+int vs_result_get_sample_ibs(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const uint32_t** col_ids, const vs_allele_counts** counts,
+                             const int64_t** het_het, const int64_t** hom_hom, const int64_t** carrier_both, const int64_t** ibs0, const int64_t** ibs2,
+                             const double** king, int64_t* n_used) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!het_het) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindIbs) return fail(VS_ERR_ARG, "not an IBS result (vs_query_sample_ibs)");
+  VS_TRY(array_to_host(r, r->d_ibs, r->ibs_words * 8, &r->cells_pin, "IBS matrices"));
+  VS_TRY(counts_to_host(r));
+  const int64_t* w = (const int64_t*)r->cells_pin.p;
+  const size_t nc = r->h_cols.size(), nn = nc * nc;
+  *het_het = w;
+  if (hom_hom) *hom_hom = w + nn;
+  if (carrier_both) *carrier_both = w + 2 * nn;
+  if (ibs0) *ibs0 = w + 3 * nn;
+  if (ibs2) *ibs2 = w + 4 * nn;
+  if (n_used) *n_used = w[5 * nn];
+  if (king) *king = r->ibs_stat == VS_IBS_KING ? (const double*)(w + r->ibs_king_off) : nullptr;
+  if (counts) *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = nc;
+  if (stat) *stat = r->ibs_stat;
+  if (col_ids) *col_ids = r->h_cols.data();
+  return VS_OK;
+}
+
+int vs_result_sample_ibs_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const void** dev_counts, const void** dev_matrices,
+                                const void** dev_king) {
+  VS_TRY(device_matrix_ready(r, dev_matrices, kKindIbs, "not an IBS result (vs_query_sample_ibs)"));
+  *dev_matrices = r->d_ibs;
+  if (dev_king) *dev_king = r->ibs_stat == VS_IBS_KING ? (const void*)(r->d_ibs + r->ibs_king_off) : nullptr;
+  if (dev_counts) *dev_counts = r->d_counts;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (stat) *stat = r->ibs_stat;
   return VS_OK;
 }
 

@@ -77,6 +77,10 @@
 //  k_gram_moments       table rows per workgroup, the tiles transposed into LDS, v_mfma_i32_16x16x64_i8, 64-bit integer atomics;
 //  k_gram_finish        the count-weighted column sums s, C and H; the GRM cells from 128-bit integers (vs_query_sample_gram: no
 //                       reference counterpart)
+// k_sample_ibs          the same staging once, three indicator products (het x het, hom x hom, carrier x carrier) into three sets of
+//  k_ibs_n_used         int32 accumulators: the pairwise genotype-state counts D^T D cannot give; the rows the duplicate rule kept;
+//  k_ibs_finish         IBS0 / IBS2 and the KING-robust kinship from exact integers (vs_query_sample_ibs: no reference counterpart;
+//                       DESIGN 5j)
 #pragma once
 #include "k_image.hip.h"
 #include "k_sites.hip.h"
@@ -97,3 +101,4 @@
 #include "k_matrix.hip.h"
 #include "k_ld.hip.h"
 #include "k_gram.hip.h"
+#include "k_ibs.hip.h"
