@@ -443,6 +443,40 @@ int vs_result_get_ld_band(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint
  * The engine has synchronised its stream when this returns: the caller needs no event. */
 int vs_result_ld_band_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* window, uint32_t* stat, const void** dev_counts,
                              const void** dev_band);
+/* LD matrices over regions: the complete square block of every region where vs_query_ld_band gives a band of the whole table -- the
+ * input of fine-mapping, conditional analysis, LD scores and "LD with the lead variant" plots (no reference counterpart).  T, its A
+ * rows, S and its n columns are those of vs_query_genotype_matrix over the same regions and sample_ids.  Region q owns the table
+ * rows row_begin[q] .. row_begin[q] + m_q, m_q = row_count[q] (vs_result_get_raw); its block is m_q x m_q four-byte cells,
+ * cells[block_begin[q] + a * m_q + b] for the pair of table rows (row_begin[q] + a, row_begin[q] + b): the full symmetric square,
+ * diagonal included.  block_begin is the exclusive scan of m_q^2 in uint64, block_begin[n] the number of cells.  Blocks go by table
+ * index and nothing else: overlapping or identical regions each get their own block over the shared rows, a row the duplicate rule
+ * dropped stays in the block as a row and a column of zeros, an empty region has an empty block.  The cells are the band's, by the
+ * same definition: VS_LD_DOT stores int32 Sxy (the diagonal is Sxx), VS_LD_R2 the float r2 formed from the count records in 64-bit
+ * integers, 0.0f where vx == 0 or vy == 0 (the diagonal of a polymorphic row is exactly 1.0f).  Every cell of every block is stored
+ * exactly once by the kernel.  The result carries the count record of every table row over S, as an LD result does.
+ * Checked on the host, in this order, before the handle's device is asked for: n == 0, sample_ids == NULL with n_ids != 0, non-NULL
+ * sample_ids with n_ids == 0, stat neither VS_LD_DOT nor VS_LD_R2 -> VS_ERR_ARG; id 0 or id >= num_samples ->
+ * VS_ERR_UNKNOWN_SAMPLE.  The blocks are formed from a temporary genotype matrix, which leaves the result as an LD batch's does;
+ * the matrix and the 4 sum(m_q^2) bytes of cells together may not exceed option "matrix_max_mib" MiB (default 32 GiB): beyond it
+ * the call is refused with VS_ERR_ARG once the plan has given the rows and before the matrix or the cells are allocated; the
+ * message names regions, rows, the largest block, columns and bytes.  The block sizes are known on the device only: the call waits
+ * once for a small scan over the per-region row counts, in front of the kernels vs_result_fill_ms times (the counts, the
+ * temporary matrix and the block kernel).  The batch is never speculative and leaves the handle's type-6 state as it was.
+ * vs_result_get_raw / vs_result_get_view with with_carriers = 0, vs_result_layout, vs_result_totals (n_carriers = the nonzero cells
+ * of the matrix) work as for an LD result; vs_result_format_region gives "Pos\tRef\tAlt" and "\t<Pos>:<Ref>:<Alt>" for every reported,
+ * non-dropped row of the region, then one line per such row: Pos, Ref, Alt and its values against the same rows, as %d or %.6g.
+ * What an LD result refuses this result refuses with the same codes; vs_result_get_ld_band refuses it with VS_ERR_ARG. */
+int vs_query_ld_matrix(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t stat,
+                       vs_result** out);
+/* The blocks of an LD-matrix result copied into page-locked memory owned by the result (int32 under VS_LD_DOT, float under
+ * VS_LD_R2: `stat` says which), block_begin[n_regions + 1], counts[i] the count record of table row i over S, col_ids[c] the sample
+ * id of column c.  Every out-pointer but `cells` may be NULL.  VS_ERR_ARG on any other result. */
+int vs_result_get_ld_matrix(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const uint32_t** col_ids,
+                            const vs_allele_counts** counts, const uint64_t** block_begin, const void** cells);
+/* Cells, block_begin (n_regions + 1 uint64) and counts (n_rows records of 16 bytes) as they lie in HBM, valid until vs_result_free.
+ * The engine has synchronised its stream when this returns: the caller needs no event. */
+int vs_result_ld_matrix_device(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const void** dev_counts,
+                               const void** dev_block_begin, const void** dev_cells);
 /* Sample Gram matrix / GRM over regions: D^T D, the samples x samples product of the dosages -- what a GRM, kinship, IBS-type sharing
  * and the PCA of a cohort start from, and the one product of the dosage matrix the other column queries leave out (D Y:
  * vs_query_assoc_scan, D^T W: vs_query_sample_scores, the band of D D^T: vs_query_ld_band; no reference counterpart).  T, its rows, S

@@ -9,6 +9,7 @@ per-region content is what the reference's `std::vector<Variant>` would hold.
 All computation happens in the HIP engine.
 """
 import ctypes as C
+import math
 from dataclasses import dataclass
 from typing import List, Sequence, Tuple
 
@@ -486,6 +487,65 @@ class QueryResult:
             out.append({"a": (int(pa), ra, aa), "b": (int(pb), rb, ab), "value": int(v) if dot else float(v)})
         return out
 
+    def ld_matrix(self):
+        """An LD-matrix result (VariantStore.ld_matrix) as numpy arrays: `cells` (flat; int32 dot products of the dosages under stat
+        "dot", float32 squared correlations under "r2"), `block_begin` (uint64[Q + 1]: region q's block is the row_count[q] x
+        row_count[q] cells from block_begin[q] on, row-major, for the table rows row_begin[q] .. + row_count[q]), `counts`
+        (structured as for allele_counts: the count record of every table row over the query's samples), `col_ids` (uint32[C], the
+        sample ids the statistics run over), `stat`, the table's `rows` and per region `row_begin` and `row_count`.  `cells`,
+        `block_begin` and `counts` are views of memory the result owns, valid until it is closed; the rest are copies."""
+        nq, a, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        st = C.c_uint32()
+        cols = C.POINTER(C.c_uint32)()
+        cnt = C.POINTER(_lib.AlleleCounts)()
+        bb = C.POINTER(C.c_uint64)()
+        p = C.c_void_p()
+        _check(self._lib.vs_result_get_ld_matrix(self._h, C.byref(nq), C.byref(a), C.byref(c), C.byref(st), C.byref(cols), C.byref(cnt),
+                                                 C.byref(bb), C.byref(p)), "vs_result_get_ld_matrix")
+        q, na, nc = int(nq.value), int(a.value), int(c.value)
+        stat = "r2" if st.value == self.LD_STATS["r2"] else "dot"
+        dtype = np.float32 if stat == "r2" else np.int32
+        block_begin = np.ctypeslib.as_array(bb, shape=(q + 1,))
+        total = int(block_begin[q])
+        cells = (np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(total * 4,)).view(dtype) if total else np.zeros(0, dtype))
+        counts = (np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint8)), shape=(na * 16,)).view(self.COUNT_DTYPE) if na
+                  else np.zeros(0, self.COUNT_DTYPE))
+        raw = self.raw(with_carriers=False)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "col_ids": np.ctypeslib.as_array(cols, shape=(nc,)).copy(), "stat": stat, "counts": counts, "block_begin": block_begin,
+                "cells": cells}
+
+    def region_ld_matrix(self, q):
+        """Region q's block of an LD-matrix result as an (m, m) array, m = the region's rows in the table: a view of the result's
+        cells, not a copy, valid until the result is closed."""
+        nq = C.c_uint64()
+        st = C.c_uint32()
+        bb = C.POINTER(C.c_uint64)()
+        p = C.c_void_p()
+        _check(self._lib.vs_result_get_ld_matrix(self._h, C.byref(nq), None, None, C.byref(st), None, None, C.byref(bb), C.byref(p)),
+               "vs_result_get_ld_matrix")
+        q = int(q)
+        if not 0 <= q < int(nq.value):
+            raise IndexError(f"region {q} of {int(nq.value)}")
+        b0, b1 = int(bb[q]), int(bb[q + 1])
+        m = math.isqrt(b1 - b0)
+        dtype = np.float32 if st.value == self.LD_STATS["r2"] else np.int32
+        if not m:
+            return np.zeros((0, 0), dtype)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(b1 * 4,)).view(dtype)[b0:b1].reshape(m, m)
+
+    def ld_matrix_device(self):
+        """(cells address, block_begin address, counts address, n_regions, n_rows, n_cols, stat) of an LD-matrix result as it lies in
+        this GPU's memory: the blocks' cells of 4 bytes (int32 under "dot", float32 under "r2"), n_regions + 1 uint64 offsets and
+        n_rows count records of four uint32, complete when this returns and valid until the result is closed."""
+        nq, a, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        st = C.c_uint32()
+        pc, pb, pcells = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_ld_matrix_device(self._h, C.byref(nq), C.byref(a), C.byref(c), C.byref(st), C.byref(pc), C.byref(pb),
+                                                    C.byref(pcells)), "vs_result_ld_matrix_device")
+        return (int(pcells.value or 0), int(pb.value or 0), int(pc.value or 0), int(nq.value), int(a.value), int(c.value),
+                "r2" if st.value == self.LD_STATS["r2"] else "dot")
+
     GRAM_STATS = {"dot": 0, "grm": 1}   # VS_GRAM_DOT, VS_GRAM_GRM
 
     def sample_gram(self):
@@ -897,6 +957,21 @@ class VariantStore:
             window = 0
         _check(self._lib.vs_query_ld_band(self._h, ptr, n, ids_ptr, n_ids, window, int(stat) & 0xFFFFFFFF, C.byref(h)),
                "vs_query_ld_band")
+        return QueryResult(self, h)
+
+    def ld_matrix(self, regions, samples=None, stat="r2") -> QueryResult:
+        """LD matrices over regions (vs_query_ld_matrix): for every region the full square block of its table rows against each
+        other, diagonal included, over the dosages of `samples` (names or ids, taken as a set; None: the whole cohort).  `stat`:
+        "r2" (squared dosage correlation, float32) or "dot" (sum of dosage products, int32, exact).  `regions` as for
+        allele_counts.  Read the result with QueryResult.ld_matrix / region_ld_matrix / ld_matrix_device / region_text."""
+        arr, ptr, n = _regions_array(regions)
+        h = C.c_void_p()
+        if isinstance(stat, str):
+            if stat.lower() not in QueryResult.LD_STATS:
+                raise ValueError(f"stat {stat!r}: 'r2' or 'dot'")
+            stat = QueryResult.LD_STATS[stat.lower()]
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        _check(self._lib.vs_query_ld_matrix(self._h, ptr, n, ids_ptr, n_ids, int(stat) & 0xFFFFFFFF, C.byref(h)), "vs_query_ld_matrix")
         return QueryResult(self, h)
 
     def sample_gram(self, regions, samples=None, stat="dot") -> QueryResult:

@@ -1156,7 +1156,19 @@ int ibs_main(const Args& a) {
   return EXIT_SUCCESS;
 }
 
-int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false) {
+// `variantstore ldmatrix`: the full LD block of every region (vs_query_ld_matrix) over the same samples.  Output as `counts`:
+// "#region <i> <x>:<y>", then the region's text (a header of the reported rows' <Pos>:<Ref>:<Alt>, then one line per row with its
+// r^2 -- or with --dot its dot product -- against every one of them).
+int ldmatrix_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore ldmatrix -p <output-prefix> -r <region> [-S <sample-name-file>] [--dot] [-o <outfile>] [--device <n>]\n\n"
+               "        For every region the square matrix of its variants (as query type 6 reports them) against each other: the\n"
+               "        squared correlation of the samples' alternate-allele dosages (of the whole cohort or of the samples named in\n"
+               "        the file), or with --dot the sum of the dosage products.\n";
+  return EXIT_FAILURE;
+}
+
+int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false, bool ldmatrix = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
   if (rc != VS_OK) die(rc, "load");
@@ -1181,11 +1193,12 @@ int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool
   std::vector<vs_region> batch;
   for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
   vs_result* res = nullptr;
-  if (ld) rc = vs_query_ld_band(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_window, a.ld_dot ? VS_LD_DOT : VS_LD_R2, &res);
+  if (ldmatrix) rc = vs_query_ld_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_dot ? VS_LD_DOT : VS_LD_R2, &res);
+  else if (ld) rc = vs_query_ld_band(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_window, a.ld_dot ? VS_LD_DOT : VS_LD_R2, &res);
   else if (genotypes) rc = vs_query_genotype_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
   else if (burden) rc = vs_query_sample_burden(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.min_ac, a.max_ac, &res);
   else rc = vs_query_allele_counts(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
-  if (rc != VS_OK) die(rc, ld ? "ld" : genotypes ? "genotypes" : burden ? "burden" : "counts");
+  if (rc != VS_OK) die(rc, ldmatrix ? "ldmatrix" : ld ? "ld" : genotypes ? "genotypes" : burden ? "burden" : "counts");
   std::ofstream file;
   if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
   std::ostream& out = a.outfile.empty() ? std::cout : file;
@@ -1243,12 +1256,12 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "score" || a.cmd == "gram" || a.cmd == "ibs") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "score" || a.cmd == "gram" || a.cmd == "ibs") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "ld" && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
-      else if (a.cmd == "ld" && f == "--dot") a.ld_dot = true;
+      else if ((a.cmd == "ld" || a.cmd == "ldmatrix") && f == "--dot") a.ld_dot = true;
       else if (a.cmd == "gram" && f == "--grm") a.gram_grm = true;
       else if (a.cmd == "ibs" && f == "--king") a.ibs_king = true;
       else if (a.cmd == "ibs" && f == "--min-kinship") {
@@ -1292,6 +1305,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "genotypes") {
     if (a.prefix.empty() || a.region.empty()) return genotypes_usage();
     return counts_main(a, /*burden=*/false, /*genotypes=*/true);
+  }
+  if (a.cmd == "ldmatrix") {
+    if (a.prefix.empty() || a.region.empty()) return ldmatrix_usage();
+    return counts_main(a, /*burden=*/false, /*genotypes=*/false, /*ld=*/false, /*ldmatrix=*/true);
   }
   if (a.cmd == "ld") {
     if (a.prefix.empty() || a.region.empty()) return ld_usage();

@@ -245,7 +245,8 @@ struct vs_result {
   const uint8_t* raw_arena = nullptr;   // NULL: carriers not copied
   int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts;
                  // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts; kKindAssoc: association scan;
-                 // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM; kKindIbs: pairwise IBS counts / KING kinship
+                 // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM; kKindIbs: pairwise IBS counts / KING kinship;
+                 // kKindLdMatrix: the full LD block of every region
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -288,6 +289,14 @@ struct vs_result {
   uint32_t* d_band = nullptr;
   uint32_t ld_window = 0, ld_stat = 0;
   std::vector<uint32_t> sl_band;   // the band rows of ONE region (vs_result_format_region)
+  // LD-matrix results (vs_query_ld_matrix): per region a square block of four-byte cells in HBM (d_ldm, ldm_cells of them in all;
+  // ld_stat says which), one buffer of 8-byte words beside it -- block_begin [Q + 1], the workgroup prefix [Q + 1], the scan's summary
+  // (four words), the nonzero cells of the (temporary) genotype matrix (d_cell_total, two words) --, counts and column ids as for an
+  // LD result; the cells' page-locked host copy is cells_pin, block_begin's host copy h_block_begin, sl_band the block of ONE region
+  uint32_t* d_ldm = nullptr;
+  uint64_t* d_ldm_meta = nullptr;
+  uint64_t ldm_cells = 0, ldm_wgs = 0;
+  std::vector<uint64_t> h_block_begin;
   // Gram results (vs_query_sample_gram): one buffer of 8-byte words in HBM -- gram [n x n] int64, col_weighted [n] int64, C, H, the
   // nonzero cells of the (temporary) genotype matrix (d_cell_total, two words), then from gram_grm_off on grm [n x n] float64 under
   // VS_GRAM_GRM -- copied to cells_pin in one piece; the count record of every table row in d_counts / counts_pin, the column ids h_cols
@@ -320,8 +329,9 @@ constexpr int kKindAssoc = 13;   // ... of an association-scan result: the rows 
 constexpr int kKindScores = 14;  // ... of a per-sample score result: the rows of type 6, a columns x scores matrix of weighted dosage sums instead of carrier lists
 constexpr int kKindGram = 15;    // ... of a Gram result: the rows of type 6, a samples x samples matrix of dosage products instead of carrier lists
 constexpr int kKindIbs = 16;     // ... of an IBS result: the rows of type 6, samples x samples matrices of genotype-state counts instead of carrier lists
+constexpr int kKindLdMatrix = 17;   // ... of an LD-matrix result: the rows of type 6, a square block of pair statistics per region instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
+  return r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
          r->kind == kKindScores;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
@@ -336,6 +346,8 @@ static int refuse_no_lists(const vs_result* r, const char* what) {
     return fail(VS_ERR_UNSUPPORTED, "%s: a Gram result holds a samples x samples matrix of dosage products, no carrier lists (vs_result_get_sample_gram)", what);
   if (r->kind == kKindIbs)
     return fail(VS_ERR_UNSUPPORTED, "%s: an IBS result holds samples x samples matrices of genotype-state counts, no carrier lists (vs_result_get_sample_ibs)", what);
+  if (r->kind == kKindLdMatrix)
+    return fail(VS_ERR_UNSUPPORTED, "%s: an LD-matrix result holds a square block of pair statistics per region, no carrier lists (vs_result_get_ld_matrix)", what);
   if (r->kind == kKindLd)
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD result holds a rows x window band of pair statistics, no carrier lists (vs_result_get_ld_band)", what);
   if (r->kind == kKindMatrix)
@@ -1196,8 +1208,8 @@ static int capture_totals(vs_result* r) {
 // phenotype table in column order, [column][Kp] float32 -- of pheno_words 8-byte words; the traits and the statistic.
 // Scores: mask, rank and n_cols as for the matrix; `weights` (host or device memory, weights_on_device) are n_weights x n_scores
 // float32 in report order; score_max_bits: per column the largest |w| as a float pattern, formed on the host from host weights.
-// Gram, Ibs: mask, rank and n_cols as for the matrix; the statistic.
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs };
+// Gram, Ibs: mask, rank and n_cols as for the matrix; the statistic.  LdMatrix: as LD without a window (ld_stat).
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1580,7 +1592,9 @@ static int launch_ibs(vs_index* idx, vs_result* r, const uint8_t* cells, uint64_
 //                      k_burden_split_plan + the SPLIT launch | k_genotype_matrix over (block of table rows, column tile) pairs |
 //                      LD: k_allele_counts over the table, k_genotype_matrix into the temporary, k_ld_band over blocks of table rows |
 //                      Gram: the same two, then k_sample_gram, k_gram_moments and (GRM) k_gram_finish (launch_gram) |
-//                      Ibs: the same two, then k_ibs_n_used, k_sample_ibs and k_ibs_finish (launch_ibs)
+//                      Ibs: the same two, then k_ibs_n_used, k_sample_ibs and k_ibs_finish (launch_ibs) |
+//                      LdMatrix: in front of them k_ld_block_scan over the per-region row counts and one host wait for its totals
+//                      (ld_matrix_tables: the size limit, the temporary matrix, the cells); behind them k_ld_block (launch_ld_block)
 //   shared_finish      enqueued: the completion event | synchronous: k_post_done, a word in mapped host memory, the host spins on it
 // A column request is never speculative, has no arena, and leaves the handle's type-6 state (size hints, sort hint) as it found
 // it: count batches interleaved with type-6 batches change none of theirs.
@@ -1591,7 +1605,7 @@ struct SharedCtx {
   uint64_t n;
   const SharedReq& req;
   ScratchBufs scratch;
-  ScratchBufs ld_tmp;   // an LD, Gram or IBS batch's temporary genotype matrix, apart from the rest: an enqueued batch keeps it only until it has finished
+  ScratchBufs ld_tmp;   // an LD, LD-matrix, Gram or IBS batch's temporary genotype matrix, apart from the rest: an enqueued batch keeps it only until it has finished
   // the consumer, asked once: Lists -- carrier lists in an arena (the result's or the resident one), may speculate, owns the handle's
   // type-6 hints; else a column request -- no arena, never speculative, hints untouched, the site of EVERY row (u_site).  Burden,
   // Matrix, LD and Scores are consumed behind k_permute_out, Lists, Counts, Groups and Assoc in front of it
@@ -1621,10 +1635,10 @@ struct SharedCtx {
   uint64_t n_fill = 0;          // shared_tables: carrier lists to expand, and the form of the rows and the expansion
   bool async_fill = false, fused = false, lean = false;
   uint32_t* u_site = nullptr;   // shared_rows: the site of every shared row (a column request: of every row)
-  uint8_t* ld_matrix = nullptr; // shared_tables: the temporary genotype matrix of an LD batch (ld_tmp)
+  uint8_t* ld_matrix = nullptr; // shared_tables: the temporary genotype matrix of an LD batch (ld_tmp); an LD-matrix batch: ld_matrix_tables
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -1975,6 +1989,14 @@ static int shared_tables(SharedCtx& c) {
       r->ibs_stat = q.ibs_stat;
       break;
     }
+    case ReqKind::LdMatrix:   // (the temporary matrix and the cells wait for the blocks' sizes: ld_matrix_tables, behind the permutation)
+      r->mx_pitch = ((uint64_t)q.n_cols + 15) & ~15ull;
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      VS_TRY(ralloc(r, 2 * (size_t)(d.Q + 1) + 6, &r->d_ldm_meta));
+      r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_ldm_meta + 2 * (d.Q + 1) + 4);
+      r->ld_stat = q.ld_stat;
+      break;
   }
   c.async_fill = c.allow_async && idx->opts.async_fill && c.n_fill > 0;
   c.fused = idx->opts.fill_fused && c.lists && !c.resident && !c.async_fill;
@@ -2084,9 +2106,12 @@ static int shared_expand(SharedCtx& c) {
 // table.  Assoc: k_allele_counts over the table, then k_assoc_scan.  Burden, Matrix, LD (behind the permutation): a burden filter's counts are inside the pair, and so are the three launches of
 // an LD batch: counts, temporary matrix, band.  Scores (behind the permutation): launch_scores, with its one host wait inside the pair.
 static int launch_scores(SharedCtx& c);
+static int ld_matrix_tables(SharedCtx& c);
+static int launch_ld_block(vs_index* idx, vs_result* r, const uint8_t* cells, const SharedReq& lq);
 static int shared_columns(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
   if (!c.behind_perm && !r->d.A) return VS_OK;
+  if (c.req.kind == ReqKind::LdMatrix) VS_TRY(ld_matrix_tables(c));   // (its one host wait in front of the pair of events: they time kernels only)
   VS_TRY(result_events(r));
   HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
   if (c.req.kind == ReqKind::Groups) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, r->d_counts);
@@ -2099,6 +2124,9 @@ static int shared_columns(SharedCtx& c) {
   if (c.req.kind == ReqKind::LD) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_ld(idx, r, c.ld_matrix, c.req));
+  } else if (c.req.kind == ReqKind::LdMatrix) {
+    VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+    VS_TRY(launch_ld_block(idx, r, c.ld_matrix, c.req));
   } else if (c.req.kind == ReqKind::Gram) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_gram(idx, r, c.ld_matrix, c.req));
@@ -2208,6 +2236,53 @@ static int launch_scores(SharedCtx& c) {
     }
   }
   hipLaunchKernelGGL(k_score_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, idx->stream, (const long long*)r->d_sums, cells, K, sh, r->d_score_out);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+
+// An LD-matrix batch behind the permutation (the per-region arrays are in the caller's order): the blocks' offsets and the workgroups'
+// prefix from the per-region row counts by one small scan; the two totals and the largest block come back in ONE host wait (the
+// batch is never speculative).  The temporary matrix and the cells together are held against option matrix_max_mib here, before
+// either is allocated.
+static int ld_matrix_tables(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  uint64_t* meta = r->d_ldm_meta;
+  hipLaunchKernelGGL(k_ld_block_scan, dim3(1), dim3(kLdBlockScanThreads), 0, idx->stream, (const uint64_t*)d.q_nvar, d.Q, meta, meta + (d.Q + 1), meta + 2 * (d.Q + 1));
+  HIP_TRY(hipGetLastError());
+  uint64_t sum[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(sum, meta + 2 * (d.Q + 1), sizeof sum, hipMemcpyDeviceToHost, idx->stream));
+  HIP_TRY(hipStreamSynchronize(idx->stream));
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  const uint64_t cells = sum[0], matrix_bytes = d.A * r->mx_pitch;
+  if (cells > cap / 4 || matrix_bytes > cap - 4 * cells) {
+    // (the handle's stream, waited for above, runs behind the plan's last event, so the plan's kernels have finished with the call's
+    //  temporaries that go back to the pool on return; the plan stream is waited for all the same, as matrix_fits does)
+    (void)hipStreamSynchronize(c.ps);
+    return fail(VS_ERR_ARG, "the LD blocks of %llu regions over %llu rows x %u columns (largest block %llu x %llu) take %llu bytes (%llu of the genotype matrix they are "
+                "formed from, %llu of the cells), more than the limit of %llu MiB (option matrix_max_mib): split the batch or the regions",
+                (unsigned long long)d.Q, (unsigned long long)d.A, c.req.n_cols, (unsigned long long)sum[2], (unsigned long long)sum[2],
+                (unsigned long long)(matrix_bytes + 4 * cells), (unsigned long long)matrix_bytes, (unsigned long long)(4 * cells), (unsigned long long)(cap >> 20));
+  }
+  if (sum[1] > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu tile pairs)", (unsigned long long)sum[1]);
+  r->ldm_cells = cells; r->ldm_wgs = sum[1];
+  VS_TRY(dev_alloc(idx, (size_t)matrix_bytes, (void**)&c.ld_matrix, &c.ld_tmp.bufs));
+  VS_TRY(ralloc(r, (size_t)cells, &r->d_ldm));
+  return VS_OK;
+}
+
+// The blocks of an LD-matrix batch from its temporary genotype matrix and the table's counts: one workgroup per (region, pair of
+// 64-row tiles), all regions in one launch.
+static int launch_ld_block(vs_index* idx, vs_result* r, const uint8_t* cells, const SharedReq& lq) {
+  const DevResult& d = r->d;
+  if (!r->ldm_cells) return VS_OK;
+  LdBlockArgs a{};
+  a.cells = cells; a.pitch = (uint32_t)r->mx_pitch; a.n_cols = lq.n_cols; a.Q = d.Q;
+  a.row_begin = (const uint64_t*)d.var_begin; a.row_count = (const uint64_t*)d.q_nvar;
+  a.block_begin = r->d_ldm_meta; a.wg_begin = r->d_ldm_meta + (d.Q + 1);
+  a.counts = r->d_counts; a.out = r->d_ldm;
+  if (lq.ld_stat == VS_LD_R2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_block<true>), dim3((unsigned)r->ldm_wgs), dim3(256), 0, idx->stream, a);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_block<false>), dim3((unsigned)r->ldm_wgs), dim3(256), 0, idx->stream, a);
   HIP_TRY(hipGetLastError());
   return VS_OK;
 }
@@ -3827,6 +3902,22 @@ int vs_query_ld_band(vs_index* idx, const vs_region* regions, uint64_t n, const 
   });
 }
 
+int vs_query_ld_matrix(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t stat, vs_result** out) {
+  VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "an LD-matrix"));
+  if (stat != VS_LD_DOT && stat != VS_LD_R2) return fail(VS_ERR_ARG, "LD statistic %u is neither VS_LD_DOT nor VS_LD_R2", stat);
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));
+  if (mask.size() * 8 > kMatrixMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", idx->g.num_samples);
+  SharedReq req = column_request(ReqKind::LdMatrix, mask, rank, cols.size());
+  req.ld_stat = stat;
+  return make_result(idx, kKindLdMatrix, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
 int vs_query_sample_gram(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t stat, vs_result** out) {
   VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "a Gram"));
   if (stat != VS_GRAM_DOT && stat != VS_GRAM_GRM) return fail(VS_ERR_ARG, "Gram statistic %u is neither VS_GRAM_DOT nor VS_GRAM_GRM", stat);
@@ -3991,6 +4082,13 @@ static int array_to_host(vs_result* r, const void* dev, size_t bytes, DevBuf* pi
     if (e2 != hipSuccess) { pin_release(idx, b); return fail(VS_ERR_HIP, "copy of the %s failed: %s", what, hipGetErrorString(e2)); }
   }
   *pin = b;
+  return VS_OK;
+}
+// block_begin of an LD-matrix result ([Q + 1]; the scan that wrote it was waited for when the batch was sized)
+static int ld_block_begin_to_host(vs_result* r) {
+  if (!r->h_block_begin.empty()) return VS_OK;
+  VS_TRY(fetch(r->idx, r->h_block_begin, (const uint64_t*)r->d_ldm_meta, (size_t)r->d.Q + 1));
+  HIP_TRY(hipStreamSynchronize(r->idx->stream));
   return VS_OK;
 }
 static int counts_to_host(vs_result* r) {   // (a grouped-count result: n_groups records per row)
@@ -4187,7 +4285,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
         for (uint64_t a = r->h_var_begin[q] * G, e = a + r->h_nvar[q] * G; a < e; ++a) nc += c[a].x;
       r->n_carriers_kept = nc;
     }
-    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGram || r->kind == kKindIbs) {   // (LD, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
+    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindGram || r->kind == kKindIbs) {   // (LD, LD matrix, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
       VS_TRY(result_ready(r));
       uint64_t nc = 0;
       HIP_TRY(hipMemcpyAsync(&nc, r->d_cell_total, 8, hipMemcpyDeviceToHost, idx->stream));
@@ -4340,6 +4438,62 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
         } else snprintf(num, sizeof num, "%d\n", (int)cell);
         out += num;
       }
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
+  if (r->kind == kKindLdMatrix) {   // the region's block without the rows and columns of dropped rows, a header of the rows' names
+    const uint64_t m = a1 - a0;
+    const VariantRow* rows;
+    if (r->have_headers) rows = r->h_rows.data() + a0;
+    else if (r->raw_rows) rows = r->raw_rows + a0;
+    else {
+      VS_TRY(fetch(idx, r->sl_rows, (const VariantRow*)r->d.rows + a0, (size_t)m));
+      rows = r->sl_rows.data();
+    }
+    VS_TRY(ld_block_begin_to_host(r));
+    const uint32_t* b;
+    if (r->cells_pin.p) b = (const uint32_t*)r->cells_pin.p + r->h_block_begin[q];
+    else {
+      VS_TRY(result_ready(r));
+      VS_TRY(fetch(idx, r->sl_band, (const uint32_t*)r->d_ldm + r->h_block_begin[q], (size_t)(m * m)));
+      b = r->sl_band.data();
+    }
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    std::string& out = r->text;
+    out = "Pos\tRef\tAlt";
+    for (uint64_t k = 0; k < m; ++k) {
+      const VariantRow& v = rows[k];
+      if (v.count_flags & kRowDropped) continue;
+      out += '\t';
+      out += std::to_string(v.pos);
+      out += ':';
+      out.append(idx->seq_chars, v.ref_off, v.ref_len);
+      out += ':';
+      out.append(idx->seq_chars, v.alt_off, v.alt_len);
+    }
+    out += '\n';
+    char num[48];
+    for (uint64_t x = 0; x < m; ++x) {
+      const VariantRow& v = rows[x];
+      if (v.count_flags & kRowDropped) continue;
+      out += std::to_string(v.pos);
+      out += '\t';
+      out.append(idx->seq_chars, v.ref_off, v.ref_len);
+      out += '\t';
+      out.append(idx->seq_chars, v.alt_off, v.alt_len);
+      for (uint64_t y = 0; y < m; ++y) {
+        if (rows[y].count_flags & kRowDropped) continue;
+        const uint32_t cell = b[x * m + y];
+        if (r->ld_stat == VS_LD_R2) {
+          float f;
+          memcpy(&f, &cell, 4);
+          snprintf(num, sizeof num, "\t%.6g", (double)f);
+        } else snprintf(num, sizeof num, "\t%d", (int)cell);
+        out += num;
+      }
+      out += '\n';
     }
     *text = out.c_str();
     if (len) *len = out.size();
@@ -4704,6 +4858,38 @@ int vs_result_ld_band_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, u
   if (n_rows) *n_rows = r->d.A;
   if (n_cols) *n_cols = r->h_cols.size();
   if (window) *window = r->ld_window;
+  if (stat) *stat = r->ld_stat;
+  return VS_OK;
+}
+
+int vs_result_get_ld_matrix(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const uint32_t** col_ids,
+                            const vs_allele_counts** counts, const uint64_t** block_begin, const void** cells) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!cells) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindLdMatrix) return fail(VS_ERR_ARG, "not an LD-matrix result (vs_query_ld_matrix)");
+  VS_TRY(array_to_host(r, r->d_ldm, (size_t)r->ldm_cells * 4, &r->cells_pin, "LD blocks"));
+  VS_TRY(counts_to_host(r));
+  VS_TRY(ld_block_begin_to_host(r));
+  *cells = r->cells_pin.p;
+  if (counts) *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (block_begin) *block_begin = r->h_block_begin.data();
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (stat) *stat = r->ld_stat;
+  if (col_ids) *col_ids = r->h_cols.data();
+  return VS_OK;
+}
+
+int vs_result_ld_matrix_device(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const void** dev_counts,
+                               const void** dev_block_begin, const void** dev_cells) {
+  VS_TRY(device_matrix_ready(r, dev_cells, kKindLdMatrix, "not an LD-matrix result (vs_query_ld_matrix)"));
+  *dev_cells = r->d_ldm;
+  if (dev_counts) *dev_counts = r->d_counts;
+  if (dev_block_begin) *dev_block_begin = r->d_ldm_meta;
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
   if (stat) *stat = r->ld_stat;
   return VS_OK;
 }

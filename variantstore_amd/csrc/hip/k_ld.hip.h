@@ -48,10 +48,24 @@ typedef int ld_i32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t ld_dosage4(uint32_t w) { return ((w >> 1) & 0x01010101u) + ((w >> 2) & 0x01010101u); }
 
+// 16 cells of a matrix row as dosages (p: 16-byte aligned)
+__device__ __forceinline__ uint4 ld_load_dosages(const uint8_t* p) {
+  uint4 v = *reinterpret_cast<const uint4*>(p);
+  v.x = ld_dosage4(v.x); v.y = ld_dosage4(v.y); v.z = ld_dosage4(v.z); v.w = ld_dosage4(v.w);
+  return v;
+}
+
 // n Sxx - Sx^2 of a row from its count record
 __device__ __forceinline__ void ld_moments(const uint4 c, int64_t n, int64_t& sx, int64_t& v) {
   sx = (int64_t)c.y;
   v = n * (int64_t)(c.y + 2ull * c.z) - sx * sx;
+}
+
+// r^2 of a pair from Sxy and the two rows' moments: exact 64-bit integers, three double operations, one cast; 0 beside a flat row
+__device__ __forceinline__ float ld_r2(int64_t n, int32_t sxy, int64_t sx, int64_t sy, int64_t vx, int64_t vy) {
+  if (vx == 0 || vy == 0) return 0.0f;
+  const double cov = (double)(n * (int64_t)sxy - sx * sy);
+  return (float)(cov * cov / ((double)vx * (double)vy));
 }
 
 template <int MAXT, bool R2>
@@ -78,10 +92,7 @@ __global__ void __launch_bounds__(256) k_ld_band(LdArgs a) {
       const uint32_t r = i >> 4, col = c0 + 16 * (i & 15);
       const uint64_t g = row0 + r;
       uint4 v{0u, 0u, 0u, 0u};
-      if (g < a.A && col < a.pitch) {
-        v = *reinterpret_cast<const uint4*>(a.cells + g * a.pitch + col);
-        v.x = ld_dosage4(v.x); v.y = ld_dosage4(v.y); v.z = ld_dosage4(v.z); v.w = ld_dosage4(v.w);
-      }
+      if (g < a.A && col < a.pitch) v = ld_load_dosages(a.cells + g * a.pitch + col);
       *reinterpret_cast<uint4*>(s_ld + r * kLdStride + 16 * (i & 15)) = v;
     }
     __syncthreads();
@@ -119,14 +130,8 @@ __global__ void __launch_bounds__(256) k_ld_band(LdArgs a) {
       const uint64_t i = i_first + g;
       if (j <= i || j - i > W) continue;   // (j < A and i < j: row i is a row of the table)
       uint32_t out;
-      if (R2) {
-        float r2 = 0.0f;
-        if (vx[g] != 0 && vy != 0) {
-          const double cov = (double)(n * (int64_t)acc[t][g] - sx[g] * sy);
-          r2 = (float)(cov * cov / ((double)vx[g] * (double)vy));
-        }
-        out = __float_as_uint(r2);
-      } else out = (uint32_t)acc[t][g];
+      if (R2) out = __float_as_uint(ld_r2(n, acc[t][g], sx[g], sy, vx[g], vy));
+      else out = (uint32_t)acc[t][g];
       a.band[i * W + (j - i - 1)] = out;
     }
   }

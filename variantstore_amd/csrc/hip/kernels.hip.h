@@ -73,6 +73,9 @@
 // k_ld_band             the band of D D^T over that matrix's dosages -- every table row against the next W rows -- on the matrix
 //                       cores (v_mfma_i32_16x16x64_i8, exact), as dot products or r^2 (vs_query_ld_band: no reference counterpart;
 //                       with k_sample_gram the kernels here on the matrix cores; by DESIGN 5e's count its reads of the matrix bound it, not the MFMAs)
+// k_ld_block            D D^T in full per region: the m x m block of every region of a batch, a pair of 64-row tiles per workgroup,
+//  k_ld_block_scan       found by bisection over the scan of the regions' workgroups; k_ld_band's staging, fragments and r^2, both
+//                       triangles stored once with plain stores (vs_query_ld_matrix: no reference counterpart)
 // k_sample_gram         D^T D over the same dosages, the samples x samples Gram matrix: a pair of 128-column tiles and a chunk of
 //  k_gram_moments       table rows per workgroup, the tiles transposed into LDS, v_mfma_i32_16x16x64_i8, 64-bit integer atomics;
 //  k_gram_finish        the count-weighted column sums s, C and H; the GRM cells from 128-bit integers (vs_query_sample_gram: no
@@ -100,5 +103,6 @@
 #include "k_burden.hip.h"
 #include "k_matrix.hip.h"
 #include "k_ld.hip.h"
+#include "k_ld_block.hip.h"
 #include "k_gram.hip.h"
 #include "k_ibs.hip.h"
