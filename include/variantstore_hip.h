@@ -282,6 +282,44 @@ int vs_result_get_assoc_scan(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, u
  * NULL), valid until vs_result_free.  The engine has synchronised its stream when this returns: the caller needs no event. */
 int vs_result_assoc_scan_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* n_traits, uint32_t* stat,
                                 const void** dev_counts, const void** dev_scores);
+/* Trait-matrix association scan: every row of the type-6 variant table against a WIDE panel of K traits, 1 <= K <=
+ * VS_TRAIT_MATRIX_MAX -- eQTL windows against every expressed gene, a variant set against every phenotype of a biobank, K shuffled
+ * copies of one trait -- as the product of the dosage matrix with the panel on the matrix cores (no reference counterpart).
+ * regions, sample_ids / n_ids, traits (HOST float32, n_ids x n_traits, in the order of the ids), the subset S, its n columns, the
+ * dosage, dropped rows, trait_names, the argument rules and their error codes are vs_query_assoc_scan's, with VS_TRAIT_MATRIX_MAX in
+ * place of VS_TRAITS_MAX; the checks come in that call's order and before the handle's device is asked for.  n must stay below 2^22
+ * (VS_ERR_UNSUPPORTED).
+ * Fixed point: per trait k, M_k = max |y| = m 2^e (frexp, 0.5 <= m < 1), f_k = 30 - e (0 for a column of zeros), q_k(s) =
+ * rint(y 2^f_k), ties to even: |q| < 2^30.  (vs_assoc_matrix_quantise gives q and f.)  scores[i * n_traits + k], a float64, is
+ *   VS_ASSOC_DOT   ldexp((double)S, -f_k), S = sum over s in S of d_i(s) q_k(s), an exact integer with |S| <= 2^53: the caller
+ *                  gets it back as ldexp(score, f_k);
+ *   VS_ASSOC_CHI2  the score test of vs_query_assoc_scan from exact integers: vx = n Sxx - Sx^2 (64 bits), Sy = sum q, Syy = sum q^2,
+ *                  vy = n Syy - Sy^2 and cov = n S - Sx Sy in 128 bits, each converted to double once, chi2 = (((double)n * cov) *
+ *                  cov) / ((double)vx * vy) in this order without contraction; 0.0 when vx == 0 or vy <= 0.  2^f_k cancels.
+ * No floating-point value is ever summed: the same call gives the same bytes.  The result also holds f_k (shift), the exact trait
+ * sums as doubles (trait_sum = ldexp(Sy, -f_k), trait_sumsq = ldexp(Syy, -2 f_k)), the rows' count records over S and the column ids.
+ * The temporary genotype matrix (rows x pitch, pitch = n rounded up to 16), the cells (rows x n_traits x 8), the count records
+ * (rows x 16) and the limb panel (ceil(n_traits / 16) x 64 x pitch) together are held to option "matrix_max_mib": a larger request
+ * is refused with VS_ERR_ARG before anything is allocated; the message gives rows, columns, traits, the total and the parts in bytes.
+ * Never speculative; the handle's type-6 state stays as it was.  What works on the result and what is refused is an
+ * association-scan result's (vs_result_format_region gives its text with K score columns), with the accessors below in place of
+ * vs_result_get_assoc_scan / _device; those two and the other kinds' getters answer VS_ERR_ARG here, these two on any other result. */
+#define VS_TRAIT_MATRIX_MAX 65536u
+int vs_query_assoc_matrix(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids,
+                          const float* traits, uint32_t n_traits, uint32_t stat, const char* const* trait_names, vs_result** out);
+/* Host copies, owned by the result: scores[i * n_traits + k], counts[i], col_ids, shift / trait_sum / trait_sumsq (n_traits each);
+ * any but `scores` may be NULL. */
+int vs_result_get_assoc_matrix(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* n_traits, uint32_t* stat,
+                               const uint32_t** col_ids, const int32_t** shift, const double** trait_sum, const double** trait_sumsq,
+                               const vs_allele_counts** counts, const double** scores);
+/* The cells as they lie in HBM: n_rows x n_traits float64, row-major, and the n_rows count records of 16 bytes (dev_counts may be
+ * NULL), valid until vs_result_free.  The engine has synchronised its stream when this returns. */
+int vs_result_assoc_matrix_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* n_traits, uint32_t* stat,
+                                  const void** dev_counts, const void** dev_scores);
+/* The engine's own quantiser, the one vs_query_assoc_matrix calls; host-only, needs no handle.  traits: n x n_traits float32,
+ * row-major; q_out: n x n_traits int32; shift_out: n_traits int32.  VS_ERR_ARG on NULL, n == 0, n_traits == 0 or a value that is
+ * not finite. */
+int vs_assoc_matrix_quantise(const float* traits, uint64_t n, uint32_t n_traits, int32_t* q_out, int32_t* shift_out);
 /* Per-sample scores: samples x K weighted dosage sums over the rows a batch reports -- "what is each sample's polygenic score under
  * this score file?", the projection of the samples onto K loadings, the second half of a matrix-free iteration on the genotype matrix
  * (vs_query_assoc_scan gives G Y: every row against K per-sample vectors; this gives G^T W: every sample against K per-variant

@@ -151,6 +151,14 @@ SYMBOLS = {
                                           C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_void_p)]),
     "vs_result_ld_matrix_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "vs_query_assoc_matrix": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_float), C.c_uint32, C.c_uint32,
+                                        C.POINTER(C.c_char_p), C.POINTER(_P)]),
+    "vs_result_get_assoc_matrix": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                             C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_double)),
+                                             C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.POINTER(AlleleCounts)), C.POINTER(C.POINTER(C.c_double))]),
+    "vs_result_assoc_matrix_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "vs_assoc_matrix_quantise": (C.c_int, [C.POINTER(C.c_float), C.c_uint64, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "vs_query_expand_site_ranges": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(_P)]),
     "vs_query_sample_var_in_ref": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.c_uint32, C.POINTER(_P)]),
     "vs_query_samples_var_in_ref": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(_P)]),

@@ -55,6 +55,23 @@ class DeviceArray:
         self.n = int(n)
 
 
+def quantise_traits(y):
+    """The engine's own quantiser (vs_assoc_matrix_quantise, host-only): `y` array-like of shape (n,) or (n, K), float32, finite.
+    Returns (q, shift): q ((n, K) int32) = rint(y * 2**shift[k]) per column, ties to even, |q| < 2**30; shift int32[K]."""
+    y = np.asarray(y, dtype=np.float32)
+    if y.ndim == 1:
+        y = y.reshape(-1, 1)
+    if y.ndim != 2 or y.shape[0] == 0 or y.shape[1] == 0:
+        raise ValueError("traits: a non-empty array of shape (n,) or (n, K)")
+    y = np.ascontiguousarray(y)
+    q = np.zeros(y.shape, np.int32)
+    shift = np.zeros(y.shape[1], np.int32)
+    _check(_lib.load().vs_assoc_matrix_quantise(y.ctypes.data_as(C.POINTER(C.c_float)), y.shape[0], y.shape[1],
+                                                q.ctypes.data_as(C.POINTER(C.c_int32)), shift.ctypes.data_as(C.POINTER(C.c_int32))),
+           "vs_assoc_matrix_quantise")
+    return q, shift
+
+
 def _regions_array(regions):
     if isinstance(regions, DeviceArray):
         return regions, C.cast(C.c_void_p(regions.ptr), C.POINTER(Region)), regions.n
@@ -333,6 +350,52 @@ class QueryResult:
         pc, ps = C.c_void_p(), C.c_void_p()
         _check(self._lib.vs_result_assoc_scan_device(self._h, C.byref(a), C.byref(c), C.byref(k), C.byref(st), C.byref(pc), C.byref(ps)),
                "vs_result_assoc_scan_device")
+        return (int(ps.value or 0), int(pc.value or 0), int(a.value), int(c.value), int(k.value),
+                "chi2" if st.value == self.ASSOC_STATS["chi2"] else "dot")
+
+    def assoc_matrix(self):
+        """A trait-matrix association result (VariantStore.assoc_matrix) as numpy arrays: what assoc_scan() gives -- `scores`
+        ((A, K) float64), `counts`, `col_ids`, `trait_sum`, `trait_sumsq`, `trait_names`, `stat`, `rows`, `row_begin`, `row_count`,
+        `flags` -- plus `shift` (int32[K]: trait k was quantised as q = rint(y * 2**shift[k])) and, under stat "dot", `sums`
+        ((A, K) int64: the exact integers sum of dosage x q, scores = ldexp(sums, -shift); None under "chi2").  trait_sum and
+        trait_sumsq are the exact sums of q and q*q scaled back.  Copies, valid after the result is closed."""
+        a, c = C.c_uint64(), C.c_uint64()
+        k, st = C.c_uint32(), C.c_uint32()
+        cols = C.POINTER(C.c_uint32)()
+        sh = C.POINTER(C.c_int32)()
+        sy, syy, sc = C.POINTER(C.c_double)(), C.POINTER(C.c_double)(), C.POINTER(C.c_double)()
+        cnt = C.POINTER(_lib.AlleleCounts)()
+        _check(self._lib.vs_result_get_assoc_matrix(self._h, C.byref(a), C.byref(c), C.byref(k), C.byref(st), C.byref(cols), C.byref(sh),
+                                                    C.byref(sy), C.byref(syy), C.byref(cnt), C.byref(sc)), "vs_result_get_assoc_matrix")
+        na, nc, nk = int(a.value), int(c.value), int(k.value)
+        if na:
+            scores = np.ctypeslib.as_array(sc, shape=(na * nk,)).reshape(na, nk).copy()
+            counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint8)), shape=(na * 16,)).view(self.COUNT_DTYPE).copy()
+        else:
+            scores, counts = np.zeros((0, nk), np.float64), np.zeros(0, self.COUNT_DTYPE)
+        shift = np.ctypeslib.as_array(sh, shape=(nk,)).copy()
+        stat = "chi2" if st.value == self.ASSOC_STATS["chi2"] else "dot"
+        sums = np.ldexp(scores, shift[None, :]).astype(np.int64) if stat == "dot" else None   # (exact: |sum| <= 2^53)
+        raw = self.raw(with_carriers=False)
+        names = self.region_text(0).split("\n")[0].split("\t")[7:]   # (the result's own: the header of every region's text)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "flags": raw["region_flags"].copy(), "scores": scores, "sums": sums, "shift": shift, "counts": counts,
+                "col_ids": np.ctypeslib.as_array(cols, shape=(nc,)).copy(), "trait_sum": np.ctypeslib.as_array(sy, shape=(nk,)).copy(),
+                "trait_sumsq": np.ctypeslib.as_array(syy, shape=(nk,)).copy(), "trait_names": list(names), "stat": stat}
+
+    def region_assoc_matrix(self, q):
+        """The rows region q of a trait-matrix association result reports, as region_assoc gives them."""
+        return self.region_assoc(q)
+
+    def assoc_matrix_device(self):
+        """(scores address, counts address, n_rows, n_cols, n_traits, stat) of a trait-matrix association result as it lies in this
+        GPU's memory: n_rows x n_traits float64 cells, row-major, and n_rows count records of four uint32, complete when this
+        returns and valid until the result is closed."""
+        a, c = C.c_uint64(), C.c_uint64()
+        k, st = C.c_uint32(), C.c_uint32()
+        pc, ps = C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_assoc_matrix_device(self._h, C.byref(a), C.byref(c), C.byref(k), C.byref(st), C.byref(pc), C.byref(ps)),
+               "vs_result_assoc_matrix_device")
         return (int(ps.value or 0), int(pc.value or 0), int(a.value), int(c.value), int(k.value),
                 "chi2" if st.value == self.ASSOC_STATS["chi2"] else "dot")
 
@@ -1036,6 +1099,37 @@ class VariantStore:
         h = C.c_void_p()
         _check(self._lib.vs_query_assoc_scan(self._h, ptr, n, ids_ptr, n_ids, y.ctypes.data_as(C.POINTER(C.c_float)), y.shape[1],
                                              int(stat) & 0xFFFFFFFF, name_arr, C.byref(h)), "vs_query_assoc_scan")
+        return QueryResult(self, h)
+
+    def assoc_matrix(self, regions, traits, samples=None, stat="dot", trait_names=None) -> QueryResult:
+        """Trait-matrix association scan over regions (vs_query_assoc_matrix): every row of the variant table a type-6 batch over
+        `regions` produces against a wide panel of K traits (1 .. 65,536) -- the product of the dosage matrix with the panel on
+        the matrix cores.  `traits`, `samples`, `stat` and `trait_names` as for assoc_scan.  Each trait is quantised to 31-bit
+        fixed point (quantise_traits gives the integers); every sum is an exact integer, so the same call gives the same bytes.
+        Read the result with QueryResult.assoc_matrix / assoc_matrix_device / region_assoc_matrix / region_text."""
+        y = np.asarray(traits, dtype=np.float32)
+        if y.ndim == 1:
+            y = y.reshape(-1, 1)
+        if y.ndim != 2:
+            raise ValueError("traits: an array of shape (n,) or (n, K)")
+        y = np.ascontiguousarray(y)
+        if isinstance(stat, str):
+            if stat.lower() not in QueryResult.ASSOC_STATS:
+                raise ValueError(f"stat {stat!r}: 'dot' or 'chi2'")
+            stat = QueryResult.ASSOC_STATS[stat.lower()]
+        arr, ptr, n = _regions_array(regions)
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        if samples is None:
+            n_ids = y.shape[0]
+        elif n_ids != y.shape[0]:
+            raise ValueError(f"traits has {y.shape[0]} rows for {n_ids} samples")
+        names = [str(s) for s in trait_names] if trait_names is not None else None
+        if names is not None and len(names) != y.shape[1]:
+            raise ValueError(f"{len(names)} trait names for {y.shape[1]} traits")
+        name_arr = (C.c_char_p * len(names))(*[s.encode() for s in names]) if names else None
+        h = C.c_void_p()
+        _check(self._lib.vs_query_assoc_matrix(self._h, ptr, n, ids_ptr, n_ids, y.ctypes.data_as(C.POINTER(C.c_float)), y.shape[1],
+                                               int(stat) & 0xFFFFFFFF, name_arr, C.byref(h)), "vs_query_assoc_matrix")
         return QueryResult(self, h)
 
     def sample_scores(self, regions, weights, samples=None, score_names=None) -> QueryResult:

@@ -812,7 +812,18 @@ int assoc_usage() {
   return EXIT_FAILURE;
 }
 
-int assoc_main(const Args& a) {
+// `variantstore assocmatrix`: the same file without the limit of 8 traits (up to 65,536), through vs_query_assoc_matrix.  Output as `assoc`.
+int assocmatrix_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore assocmatrix -p <output-prefix> -r <region> -P <phenotype-file> [--chi2] [-o <outfile>] [--device <n>]\n\n"
+               "        Every variant query type 6 reports in each region against a wide panel of phenotypes (up to 65536): the sum of\n"
+               "        dosage x value over the file's samples from exact fixed-point integers, or with --chi2 the score test.  The file\n"
+               "        is `assoc`'s: one `sample value [value ...]` line per sample; a first line `#sample name1 name2 ...` names the traits.\n";
+  return EXIT_FAILURE;
+}
+
+// (max_traits: VS_TRAITS_MAX for `assoc`, VS_TRAIT_MATRIX_MAX for `assocmatrix`, which also picks the query)
+int assoc_main(const Args& a, const size_t max_traits = VS_TRAITS_MAX) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
   if (rc != VS_OK) die(rc, "load");
@@ -841,7 +852,7 @@ int assoc_main(const Args& a) {
     if (f.empty()) continue;
     if (f[0] == "#sample") {
       if (!ids.empty() || !names.empty() || f.size() < 2) return fail_with(at + ": a `#sample name ...` line comes first and once");
-      if (f.size() - 1 > VS_TRAITS_MAX) return fail_with(at + ": more than " + std::to_string(VS_TRAITS_MAX) + " traits");
+      if (f.size() - 1 > max_traits) return fail_with(at + ": more than " + std::to_string(max_traits) + " traits");
       names.assign(f.begin() + 1, f.end());
       n_traits = names.size();
       continue;
@@ -849,7 +860,7 @@ int assoc_main(const Args& a) {
     if (f.size() < 2) return fail_with(at + ": no value behind the sample");
     if (!n_traits) n_traits = f.size() - 1;
     if (f.size() - 1 != n_traits) return fail_with(at + ": " + std::to_string(f.size() - 1) + " values, " + std::to_string(n_traits) + " expected");
-    if (n_traits > VS_TRAITS_MAX) return fail_with(at + ": more than " + std::to_string(VS_TRAITS_MAX) + " traits");
+    if (n_traits > max_traits) return fail_with(at + ": more than " + std::to_string(max_traits) + " traits");
     uint32_t sid = 0;
     if (vs_index_sample_id(idx, f[0].c_str(), &sid) != VS_OK || sid == 0) return fail_with(at + ": Sample not found: " + f[0]);
     ids.push_back(sid);
@@ -866,9 +877,10 @@ int assoc_main(const Args& a) {
   std::vector<vs_region> batch;
   for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
   vs_result* res = nullptr;
-  rc = vs_query_assoc_scan(idx, batch.data(), batch.size(), ids.data(), ids.size(), traits.data(), (uint32_t)n_traits, a.assoc_chi2 ? VS_ASSOC_CHI2 : VS_ASSOC_DOT,
-                           names.empty() ? nullptr : name_ptrs.data(), &res);
-  if (rc != VS_OK) die(rc, "assoc");
+  const bool wide = max_traits != VS_TRAITS_MAX;
+  rc = (wide ? vs_query_assoc_matrix : vs_query_assoc_scan)(idx, batch.data(), batch.size(), ids.data(), ids.size(), traits.data(), (uint32_t)n_traits,
+                                                            a.assoc_chi2 ? VS_ASSOC_CHI2 : VS_ASSOC_DOT, names.empty() ? nullptr : name_ptrs.data(), &res);
+  if (rc != VS_OK) die(rc, wide ? "assocmatrix" : "assoc");
   std::ofstream file;
   if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
   std::ostream& out = a.outfile.empty() ? std::cout : file;
@@ -1256,7 +1268,7 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "score" || a.cmd == "gram" || a.cmd == "ibs") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "gram" || a.cmd == "ibs") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
@@ -1273,10 +1285,10 @@ int main(int argc, char** argv) {
       }
       else if (f == "-r" || f == "--region") a.region = need(i);
       else if (a.cmd == "groups" && (f == "-G" || f == "--groups")) a.groups_file = need(i);
-      else if (a.cmd == "assoc" && (f == "-P" || f == "--phenotypes")) a.pheno_file = need(i);
-      else if (a.cmd == "assoc" && f == "--chi2") a.assoc_chi2 = true;
+      else if ((a.cmd == "assoc" || a.cmd == "assocmatrix") && (f == "-P" || f == "--phenotypes")) a.pheno_file = need(i);
+      else if ((a.cmd == "assoc" || a.cmd == "assocmatrix") && f == "--chi2") a.assoc_chi2 = true;
       else if (a.cmd == "score" && (f == "-W" || f == "--weights")) a.weights_file = need(i);
-      else if (a.cmd != "groups" && a.cmd != "assoc" && (f == "-S" || f == "--samples")) a.samples_file = need(i);
+      else if (a.cmd != "groups" && a.cmd != "assoc" && a.cmd != "assocmatrix" && (f == "-S" || f == "--samples")) a.samples_file = need(i);
       else if (f == "-o" || f == "--output_file") a.outfile = need(i);
       else if (f == "--device") a.device = atoi(need(i).c_str());
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
@@ -1289,6 +1301,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "groups") {
     if (a.prefix.empty() || a.region.empty() || a.groups_file.empty()) return groups_usage();
     return groups_main(a);
+  }
+  if (a.cmd == "assocmatrix") {
+    if (a.prefix.empty() || a.region.empty() || a.pheno_file.empty()) return assocmatrix_usage();
+    return assoc_main(a, VS_TRAIT_MATRIX_MAX);
   }
   if (a.cmd == "assoc") {
     if (a.prefix.empty() || a.region.empty() || a.pheno_file.empty()) return assoc_usage();

@@ -246,7 +246,7 @@ struct vs_result {
   int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts;
                  // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts; kKindAssoc: association scan;
                  // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM; kKindIbs: pairwise IBS counts / KING kinship;
-                 // kKindLdMatrix: the full LD block of every region
+                 // kKindLdMatrix: the full LD block of every region; kKindAssocMatrix: trait-matrix association scan
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -262,6 +262,9 @@ struct vs_result {
   uint32_t n_traits = 0, assoc_stat = 0;
   std::vector<double> trait_sum, trait_sumsq;
   std::vector<std::string> trait_names;
+  // trait-matrix association results (vs_query_assoc_matrix): the same fields (n_traits up to VS_TRAIT_MATRIX_MAX; trait_sum and
+  // trait_sumsq from the exact integer sums) and f_k per trait; d_cell_total, two words of their own, is the matrix kernel's
+  std::vector<int32_t> trait_shift;
   // score results (vs_query_sample_scores): columns x n_scores int64 sums in HBM (row-major) with the float64 scores formed from
   // them right behind (d_score_out), both copied to cells_pin in one piece; the kernels' words (largest |w| per column, the
   // pair count of vs_result_totals); f_k per column and the scores' names (empty: the decimal index stands for a score)
@@ -330,8 +333,9 @@ constexpr int kKindScores = 14;  // ... of a per-sample score result: the rows o
 constexpr int kKindGram = 15;    // ... of a Gram result: the rows of type 6, a samples x samples matrix of dosage products instead of carrier lists
 constexpr int kKindIbs = 16;     // ... of an IBS result: the rows of type 6, samples x samples matrices of genotype-state counts instead of carrier lists
 constexpr int kKindLdMatrix = 17;   // ... of an LD-matrix result: the rows of type 6, a square block of pair statistics per region instead of carrier lists
+constexpr int kKindAssocMatrix = 18;   // ... of a trait-matrix association result: the rows of type 6, a score per row and trait (up to VS_TRAIT_MATRIX_MAX traits) instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
+  return r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
          r->kind == kKindScores;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
@@ -340,6 +344,8 @@ static int refuse_no_lists(const vs_result* r, const char* what) {
     return fail(VS_ERR_UNSUPPORTED, "%s: a grouped-count result holds counts per row and group, no carrier lists (vs_result_get_group_counts)", what);
   if (r->kind == kKindAssoc)
     return fail(VS_ERR_UNSUPPORTED, "%s: an association-scan result holds a score per row and trait, no carrier lists (vs_result_get_assoc_scan)", what);
+  if (r->kind == kKindAssocMatrix)
+    return fail(VS_ERR_UNSUPPORTED, "%s: a trait-matrix association result holds a score per row and trait, no carrier lists (vs_result_get_assoc_matrix)", what);
   if (r->kind == kKindScores)
     return fail(VS_ERR_UNSUPPORTED, "%s: a per-sample score result holds a score per sample and weight column, no carrier lists (vs_result_get_sample_scores)", what);
   if (r->kind == kKindGram)
@@ -1209,7 +1215,9 @@ static int capture_totals(vs_result* r) {
 // Scores: mask, rank and n_cols as for the matrix; `weights` (host or device memory, weights_on_device) are n_weights x n_scores
 // float32 in report order; score_max_bits: per column the largest |w| as a float pattern, formed on the host from host weights.
 // Gram, Ibs: mask, rank and n_cols as for the matrix; the statistic.  LdMatrix: as LD without a window (ld_stat).
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix };
+// AssocMatrix: mask, rank and n_cols as for the matrix; `am` is the host's limb panel with the traits' shifts and sums (it goes to
+// the device once the batch has passed the size limit: assoc_matrix_upload); the traits and the statistic.
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1220,6 +1228,7 @@ struct SharedReq {
   const uint64_t* pheno = nullptr;
   size_t pheno_words = 0;
   uint32_t n_traits = 0, assoc_stat = 0;
+  const AmPanel* am = nullptr;
   const float* weights = nullptr;
   uint64_t n_weights = 0;
   uint32_t n_scores = 0, score_max_bits[kScoresMax] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1605,7 +1614,7 @@ struct SharedCtx {
   uint64_t n;
   const SharedReq& req;
   ScratchBufs scratch;
-  ScratchBufs ld_tmp;   // an LD, LD-matrix, Gram or IBS batch's temporary genotype matrix, apart from the rest: an enqueued batch keeps it only until it has finished
+  ScratchBufs ld_tmp;   // an LD, LD-matrix, Gram, IBS or trait-matrix batch's temporary genotype matrix (the last one's limb panel too), apart from the rest: an enqueued batch keeps it only until it has finished
   // the consumer, asked once: Lists -- carrier lists in an arena (the result's or the resident one), may speculate, owns the handle's
   // type-6 hints; else a column request -- no arena, never speculative, hints untouched, the site of EVERY row (u_site).  Burden,
   // Matrix, LD and Scores are consumed behind k_permute_out, Lists, Counts, Groups and Assoc in front of it
@@ -1636,9 +1645,10 @@ struct SharedCtx {
   bool async_fill = false, fused = false, lean = false;
   uint32_t* u_site = nullptr;   // shared_rows: the site of every shared row (a column request: of every row)
   uint8_t* ld_matrix = nullptr; // shared_tables: the temporary genotype matrix of an LD batch (ld_tmp); an LD-matrix batch: ld_matrix_tables
+  uint64_t* am_dev = nullptr;   // shared_tables: a trait-matrix batch's Sy, vy, shifts and limb panel on the device (ld_tmp)
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -1896,6 +1906,23 @@ static int ibs_fits(SharedCtx& c) {
               (unsigned long long)(r->d.A * r->mx_pitch + cell_bytes), (unsigned long long)(r->d.A * r->mx_pitch), (unsigned long long)cell_bytes, c.req.n_cols,
               c.req.n_cols, (unsigned long long)(cap >> 20));
 }
+// A trait-matrix association batch: the temporary matrix, the rows x K cells of 8 bytes, the rows' count records and the limb panel
+// together, under the same limit.
+static uint64_t am_meta_words(uint32_t K) { return (3ull * K + 1) & ~1ull; }   // Sy, vy and the shifts (8 bytes each), the panel behind them 16-byte aligned
+static int assoc_matrix_fits(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  r->mx_pitch = ((uint64_t)c.req.n_cols + 15) & ~15ull;
+  const uint64_t K = c.req.n_traits, panel_bytes = (uint64_t)c.req.am->tiles * kAmTileRows * r->mx_pitch;
+  const uint64_t row_bytes = r->mx_pitch + 8 * K + 16;   // (at most 16 + 2^22 + 2^19: no overflow below)
+  if (panel_bytes <= cap && r->d.A <= (cap - panel_bytes) / row_bytes) return VS_OK;
+  (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+  (void)hipStreamSynchronize(idx->stream);
+  return fail(VS_ERR_ARG, "a trait-matrix association scan of %llu rows x %u columns x %u traits takes %llu bytes (%llu of the genotype matrix it is formed from, "
+              "%llu of the cells, %llu of the count records, %llu of the limb panel), more than the limit of %llu MiB (option matrix_max_mib): split the batch or the traits",
+              (unsigned long long)r->d.A, c.req.n_cols, c.req.n_traits, (unsigned long long)(r->d.A * row_bytes + panel_bytes), (unsigned long long)(r->d.A * r->mx_pitch),
+              (unsigned long long)(r->d.A * 8 * K), (unsigned long long)(r->d.A * 16), (unsigned long long)panel_bytes, (unsigned long long)(cap >> 20));
+}
 // Reads the totals (*pt) or the speculation.  Leaves U / n_slow / n_runs, the result's sizes and bookkeeping, a speculative batch
 // registered with its slot, what the request's kind allocates, and the form of the rows and the expansion (n_fill .. lean).
 static int shared_tables(SharedCtx& c) {
@@ -1987,6 +2014,16 @@ static int shared_tables(SharedCtx& c) {
       VS_TRY(ralloc(r, r->ibs_words, &r->d_ibs));
       r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_ibs + head);
       r->ibs_stat = q.ibs_stat;
+      break;
+    }
+    case ReqKind::AssocMatrix: {   // (the traits' words and the limb panel are temporaries like the matrix: the kernel alone reads them)
+      VS_TRY(assoc_matrix_fits(c));
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(dev_alloc(idx, (size_t)(d.A * r->mx_pitch), (void**)&c.ld_matrix, &c.ld_tmp.bufs));
+      VS_TRY(dev_alloc(idx, (size_t)(am_meta_words(q.n_traits) * 8 + q.am->n_bytes()), (void**)&c.am_dev, &c.ld_tmp.bufs));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      VS_TRY(ralloc(r, (size_t)(d.A * q.n_traits), &r->d_scores));
+      VS_TRY(ralloc(r, 2, &r->d_cell_total));
       break;
     }
     case ReqKind::LdMatrix:   // (the temporary matrix and the cells wait for the blocks' sizes: ld_matrix_tables, behind the permutation)
@@ -2107,11 +2144,14 @@ static int shared_expand(SharedCtx& c) {
 // an LD batch: counts, temporary matrix, band.  Scores (behind the permutation): launch_scores, with its one host wait inside the pair.
 static int launch_scores(SharedCtx& c);
 static int ld_matrix_tables(SharedCtx& c);
+static int assoc_matrix_upload(SharedCtx& c);
+static int launch_assoc_matrix(SharedCtx& c);
 static int launch_ld_block(vs_index* idx, vs_result* r, const uint8_t* cells, const SharedReq& lq);
 static int shared_columns(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
   if (!c.behind_perm && !r->d.A) return VS_OK;
   if (c.req.kind == ReqKind::LdMatrix) VS_TRY(ld_matrix_tables(c));   // (its one host wait in front of the pair of events: they time kernels only)
+  if (c.req.kind == ReqKind::AssocMatrix) VS_TRY(assoc_matrix_upload(c));   // (in front of the pair of events as well)
   VS_TRY(result_events(r));
   HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
   if (c.req.kind == ReqKind::Groups) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, r->d_counts);
@@ -2127,6 +2167,9 @@ static int shared_columns(SharedCtx& c) {
   } else if (c.req.kind == ReqKind::LdMatrix) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_ld_block(idx, r, c.ld_matrix, c.req));
+  } else if (c.req.kind == ReqKind::AssocMatrix) {
+    VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+    VS_TRY(launch_assoc_matrix(c));
   } else if (c.req.kind == ReqKind::Gram) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_gram(idx, r, c.ld_matrix, c.req));
@@ -2283,6 +2326,46 @@ static int launch_ld_block(vs_index* idx, vs_result* r, const uint8_t* cells, co
   a.counts = r->d_counts; a.out = r->d_ldm;
   if (lq.ld_stat == VS_LD_R2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_block<true>), dim3((unsigned)r->ldm_wgs), dim3(256), 0, idx->stream, a);
   else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_block<false>), dim3((unsigned)r->ldm_wgs), dim3(256), 0, idx->stream, a);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+
+// A trait-matrix association batch: Sy, vy and the shifts of the K traits and the limb panel, from the host's memory to the buffer
+// shared_tables took from the pool.  The host's copy lives in the entry point's frame and an enqueued batch outlives that, so the
+// copy is waited for here.
+static int assoc_matrix_upload(SharedCtx& c) {
+  vs_index* idx = c.idx;
+  const AmPanel& p = *c.req.am;
+  const uint32_t K = c.req.n_traits;
+  if (!c.r->d.A) return VS_OK;
+  std::vector<uint64_t> meta(am_meta_words(K), 0);
+  memcpy(meta.data(), p.sy.data(), (size_t)K * 8);
+  memcpy(meta.data() + K, p.vy.data(), (size_t)K * 8);
+  memcpy(meta.data() + 2 * (size_t)K, p.shift.data(), (size_t)K * 4);
+  HIP_TRY(hipMemcpyAsync(c.am_dev, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, idx->stream));
+  HIP_TRY(hipMemcpyAsync(c.am_dev + meta.size(), p.bytes(), p.n_bytes(), hipMemcpyHostToDevice, idx->stream));
+  HIP_TRY(hipStreamSynchronize(idx->stream));
+  return VS_OK;
+}
+
+// The cells of a trait-matrix association batch from its temporary genotype matrix, the limb panel and the table's counts: one
+// workgroup per (64 table rows, 16 traits), the trait tile fastest, all in one launch.
+static int launch_assoc_matrix(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  const SharedReq& q = c.req;
+  if (!d.A) return VS_OK;
+  const uint32_t K = q.n_traits;
+  AssocMatrixArgs a{};
+  a.cells = c.ld_matrix; a.A = d.A; a.pitch = (uint32_t)r->mx_pitch; a.n_cols = q.n_cols; a.K = K; a.tiles = q.am->tiles;
+  a.sy = reinterpret_cast<const int64_t*>(c.am_dev); a.vy = reinterpret_cast<const double*>(c.am_dev + K);
+  a.shift = reinterpret_cast<const int32_t*>(c.am_dev + 2 * (size_t)K);
+  a.panel = reinterpret_cast<const int8_t*>(c.am_dev + am_meta_words(K));
+  a.counts = r->d_counts; a.out = r->d_scores;
+  const uint64_t wgs = (d.A + kAmRows - 1) / kAmRows * a.tiles;
+  if (wgs > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu workgroups): split the batch or the traits", (unsigned long long)wgs);
+  if (q.assoc_stat == VS_ASSOC_CHI2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_assoc_matrix<true>), dim3((unsigned)wgs), dim3(256), 0, idx->stream, a);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_assoc_matrix<false>), dim3((unsigned)wgs), dim3(256), 0, idx->stream, a);
   HIP_TRY(hipGetLastError());
   return VS_OK;
 }
@@ -3796,6 +3879,82 @@ int vs_query_assoc_scan(vs_index* idx, const vs_region* regions, uint64_t n, con
   });
 }
 
+int vs_assoc_matrix_quantise(const float* traits, uint64_t n, uint32_t n_traits, int32_t* q_out, int32_t* shift_out) {
+  if (!traits || !q_out || !shift_out) return fail(VS_ERR_ARG, "null argument");
+  if (n == 0 || n_traits == 0) return fail(VS_ERR_ARG, "an empty trait matrix (%llu rows x %u traits)", (unsigned long long)n, n_traits);
+  if (!am_quantise(traits, (size_t)n, n_traits, q_out, shift_out)) return fail(VS_ERR_ARG, "a trait value is not finite");
+  return VS_OK;
+}
+
+int vs_query_assoc_matrix(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, const float* traits, uint32_t n_traits,
+                          uint32_t stat, const char* const* trait_names, vs_result** out) {
+  if (!idx || !out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
+  if (n == 0) return fail(VS_ERR_ARG, "an association batch needs at least one region");
+  if (!traits) return fail(VS_ERR_ARG, "null argument: an association batch takes the samples' phenotype values");
+  if (n_traits == 0 || n_traits > VS_TRAIT_MATRIX_MAX) return fail(VS_ERR_ARG, "%u traits (1 .. %u)", n_traits, VS_TRAIT_MATRIX_MAX);
+  if (stat != VS_ASSOC_DOT && stat != VS_ASSOC_CHI2) return fail(VS_ERR_ARG, "association statistic %u is neither VS_ASSOC_DOT nor VS_ASSOC_CHI2", stat);
+  if (n_ids == 0) return fail(VS_ERR_ARG, "an empty list of samples: phenotypes of nobody");
+  const uint32_t ns = idx->g.num_samples;
+  if (!sample_ids && n_ids != (uint64_t)ns - 1)
+    return fail(VS_ERR_ARG, "without sample ids the phenotypes are the whole cohort's: %llu rows given, %u samples", (unsigned long long)n_ids, ns - 1);
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));   // (VS_ERR_UNKNOWN_SAMPLE: id 0 or an id beyond the cohort)
+  if (sample_ids && cols.size() != n_ids) {   // a sample listed twice: which of its phenotype rows would count?
+    std::vector<uint64_t> seen(mask.size(), 0);
+    for (uint64_t i = 0; i < n_ids; ++i) {
+      const uint32_t id = sample_ids[i];
+      if (seen[id >> 6] >> (id & 63) & 1) return fail(VS_ERR_ARG, "sample id %u is listed twice: a sample has one row of phenotypes", id);
+      seen[id >> 6] |= 1ull << (id & 63);
+    }
+  }
+  AmPanel panel;
+  {
+    const size_t bad = am_shifts(traits, (size_t)n_ids, n_traits, panel.shift);
+    if (bad != (size_t)n_ids * n_traits) {
+      const size_t i = bad / n_traits;
+      return fail(VS_ERR_ARG, "trait %u of sample id %u is not finite: pass the subset of samples that have a value", (uint32_t)(bad % n_traits),
+                  sample_ids ? sample_ids[i] : (uint32_t)i + 1);
+    }
+  }
+  std::vector<std::string> names;
+  if (trait_names)
+    for (uint32_t k = 0; k < n_traits; ++k) {
+      if (!trait_names[k]) return fail(VS_ERR_ARG, "null name of trait %u", k);
+      names.emplace_back(trait_names[k]);
+      if (names.back().find_first_of("\t\n") != std::string::npos) return fail(VS_ERR_ARG, "the name of trait %u holds a tab or a newline", k);
+    }
+  const size_t n_cols = cols.size();
+  if (n_cols >= kAmMaxCols)
+    return fail(VS_ERR_UNSUPPORTED, "%zu columns: a trait-matrix association scan takes fewer than 2^22 samples (a 32-bit limb sum could overflow beyond)", n_cols);
+  if (mask.size() * 8 > kMatrixMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", ns);
+  // the fixed-point traits as int8 limbs in column order, and their exact sums
+  std::vector<uint32_t> col_of;
+  if (sample_ids) {
+    col_of.resize(n_ids);
+    for (uint64_t i = 0; i < n_ids; ++i) {
+      const uint32_t id = sample_ids[i];
+      col_of[i] = rank[id >> 6] + (uint32_t)__builtin_popcountll(mask[id >> 6] & ((1ull << (id & 63)) - 1ull));
+    }
+  }
+  am_write_panel(traits, (size_t)n_ids, n_traits, sample_ids ? col_of.data() : nullptr, (n_cols + 15) & ~(size_t)15, panel);
+  std::vector<double> sum(n_traits), sumsq(n_traits);
+  for (uint32_t k = 0; k < n_traits; ++k) {
+    sum[k] = std::ldexp((double)panel.sy[k], -panel.shift[k]);
+    sumsq[k] = std::ldexp((double)panel.syy[k], -2 * panel.shift[k]);
+  }
+  SharedReq req = column_request(ReqKind::AssocMatrix, mask, rank, n_cols);
+  req.am = &panel; req.n_traits = n_traits; req.assoc_stat = stat;
+  return make_result(idx, kKindAssocMatrix, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    r->n_traits = n_traits; r->assoc_stat = stat;
+    r->trait_sum = sum; r->trait_sumsq = sumsq; r->trait_shift = panel.shift;
+    r->trait_names = names;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
 int vs_query_sample_scores(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, const float* weights, uint64_t n_weights,
                            uint32_t n_scores, const char* const* score_names, vs_result** out) {
   if (!idx || !out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
@@ -4259,7 +4418,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
     HIP_TRY(hipStreamSynchronize(idx->stream));
     tmp.release();
     r->n_variants = h[0]; r->n_carriers_kept = h[1]; r->n_bases = h[2];
-    if (r->kind == kKindCounts || r->kind == kKindAssoc) {   // the carriers that lie in the subset: the counts of the rows every region reports (dropped rows count 0)
+    if (r->kind == kKindCounts || r->kind == kKindAssoc || r->kind == kKindAssocMatrix) {   // the carriers that lie in the subset: the counts of the rows every region reports (dropped rows count 0)
       VS_TRY(fetch_region_meta(r));
       VS_TRY(counts_to_host(r));
       const uint4* c = (const uint4*)r->counts_pin.p;
@@ -4535,7 +4694,7 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
     if (len) *len = out.size();
     return VS_OK;
   }
-  if (r->kind == kKindAssoc) {   // the region's reported rows: the count text's columns, then the K cells
+  if (r->kind == kKindAssoc || r->kind == kKindAssocMatrix) {   // the region's reported rows: the count text's columns, then the K cells
     VS_TRY(array_to_host(r, r->d_scores, (size_t)(r->d.A * r->n_traits) * sizeof(double), &r->cells_pin, "association scores"));
     VS_TRY(counts_to_host(r));
     const VariantRow* rows;
@@ -4750,6 +4909,26 @@ int vs_result_get_assoc_scan(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, u
   if (n_traits) *n_traits = r->n_traits;
   if (stat) *stat = r->assoc_stat;
   if (col_ids) *col_ids = r->h_cols.data();
+  if (trait_sum) *trait_sum = r->trait_sum.data();
+  if (trait_sumsq) *trait_sumsq = r->trait_sumsq.data();
+  return VS_OK;
+}
+
+int vs_result_get_assoc_matrix(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* n_traits, uint32_t* stat, const uint32_t** col_ids, const int32_t** shift,
+                               const double** trait_sum, const double** trait_sumsq, const vs_allele_counts** counts, const double** scores) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!scores) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindAssocMatrix) return fail(VS_ERR_ARG, "not a trait-matrix association result (vs_query_assoc_matrix)");
+  VS_TRY(array_to_host(r, r->d_scores, (size_t)(r->d.A * r->n_traits) * sizeof(double), &r->cells_pin, "association scores"));
+  VS_TRY(counts_to_host(r));
+  *scores = (const double*)r->cells_pin.p;
+  if (counts) *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_traits) *n_traits = r->n_traits;
+  if (stat) *stat = r->assoc_stat;
+  if (col_ids) *col_ids = r->h_cols.data();
+  if (shift) *shift = r->trait_shift.data();
   if (trait_sum) *trait_sum = r->trait_sum.data();
   if (trait_sumsq) *trait_sumsq = r->trait_sumsq.data();
   return VS_OK;
@@ -4970,6 +5149,18 @@ int vs_result_sample_ibs_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols
 int vs_result_assoc_scan_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* n_traits, uint32_t* stat, const void** dev_counts,
                                 const void** dev_scores) {
   VS_TRY(device_matrix_ready(r, dev_scores, kKindAssoc, "not an association-scan result (vs_query_assoc_scan)"));
+  *dev_scores = r->d_scores;
+  if (dev_counts) *dev_counts = r->d_counts;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_traits) *n_traits = r->n_traits;
+  if (stat) *stat = r->assoc_stat;
+  return VS_OK;
+}
+
+int vs_result_assoc_matrix_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* n_traits, uint32_t* stat, const void** dev_counts,
+                                  const void** dev_scores) {
+  VS_TRY(device_matrix_ready(r, dev_scores, kKindAssocMatrix, "not a trait-matrix association result (vs_query_assoc_matrix)"));
   *dev_scores = r->d_scores;
   if (dev_counts) *dev_counts = r->d_counts;
   if (n_rows) *n_rows = r->d.A;

@@ -76,6 +76,10 @@
 // k_ld_block            D D^T in full per region: the m x m block of every region of a batch, a pair of 64-row tiles per workgroup,
 //  k_ld_block_scan       found by bisection over the scan of the regions' workgroups; k_ld_band's staging, fragments and r^2, both
 //                       triangles stored once with plain stores (vs_query_ld_matrix: no reference counterpart)
+// k_assoc_matrix        D Y over the same dosages: table rows x K traits (K up to 65,536) given as four int8 limbs of a fixed-point
+//                       value, 64 rows x 16 traits per workgroup, k_ld_band's staging and fragments, four MFMAs per 64-column step,
+//                       the limb sums combined in int64: exact dot products or the score test from 128-bit integers
+//                       (vs_query_assoc_matrix: no reference counterpart)
 // k_sample_gram         D^T D over the same dosages, the samples x samples Gram matrix: a pair of 128-column tiles and a chunk of
 //  k_gram_moments       table rows per workgroup, the tiles transposed into LDS, v_mfma_i32_16x16x64_i8, 64-bit integer atomics;
 //  k_gram_finish        the count-weighted column sums s, C and H; the GRM cells from 128-bit integers (vs_query_sample_gram: no
@@ -104,5 +108,7 @@
 #include "k_matrix.hip.h"
 #include "k_ld.hip.h"
 #include "k_ld_block.hip.h"
+#include "k_int128.hip.h"
 #include "k_gram.hip.h"
+#include "k_assoc_matrix.hip.h"
 #include "k_ibs.hip.h"
