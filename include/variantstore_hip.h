@@ -360,6 +360,45 @@ int vs_result_get_sample_scores(vs_result* r, uint64_t* n_cols, uint32_t* n_scor
 /* The cells as they lie in HBM: n_cols x n_scores int64 sums and float64 scores, row-major (dev_sums may be NULL), valid until
  * vs_result_free.  The engine has synchronised its stream when this returns: the caller needs no event. */
 int vs_result_sample_scores_device(vs_result* r, uint64_t* n_cols, uint32_t* n_scores, const void** dev_sums, const void** dev_scores);
+/* Score matrix: vs_query_sample_scores for a WIDE panel of weight columns, 1 <= n_scores <= VS_SCORE_MATRIX_MAX -- a cohort against
+ * dozens of polygenic score files, a projection onto PCA loadings, the second half of a randomised-SVD step on the vectors
+ * vs_query_assoc_matrix produced -- as the product D^T W of the dosage matrix with the weights on the matrix cores (no reference
+ * counterpart).  regions, the subset S and its n columns, the dosage, dropped rows, score_names and the report-keyed `weights`
+ * (n_weights x n_scores float32, row-major, entry off[q] + j for the j-th row region q reports; a shared row takes part once per
+ * report with that report's weight) are vs_query_sample_scores'.  The weights are in HOST memory.
+ * Fixed point is the trait quantiser's (vs_assoc_matrix_quantise over the N x n_scores weights gives q and f): per column k, M_k =
+ * max |w| = m 2^e (frexp), f_k = 30 - e (0 for a column of zeros), q = rint((double)w 2^f_k), ties to even, |q| < 2^30.
+ * sums[c * n_scores + k] = the sum over the reports of d(row(report), column c) q_k(report), an exact int64 (|sum| <= 2 x 2^30 x N
+ * < 2^57); scores[c * n_scores + k] = ldexp((double)sums, -f_k), one rounding.  No floating-point value is summed: the same call
+ * gives the same bytes under every option setting, with or without share_lists.  Any term is off by at most d 2^(e - 31).
+ * The kernel multiplies by the per-row totals T[row][k] = the sum of q_k over the row's reports, split into balanced base-256 int8
+ * limbs: four hold |T| <= 2,139,062,143 (every batch in which no row is reported twice), five up to 547,599,908,735; the engine
+ * runs four where the batch's largest |T| allows it, else five, and the result records which (limbs).  |T| > 2^38 -- more than 256
+ * regions reporting one row -- is refused with VS_ERR_UNSUPPORTED: split the batch.
+ * Refused on the host, in this order, before the handle's device is asked for: n_scores outside 1 .. VS_SCORE_MATRIX_MAX ->
+ * VS_ERR_ARG; a weight that is not finite -> VS_ERR_ARG, the message names the column; a score name with a tab or a newline ->
+ * VS_ERR_ARG; ids as vs_query_sample_scores refuses them (none, an id twice -> VS_ERR_ARG; id 0 or beyond the cohort ->
+ * VS_ERR_UNKNOWN_SAMPLE); n_weights >= 2^26 -> VS_ERR_ARG.  A handle opened without a device reports these first and
+ * VS_ERR_NO_DEVICE otherwise.  Then, after the plan's one host wait: n_weights != N -> VS_ERR_ARG, the message gives both numbers;
+ * N >= 2^26 -> VS_ERR_ARG; and the batch's buffers -- the temporary genotype matrix (rows x pitch, pitch = n rounded up to 16), the
+ * uploaded weights (N x n_scores x 4), T (rows x n_scores x 8), the limb panel (ceil(n_scores / 16) x 16 x 5 x rows rounded up to
+ * 128: it is laid out for five limbs) and the sums and scores (n x n_scores x 16) -- together are held to option "matrix_max_mib":
+ * a larger request is refused with VS_ERR_ARG before anything of it is allocated; the message gives the parts in bytes.
+ * A batch whose table is empty gives all-zero cells and is no error.  Never speculative; the handle's type-6 state stays as it
+ * was.  The result is a score result in everything else (per-region arrays and variant table, no arena, vs_result_format_region's
+ * "Pos\tRef\tAlt" lines, vs_result_fill_ms its own pair of events), but vs_result_totals' n_carriers is what a Gram result
+ * reports: the nonzero cells of the temporary matrix.  The two accessors below answer VS_ERR_ARG on every other kind of result;
+ * every other kind's getter, vs_result_get_sample_scores included, answers VS_ERR_ARG on this one. */
+#define VS_SCORE_MATRIX_MAX 65536u
+int vs_query_score_matrix(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids,
+                          const float* weights, uint64_t n_weights, uint32_t n_scores, const char* const* score_names, vs_result** out);
+/* Host copies in page-locked memory owned by the result: sums and scores [n_cols x n_scores], shift the n_scores values f_k, limbs
+ * (4 or 5), col_ids the n_cols column ids (any may be NULL but not both sums and scores). */
+int vs_result_get_score_matrix(vs_result* r, uint64_t* n_cols, uint32_t* n_scores, const uint32_t** col_ids, const int32_t** shift,
+                               uint32_t* limbs, const int64_t** sums, const double** scores);
+/* The cells as they lie in HBM: n_cols x n_scores int64 sums and float64 scores, row-major (dev_sums may be NULL), valid until
+ * vs_result_free.  The engine has synchronised its stream when this returns: the caller needs no event. */
+int vs_result_score_matrix_device(vs_result* r, uint64_t* n_cols, uint32_t* n_scores, const void** dev_sums, const void** dev_scores);
 /* Per-sample burden over regions: the counts above along the other axis -- a regions x samples matrix, the input of gene-burden
  * and collapsing tests and of per-sample QC counts (no reference counterpart: what a caller of type 6 would reduce on the host
  * from every carrier list).  Let R(q) be the rows type 6 reports for region q (same order, duplicate rule and region flags; a
@@ -826,6 +865,9 @@ void vs_comm_destroy(vs_comm* c);
  *   "score_chunk"     table rows one workgroup of the score kernel walks (vs_query_sample_scores).  0 (default): 4096; else 64..65536
  *   "gram_chunk"      table rows one workgroup of the Gram kernel sums (vs_query_sample_gram).  0 (default): by the batch's shape,
  *                     about 256 workgroups; else 64..65536.  The sums are the same integers under every setting
+ *   "score_matrix_chunk" table rows one workgroup of the score-matrix kernel sums (vs_query_score_matrix).  0 (default): by the
+ *                     batch's shape, about 1024 workgroups; else a multiple of 128 in 128..65536.  The sums are the same integers
+ *                     under every setting
  *   "ibs_chunk"       table rows one workgroup of the IBS kernel sums (vs_query_sample_ibs).  0 (default): by the batch's shape,
  *                     about 128 workgroups; else 64..65536.  The sums are the same integers under every setting
  *   "score_tile_cols" columns of a workgroup's tile of the score kernel: 0 (default): all that 64 KiB of int64 cells hold,

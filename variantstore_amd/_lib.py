@@ -116,6 +116,12 @@ SYMBOLS = {
     "vs_result_get_sample_scores": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)),
                                               C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.POINTER(C.c_double))]),
     "vs_result_sample_scores_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "vs_query_score_matrix": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_float), C.c_uint64, C.c_uint32,
+                                        C.POINTER(C.c_char_p), C.POINTER(_P)]),
+    "vs_result_get_score_matrix": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)),
+                                             C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_int64)),
+                                             C.POINTER(C.POINTER(C.c_double))]),
+    "vs_result_score_matrix_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "vs_query_sample_burden": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.c_uint32,
                                          C.POINTER(_P)]),
     "vs_result_get_sample_burden": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.POINTER(C.c_uint32)),

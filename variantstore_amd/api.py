@@ -432,6 +432,39 @@ class QueryResult:
                "vs_result_sample_scores_device")
         return int(ps.value or 0), int(pu.value or 0), int(c.value), int(k.value)
 
+    def score_matrix(self):
+        """A score-matrix result (VariantStore.score_matrix) as numpy arrays: `scores` ((n, K) float64), `sums` ((n, K) int64: the
+        same sums in fixed point, exact), `shift` (int32[K]: scores = ldexp(sums, -shift)) and `limbs` (4 or 5: the int8 limbs the
+        kernel split the rows' weight totals into), `col_ids` (uint32[n], the sample ids of the columns, ascending) and their
+        `names`, `score_names` (list of K strings), the table's `rows` and per region `row_begin`, `row_count` and `flags`.
+        Copies, valid after the result is closed."""
+        c, k, lb = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        cols = C.POINTER(C.c_uint32)()
+        sh = C.POINTER(C.c_int32)()
+        su = C.POINTER(C.c_int64)()
+        sc = C.POINTER(C.c_double)()
+        _check(self._lib.vs_result_get_score_matrix(self._h, C.byref(c), C.byref(k), C.byref(cols), C.byref(sh), C.byref(lb), C.byref(su),
+                                                    C.byref(sc)), "vs_result_get_score_matrix")
+        nc, nk = int(c.value), int(k.value)
+        raw = self.raw(with_carriers=False)
+        col_ids = np.ctypeslib.as_array(cols, shape=(nc,)).copy()
+        given = getattr(self, "score_names", None)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "flags": raw["region_flags"].copy(), "col_ids": col_ids, "names": [self._store.sample_name(int(i)) for i in col_ids],
+                "shift": np.ctypeslib.as_array(sh, shape=(nk,)).copy(), "limbs": int(lb.value),
+                "sums": np.ctypeslib.as_array(su, shape=(nc * nk,)).reshape(nc, nk).copy(),
+                "scores": np.ctypeslib.as_array(sc, shape=(nc * nk,)).reshape(nc, nk).copy(),
+                "score_names": list(given) if given else [str(i) for i in range(nk)]}
+
+    def score_matrix_device(self):
+        """(scores address, sums address, n_cols, n_scores) of a score-matrix result as it lies in this GPU's memory:
+        n_cols x n_scores float64 scores and int64 sums, row-major, complete when this returns and valid until the result is closed."""
+        c, k = C.c_uint64(), C.c_uint32()
+        pu, ps = C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_score_matrix_device(self._h, C.byref(c), C.byref(k), C.byref(pu), C.byref(ps)),
+               "vs_result_score_matrix_device")
+        return int(ps.value or 0), int(pu.value or 0), int(c.value), int(k.value)
+
     BURDEN_DTYPE = np.dtype([("variants", "<u4"), ("alt_alleles", "<u4"), ("hom_alt", "<u4"), ("phased", "<u4")])
 
     def sample_burden(self):
@@ -1174,6 +1207,43 @@ class VariantStore:
         h = C.c_void_p()
         _check(self._lib.vs_query_sample_scores(self._h, ptr, n, ids_ptr, n_ids, w_ptr, n_w, k, name_arr, C.byref(h)), "vs_query_sample_scores")
         del keep
+        res = QueryResult(self, h)
+        res.score_names = names
+        res.unmatched = unmatched
+        return res
+
+    def score_matrix(self, regions, weights, samples=None, score_names=None) -> QueryResult:
+        """Score matrix over regions (vs_query_score_matrix): sample_scores for a wide panel of weight columns, 1 .. 65,536, as a
+        product with the temporary genotype matrix on the matrix cores.  `regions`, `samples`, `score_names` and `weights` -- an
+        array-like of shape (N,) or (N, K), float32, in report order, or a mapping {(pos, ref, alt): value or K values}, with
+        `result.unmatched` -- are sample_scores'; the weights are host memory.  The sums are taken in fixed point (the weights of a
+        column are quantised to 2^-30 of the column's largest): the same call gives the same bytes.  Read the result with
+        QueryResult.score_matrix / score_matrix_device."""
+        names = [str(s) for s in score_names] if score_names is not None else None
+        unmatched = None
+        if isinstance(weights, dict):
+            weights, unmatched = self._weights_from_mapping(regions, weights)
+        if isinstance(weights, DeviceArray):
+            raise ValueError("score_matrix takes its weights from host memory")
+        w = np.asarray(weights, dtype=np.float32)
+        if w.ndim == 1:
+            w = w.reshape(-1, 1)
+        if w.ndim != 2:
+            raise ValueError("weights: an array of shape (N,) or (N, K), or a mapping")
+        w = np.ascontiguousarray(w)
+        k = w.shape[1]
+        if names is not None and len(names) != k:
+            raise ValueError(f"{len(names)} score names for {k} weight columns")
+        arr, ptr, n = _regions_array(regions)
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        if samples is None:
+            if getattr(self, "_cohort", None) is None:
+                self._cohort = self.info().num_samples - 1
+            n_ids = self._cohort
+        name_arr = (C.c_char_p * len(names))(*[s.encode() for s in names]) if names else None
+        h = C.c_void_p()
+        w_ptr = w.ctypes.data_as(C.POINTER(C.c_float)) if w.size else None
+        _check(self._lib.vs_query_score_matrix(self._h, ptr, n, ids_ptr, n_ids, w_ptr, w.shape[0], k, name_arr, C.byref(h)), "vs_query_score_matrix")
         res = QueryResult(self, h)
         res.score_names = names
         res.unmatched = unmatched

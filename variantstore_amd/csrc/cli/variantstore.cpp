@@ -912,7 +912,20 @@ int score_usage() {
   return EXIT_FAILURE;
 }
 
-int score_main(const Args& a) {
+// `variantstore scorematrix`: the same over any number of weight columns up to VS_SCORE_MATRIX_MAX, as a product on the matrix cores
+// (vs_query_score_matrix); the weights file, its header line, the warning about unmatched variants and the output are `score`'s.
+int scorematrix_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore scorematrix -p <output-prefix> -r <region> -W <weights-file> [-S <samples-file>] [-o <outfile>] [--device <n>]\n\n"
+               "        For every sample (of the file: one name per line; default: the whole cohort) any number of weighted sums of its\n"
+               "        dosages over the variants query type 6 reports in the regions, as one matrix product.  The weights file holds one\n"
+               "        `pos ref alt weight [weight ...]` line per variant; a first line `#pos ref alt name1 name2 ...` names the scores.\n";
+  return EXIT_FAILURE;
+}
+
+int score_main(const Args& a, bool matrix = false) {
+  const size_t max_scores = matrix ? VS_SCORE_MATRIX_MAX : VS_SCORES_MAX;
+  const char* const what = matrix ? "scorematrix" : "score";
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
   if (rc != VS_OK) die(rc, "load");
@@ -941,7 +954,7 @@ int score_main(const Args& a) {
     if (f.empty()) continue;
     if (f[0] == "#pos") {
       if (!key_row.empty() || !names.empty() || f.size() < 4) return fail_with(at + ": a `#pos ref alt name ...` line comes first and once");
-      if (f.size() - 3 > VS_SCORES_MAX) return fail_with(at + ": more than " + std::to_string(VS_SCORES_MAX) + " values");
+      if (f.size() - 3 > max_scores) return fail_with(at + ": more than " + std::to_string(max_scores) + " values");
       names.assign(f.begin() + 3, f.end());
       K = names.size();
       continue;
@@ -952,7 +965,7 @@ int score_main(const Args& a) {
     if (end == f[0].c_str() || *end) return fail_with(at + ": malformed line, not a position: " + f[0]);
     if (!K) K = f.size() - 3;
     if (f.size() - 3 != K) return fail_with(at + ": " + std::to_string(f.size() - 3) + " values, " + std::to_string(K) + " expected");
-    if (K > VS_SCORES_MAX) return fail_with(at + ": more than " + std::to_string(VS_SCORES_MAX) + " values");
+    if (K > max_scores) return fail_with(at + ": more than " + std::to_string(max_scores) + " values");
     auto allele = [](const std::string& x) { return x == "-" || x == "." ? std::string() : x; };   // (an empty allele, as the texts print a deletion's)
     const std::string key = std::to_string(pos) + "\t" + allele(f[1]) + "\t" + allele(f[2]);
     if (!key_row.emplace(key, table.size() / K).second) return fail_with(at + ": the variant is listed twice: " + f[0] + " " + f[1] + " " + f[2]);
@@ -985,7 +998,7 @@ int score_main(const Args& a) {
   // the reported rows, region after region: a count batch's text
   vs_result* cres = nullptr;
   rc = vs_query_allele_counts(idx, batch.data(), batch.size(), nullptr, 0, &cres);
-  if (rc != VS_OK) die(rc, "score");
+  if (rc != VS_OK) die(rc, what);
   std::vector<float> weights;
   std::vector<uint8_t> matched(key_row.size(), 0);
   for (size_t i = 0; i < batch.size(); ++i) {
@@ -1014,14 +1027,16 @@ int score_main(const Args& a) {
   std::vector<const char*> name_ptrs;
   for (auto& n : names) name_ptrs.push_back(n.c_str());
   vs_result* res = nullptr;
-  rc = vs_query_sample_scores(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.empty() ? info.num_samples - 1 : ids.size(), weights.data(),
-                              weights.size() / K, (uint32_t)K, names.empty() ? nullptr : name_ptrs.data(), &res);
-  if (rc != VS_OK) die(rc, "score");
+  rc = (matrix ? vs_query_score_matrix : vs_query_sample_scores)(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(),
+                                                                 ids.empty() ? info.num_samples - 1 : ids.size(), weights.data(), weights.size() / K, (uint32_t)K,
+                                                                 names.empty() ? nullptr : name_ptrs.data(), &res);
+  if (rc != VS_OK) die(rc, what);
   uint64_t n_cols = 0;
   uint32_t n_scores = 0;
   const uint32_t* cols = nullptr;
   const double* sc = nullptr;
-  rc = vs_result_get_sample_scores(res, &n_cols, &n_scores, &cols, nullptr, nullptr, &sc);
+  rc = matrix ? vs_result_get_score_matrix(res, &n_cols, &n_scores, &cols, nullptr, nullptr, nullptr, &sc)
+              : vs_result_get_sample_scores(res, &n_cols, &n_scores, &cols, nullptr, nullptr, &sc);
   if (rc != VS_OK) die(rc, "result");
   std::ofstream file;
   if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
@@ -1268,7 +1283,7 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "gram" || a.cmd == "ibs") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
@@ -1287,7 +1302,7 @@ int main(int argc, char** argv) {
       else if (a.cmd == "groups" && (f == "-G" || f == "--groups")) a.groups_file = need(i);
       else if ((a.cmd == "assoc" || a.cmd == "assocmatrix") && (f == "-P" || f == "--phenotypes")) a.pheno_file = need(i);
       else if ((a.cmd == "assoc" || a.cmd == "assocmatrix") && f == "--chi2") a.assoc_chi2 = true;
-      else if (a.cmd == "score" && (f == "-W" || f == "--weights")) a.weights_file = need(i);
+      else if ((a.cmd == "score" || a.cmd == "scorematrix") && (f == "-W" || f == "--weights")) a.weights_file = need(i);
       else if (a.cmd != "groups" && a.cmd != "assoc" && a.cmd != "assocmatrix" && (f == "-S" || f == "--samples")) a.samples_file = need(i);
       else if (f == "-o" || f == "--output_file") a.outfile = need(i);
       else if (f == "--device") a.device = atoi(need(i).c_str());
@@ -1309,6 +1324,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "assoc") {
     if (a.prefix.empty() || a.region.empty() || a.pheno_file.empty()) return assoc_usage();
     return assoc_main(a);
+  }
+  if (a.cmd == "scorematrix") {
+    if (a.prefix.empty() || a.region.empty() || a.weights_file.empty()) return scorematrix_usage();
+    return score_main(a, true);
   }
   if (a.cmd == "score") {
     if (a.prefix.empty() || a.region.empty() || a.weights_file.empty()) return score_usage();

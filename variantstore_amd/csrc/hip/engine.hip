@@ -93,6 +93,7 @@ struct EngineOpts {
   uint32_t score_chunk = 0;     // table rows one workgroup of k_sample_scores walks: 0 = kScoreChunkRows, else 64..65536
   uint32_t score_tile_cols = 0; // column tile of k_sample_scores: 0 = all a 64 KiB tile holds, 65536 / (8 Kp); else a multiple of 16, held to that
   uint32_t gram_chunk = 0;      // table rows one workgroup of k_sample_gram sums: 0 = by the batch's shape (gram_chunk_rows), else 64..65536
+  uint32_t score_matrix_chunk = 0;   // table rows one workgroup of k_score_matrix sums: 0 = by the batch's shape (score_matrix_chunk_rows), else a multiple of 128 in 128..65536
   uint32_t ibs_chunk = 0;       // table rows one workgroup of k_sample_ibs sums: 0 = by the batch's shape (ibs_chunk_rows), else 64..65536
   uint32_t matrix_tile_cols = 0;   // column tile of the matrix kernel: 0 = kMatrixTileCols, else a multiple of 16 in 16..65536
   int fill_mode = 0;            // shared expansion: 0 one launch, 2 split (lists + rows, then the dense sites: what a profiler wants to see apart)
@@ -246,7 +247,8 @@ struct vs_result {
   int kind = 0;  // 7: samples_has_var result (vs_result_format_region writes the sample line); 2 / 3: sequences; kKindCounts: allele counts;
                  // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts; kKindAssoc: association scan;
                  // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM; kKindIbs: pairwise IBS counts / KING kinship;
-                 // kKindLdMatrix: the full LD block of every region; kKindAssocMatrix: trait-matrix association scan
+                 // kKindLdMatrix: the full LD block of every region; kKindAssocMatrix: trait-matrix association scan;
+                 // kKindScoreMatrix: score matrix
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -274,6 +276,10 @@ struct vs_result {
   uint32_t n_scores = 0;
   std::vector<int32_t> score_shift;
   std::vector<std::string> score_names;
+  // score-matrix results (vs_query_score_matrix): d_sums / d_score_out, h_cols, n_scores (up to VS_SCORE_MATRIX_MAX), score_shift and
+  // score_names as for a score result; the limbs the kernel ran with (4 or 5); the nonzero cells of the (temporary) genotype matrix
+  // in d_cell_total (two words of their own); the count record of every table row in d_counts as for a Gram result
+  uint32_t sm_limbs = 0;
   // burden results (vs_query_sample_burden): the regions x columns matrix in HBM (16 bytes per cell, row-major), the sum of its
   // `variants` (a device word the kernels add to), the column ids, and the matrix's page-locked host copy
   uint4* d_cells = nullptr;
@@ -334,8 +340,9 @@ constexpr int kKindGram = 15;    // ... of a Gram result: the rows of type 6, a 
 constexpr int kKindIbs = 16;     // ... of an IBS result: the rows of type 6, samples x samples matrices of genotype-state counts instead of carrier lists
 constexpr int kKindLdMatrix = 17;   // ... of an LD-matrix result: the rows of type 6, a square block of pair statistics per region instead of carrier lists
 constexpr int kKindAssocMatrix = 18;   // ... of a trait-matrix association result: the rows of type 6, a score per row and trait (up to VS_TRAIT_MATRIX_MAX traits) instead of carrier lists
+constexpr int kKindScoreMatrix = 19;   // ... of a score-matrix result: the rows of type 6, a columns x scores matrix of weighted dosage sums (up to VS_SCORE_MATRIX_MAX scores) instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
+  return r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
          r->kind == kKindScores;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
@@ -348,6 +355,8 @@ static int refuse_no_lists(const vs_result* r, const char* what) {
     return fail(VS_ERR_UNSUPPORTED, "%s: a trait-matrix association result holds a score per row and trait, no carrier lists (vs_result_get_assoc_matrix)", what);
   if (r->kind == kKindScores)
     return fail(VS_ERR_UNSUPPORTED, "%s: a per-sample score result holds a score per sample and weight column, no carrier lists (vs_result_get_sample_scores)", what);
+  if (r->kind == kKindScoreMatrix)
+    return fail(VS_ERR_UNSUPPORTED, "%s: a score-matrix result holds a score per sample and weight column, no carrier lists (vs_result_get_score_matrix)", what);
   if (r->kind == kKindGram)
     return fail(VS_ERR_UNSUPPORTED, "%s: a Gram result holds a samples x samples matrix of dosage products, no carrier lists (vs_result_get_sample_gram)", what);
   if (r->kind == kKindIbs)
@@ -1217,7 +1226,9 @@ static int capture_totals(vs_result* r) {
 // Gram, Ibs: mask, rank and n_cols as for the matrix; the statistic.  LdMatrix: as LD without a window (ld_stat).
 // AssocMatrix: mask, rank and n_cols as for the matrix; `am` is the host's limb panel with the traits' shifts and sums (it goes to
 // the device once the batch has passed the size limit: assoc_matrix_upload); the traits and the statistic.
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix };
+// ScoreMatrix: mask, rank and n_cols as for the matrix; `weights` (host memory), n_weights and n_scores as for Scores; `sm_shift`: f_k
+// per weight column, formed on the host.
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1233,6 +1244,7 @@ struct SharedReq {
   uint64_t n_weights = 0;
   uint32_t n_scores = 0, score_max_bits[kScoresMax] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool weights_on_device = false;
+  const std::vector<int32_t>* sm_shift = nullptr;
   bool window() const { return min_ac != 0 || max_ac != UINT32_MAX; }
 };
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
@@ -1648,7 +1660,7 @@ struct SharedCtx {
   uint64_t* am_dev = nullptr;   // shared_tables: a trait-matrix batch's Sy, vy, shifts and limb panel on the device (ld_tmp)
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -2026,6 +2038,12 @@ static int shared_tables(SharedCtx& c) {
       VS_TRY(ralloc(r, 2, &r->d_cell_total));
       break;
     }
+    case ReqKind::ScoreMatrix:   // (the temporary matrix, the sums and what they are formed from wait for the number of reports: launch_score_matrix)
+      r->mx_pitch = ((uint64_t)q.n_cols + 15) & ~15ull;
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      VS_TRY(ralloc(r, 2, &r->d_cell_total));
+      break;
     case ReqKind::LdMatrix:   // (the temporary matrix and the cells wait for the blocks' sizes: ld_matrix_tables, behind the permutation)
       r->mx_pitch = ((uint64_t)q.n_cols + 15) & ~15ull;
       VS_TRY(ralloc(r, d.A, &d.rows));
@@ -2143,6 +2161,7 @@ static int shared_expand(SharedCtx& c) {
 // table.  Assoc: k_allele_counts over the table, then k_assoc_scan.  Burden, Matrix, LD (behind the permutation): a burden filter's counts are inside the pair, and so are the three launches of
 // an LD batch: counts, temporary matrix, band.  Scores (behind the permutation): launch_scores, with its one host wait inside the pair.
 static int launch_scores(SharedCtx& c);
+static int launch_score_matrix(SharedCtx& c);
 static int ld_matrix_tables(SharedCtx& c);
 static int assoc_matrix_upload(SharedCtx& c);
 static int launch_assoc_matrix(SharedCtx& c);
@@ -2155,11 +2174,12 @@ static int shared_columns(SharedCtx& c) {
   VS_TRY(result_events(r));
   HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
   if (c.req.kind == ReqKind::Groups) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, r->d_counts);
-  else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD, Gram, Ibs; Burden only under a window: shared_tables gives it counts)
+  else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD, Gram, Ibs, ScoreMatrix; Burden only under a window: shared_tables gives it counts)
     launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
   HIP_TRY(hipGetLastError());
   if (c.req.kind == ReqKind::Assoc) VS_TRY(launch_assoc(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.d_pheno, c.req));
   if (c.req.kind == ReqKind::Scores) VS_TRY(launch_scores(c));
+  if (c.req.kind == ReqKind::ScoreMatrix) VS_TRY(launch_score_matrix(c));
   if (c.req.kind == ReqKind::Burden) VS_TRY(launch_burden(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.req, c.scratch));
   if (c.req.kind == ReqKind::LD) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
@@ -2279,6 +2299,111 @@ static int launch_scores(SharedCtx& c) {
     }
   }
   hipLaunchKernelGGL(k_score_finish, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, idx->stream, (const long long*)r->d_sums, cells, K, sh, r->d_score_out);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+
+// Table rows per workgroup of k_score_matrix.  Option score_matrix_chunk, or by the batch's shape as gram_chunk_rows: the chunk that
+// gives about kSmBlocksWanted workgroups over all (score tile group, column tile) pairs, a multiple of kGramK, at least 2 kGramK
+// (fewer rows per workgroup only add atomics) and at most kSmChunkMax.
+static uint32_t score_matrix_chunk_rows(const vs_index* idx, uint64_t A, uint64_t n_pairs) {
+  if (idx->opts.score_matrix_chunk) return idx->opts.score_matrix_chunk;
+  const uint64_t per = (A * n_pairs + kSmBlocksWanted - 1) / kSmBlocksWanted;
+  const uint64_t rows = (per + kGramK - 1) / kGramK * kGramK;
+  return (uint32_t)std::min<uint64_t>(kSmChunkMax, std::max<uint64_t>(2 * kGramK, rows));
+}
+// A score-matrix batch behind the permutation (the per-region arrays are in the caller's order).  The reports' offsets come back in a
+// first host wait (the batch is never speculative) and the number of reports is held against n_weights, then the whole batch against
+// option matrix_max_mib, before anything of it is allocated.  Then the temporary matrix, the weights' row totals T and the limb
+// panel; the largest |T| comes back in a second wait -- the call refuses a batch beyond 2^38, so the host has to see it, and the
+// matrix kernel is then picked by the limbs the batch needs --; the product and the scores.
+static int launch_score_matrix(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  const SharedReq& q = c.req;
+  const uint32_t K = q.n_scores;
+  uint64_t* off = nullptr;
+  VS_TRY(dev_alloc(idx, (d.Q + 1) * 8, (void**)&off, &c.scratch.bufs));
+  hipLaunchKernelGGL(k_score_offsets, dim3(1), dim3(kScoreOffBlock), 0, idx->stream, (const uint64_t*)d.var_count, d.Q, off);
+  HIP_TRY(hipGetLastError());
+  uint64_t N = 0;
+  HIP_TRY(hipMemcpyAsync(&N, off + d.Q, 8, hipMemcpyDeviceToHost, idx->stream));
+  HIP_TRY(hipStreamSynchronize(idx->stream));
+  if (N != q.n_weights)
+    return fail(VS_ERR_ARG, "%llu rows of weights for the %llu rows the regions report: one row of weights per reported row, in report order",
+                (unsigned long long)q.n_weights, (unsigned long long)N);
+  if (N >= kSmMaxReports)
+    return fail(VS_ERR_ARG, "%llu reported rows: a score-matrix batch takes fewer than 2^26 (the 64-bit sums could overflow beyond): split the batch", (unsigned long long)N);
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  const uint64_t cells = (uint64_t)q.n_cols * K, apad = (d.A + 127) & ~127ull, tiles = (K + kSmScoreTile - 1) / kSmScoreTile;
+  // (the table's rows are slots of the regions, N of them and the dropped ones: with N < 2^26, K <= 2^16 and a pitch below 2^32 every part stays far below 2^63)
+  const uint64_t b_matrix = d.A * r->mx_pitch, b_weights = N * K * 4, b_totals = d.A * K * 8, b_panel = tiles * kSmScoreTile * kSmLimbsMax * apad, b_cells = cells * 16;
+  const uint64_t need = b_matrix + b_weights + b_totals + b_panel + b_cells;
+  if (need > cap)
+    return fail(VS_ERR_ARG, "a score-matrix batch of %llu reports x %u scores over %llu rows and %u columns takes %llu bytes (%llu of the genotype matrix it is formed from, "
+                "%llu of the weights, %llu of the rows' totals, %llu of the limb panel, %llu of the sums and scores), more than the limit of %llu MiB (option matrix_max_mib): "
+                "split the batch or the scores", (unsigned long long)N, K, (unsigned long long)d.A, q.n_cols, (unsigned long long)need, (unsigned long long)b_matrix,
+                (unsigned long long)b_weights, (unsigned long long)b_totals, (unsigned long long)b_panel, (unsigned long long)b_cells, (unsigned long long)(cap >> 20));
+  VS_TRY(ralloc(r, (size_t)cells * 2, &r->d_sums));
+  r->d_score_out = reinterpret_cast<double*>(r->d_sums + cells);
+  HIP_TRY(hipMemsetAsync(r->d_sums, 0, cells * 16, idx->stream));   // (the scores of an all-zero batch are +0.0: the same bytes)
+  r->sm_limbs = 4;
+  VS_TRY(dev_alloc(idx, (size_t)b_matrix, (void**)&c.ld_matrix, &c.ld_tmp.bufs));
+  VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, q));
+  if (!N || !d.A) return VS_OK;
+  // ---- the weights and their shifts to the device, the rows' totals, the limb panel ----
+  int32_t* shift = nullptr;
+  float* dw = nullptr;
+  long long* T = nullptr;
+  int8_t* panel = nullptr;
+  unsigned long long* meta = nullptr;
+  const uint64_t lrows = apad / kSmLimbRows, lcols = (tiles * kSmScoreTile + kSmLimbCols - 1) / kSmLimbCols;
+  if (lrows > 0x7FFFFFFFull || lcols > 65535) return fail(VS_ERR_ARG, "batch too large for one launch (%llu row blocks of the limb panel)", (unsigned long long)lrows);
+  VS_TRY(dev_alloc(idx, (size_t)K * 4 + 16, (void**)&shift, &c.ld_tmp.bufs));
+  VS_TRY(dev_alloc(idx, (size_t)b_weights, (void**)&dw, &c.ld_tmp.bufs));
+  VS_TRY(dev_alloc(idx, (size_t)b_totals + 8, (void**)&T, &c.ld_tmp.bufs));
+  VS_TRY(dev_alloc(idx, (size_t)b_panel, (void**)&panel, &c.ld_tmp.bufs));
+  meta = reinterpret_cast<unsigned long long*>(T + d.A * K);
+  HIP_TRY(hipMemcpyAsync(shift, r->score_shift.data(), (size_t)K * 4, hipMemcpyHostToDevice, idx->stream));
+  // From here on the runtime may be reading the caller's weights: nothing returns before the stream has been waited for.
+  uint64_t max_abs = 0;
+  const int enq = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(dw, q.weights, (size_t)b_weights, hipMemcpyHostToDevice, idx->stream));
+    HIP_TRY(hipMemsetAsync(T, 0, (size_t)b_totals + 8, idx->stream));
+    ScoreMatrixWeightArgs wa{};
+    wa.rows = (const VariantRow*)d.rows; wa.var_begin = d.var_begin; wa.q_nvar = d.q_nvar; wa.off = off; wa.Q = d.Q; wa.N = N;
+    wa.w = dw; wa.shift = shift; wa.K = K; wa.T = T;
+    wa.G = 1;
+    while (wa.G < 64 && wa.G < K) wa.G *= 2;
+    hipLaunchKernelGGL(k_score_matrix_weights, dim3((unsigned)std::min<uint64_t>((d.Q + 3) / 4, 8192)), dim3(256), 0, idx->stream, wa);
+    ScoreMatrixLimbArgs la{};
+    la.T = T; la.A = d.A; la.apad = apad; la.K = K; la.tiles = (uint32_t)tiles; la.panel = panel; la.meta = meta;
+    hipLaunchKernelGGL(k_score_matrix_limbs, dim3((unsigned)lrows, (unsigned)lcols), dim3(256), 0, idx->stream, la);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&max_abs, meta, 8, hipMemcpyDeviceToHost, idx->stream));
+    return VS_OK;
+  }();
+  const hipError_t waited = hipStreamSynchronize(idx->stream);   // (the weights have left the caller's memory as well, whatever failed above)
+  VS_TRY(enq);
+  HIP_TRY(waited);
+  if (max_abs > (uint64_t)kSmMaxTotal)
+    return fail(VS_ERR_UNSUPPORTED, "the weights of the reports of one table row add up to %llu in fixed point, more than 2^38 (more than 256 regions report the row): split the batch",
+                (unsigned long long)max_abs);
+  r->sm_limbs = sm_limbs_needed(max_abs);
+  // ---- the product ----
+  const uint32_t ts = r->sm_limbs == 4 ? kSmTilesPerWg : kSmTilesPerWg5;   // score tiles per workgroup
+  ScoreMatrixArgs a{};
+  a.cells = c.ld_matrix; a.panel = panel; a.A = d.A; a.apad = apad; a.pitch = (uint32_t)r->mx_pitch; a.n_cols = q.n_cols; a.K = K;
+  a.tiles = (uint32_t)tiles; a.tile_groups = (a.tiles + ts - 1) / ts; a.col_tiles = (q.n_cols + kGramTile - 1) / kGramTile;
+  a.sums = reinterpret_cast<unsigned long long*>(r->d_sums);
+  const uint64_t pairs = (uint64_t)a.tile_groups * a.col_tiles;
+  a.chunk = score_matrix_chunk_rows(idx, d.A, pairs);
+  const uint64_t blocks = (d.A + a.chunk - 1) / a.chunk * pairs, fblocks = (cells + 255) / 256;
+  if (blocks > 0x7FFFFFFFull || fblocks > 0x7FFFFFFFull)
+    return fail(VS_ERR_ARG, "batch too large for one launch (%llu row chunks x %llu tiles)", (unsigned long long)(blocks / pairs), (unsigned long long)pairs);
+  if (r->sm_limbs == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_score_matrix<4, kSmTilesPerWg>), dim3((unsigned)blocks), dim3(256), 0, idx->stream, a);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_score_matrix<5, kSmTilesPerWg5>), dim3((unsigned)blocks), dim3(256), 0, idx->stream, a);
+  hipLaunchKernelGGL(k_score_matrix_finish, dim3((unsigned)fblocks), dim3(256), 0, idx->stream, (const long long*)r->d_sums, cells, K, (const int32_t*)shift, r->d_score_out);
   HIP_TRY(hipGetLastError());
   return VS_OK;
 }
@@ -3643,6 +3768,10 @@ int vs_index_set_option(vs_index* idx, const char* key, int64_t value) {
   } else if (k == "gram_chunk") {
     if (value != 0 && (value < 64 || value > kGramChunkMax)) return fail(VS_ERR_ARG, "gram_chunk takes 0 (default: by the batch's shape) or 64..%u rows", kGramChunkMax);
     o.gram_chunk = (uint32_t)value;
+  } else if (k == "score_matrix_chunk") {
+    if (value != 0 && (value < 128 || value > kSmChunkMax || value % 128))
+      return fail(VS_ERR_ARG, "score_matrix_chunk takes 0 (default: by the batch's shape) or a multiple of 128 in 128..%u rows", kSmChunkMax);
+    o.score_matrix_chunk = (uint32_t)value;
   } else if (k == "ibs_chunk") {
     if (value != 0 && (value < 64 || value > kIbsChunkMax)) return fail(VS_ERR_ARG, "ibs_chunk takes 0 (default: by the batch's shape) or 64..%u rows", kIbsChunkMax);
     o.ibs_chunk = (uint32_t)value;
@@ -4004,6 +4133,57 @@ int vs_query_sample_scores(vs_index* idx, const vs_region* regions, uint64_t n, 
     r->h_cols = cols;
     r->n_scores = n_scores;
     r->score_names = names;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
+int vs_query_score_matrix(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, const float* weights, uint64_t n_weights,
+                          uint32_t n_scores, const char* const* score_names, vs_result** out) {
+  if (!idx || !out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
+  if (n == 0) return fail(VS_ERR_ARG, "a score-matrix batch needs at least one region");
+  if (n_scores == 0 || n_scores > VS_SCORE_MATRIX_MAX) return fail(VS_ERR_ARG, "%u scores (1 .. %u)", n_scores, VS_SCORE_MATRIX_MAX);
+  if (!weights && n_weights) return fail(VS_ERR_ARG, "null argument: a score-matrix batch takes a row of weights per reported row");
+  // the weights: finite, and f_k from the largest |w| of every column, before the device is asked
+  std::vector<int32_t> shift;
+  {
+    const size_t bad = am_shifts(weights, (size_t)n_weights, n_scores, shift);
+    if (bad != (size_t)n_weights * n_scores)
+      return fail(VS_ERR_ARG, "weight column %u holds a value that is not finite (row %llu)", (uint32_t)(bad % n_scores), (unsigned long long)(bad / n_scores));
+  }
+  std::vector<std::string> names;
+  if (score_names)
+    for (uint32_t k = 0; k < n_scores; ++k) {
+      if (!score_names[k]) return fail(VS_ERR_ARG, "null name of score %u", k);
+      names.emplace_back(score_names[k]);
+      if (names.back().find_first_of("\t\n") != std::string::npos) return fail(VS_ERR_ARG, "the name of score %u holds a tab or a newline", k);
+    }
+  if (n_ids == 0) return fail(VS_ERR_ARG, "an empty list of samples: scores of nobody");
+  const uint32_t ns = idx->g.num_samples;
+  if (!sample_ids && n_ids != (uint64_t)ns - 1)
+    return fail(VS_ERR_ARG, "without sample ids the scores are the whole cohort's: %llu ids announced, %u samples", (unsigned long long)n_ids, ns - 1);
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));   // (VS_ERR_UNKNOWN_SAMPLE: id 0 or an id beyond the cohort)
+  if (sample_ids && cols.size() != n_ids) {
+    std::vector<uint64_t> seen(mask.size(), 0);
+    for (uint64_t i = 0; i < n_ids; ++i) {
+      const uint32_t id = sample_ids[i];
+      if (seen[id >> 6] >> (id & 63) & 1) return fail(VS_ERR_ARG, "sample id %u is listed twice: a sample has one row of scores", id);
+      seen[id >> 6] |= 1ull << (id & 63);
+    }
+  }
+  if (n_weights >= kSmMaxReports)
+    return fail(VS_ERR_ARG, "%llu rows of weights: a score-matrix batch takes fewer than 2^26 reported rows (the 64-bit sums could overflow beyond): split the batch",
+                (unsigned long long)n_weights);
+  if (mask.size() * 8 > kMatrixMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", ns);
+  SharedReq req = column_request(ReqKind::ScoreMatrix, mask, rank, cols.size());
+  req.weights = weights; req.n_weights = n_weights; req.n_scores = n_scores;
+  return make_result(idx, kKindScoreMatrix, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    r->n_scores = n_scores;
+    r->score_names = names;
+    r->score_shift = shift;
     return run_column_batch(idx, regions, n, r, req);
   });
 }
@@ -4444,7 +4624,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
         for (uint64_t a = r->h_var_begin[q] * G, e = a + r->h_nvar[q] * G; a < e; ++a) nc += c[a].x;
       r->n_carriers_kept = nc;
     }
-    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindGram || r->kind == kKindIbs) {   // (LD, LD matrix, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
+    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
       VS_TRY(result_ready(r));
       uint64_t nc = 0;
       HIP_TRY(hipMemcpyAsync(&nc, r->d_cell_total, 8, hipMemcpyDeviceToHost, idx->stream));
@@ -4729,7 +4909,7 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
     if (len) *len = out.size();
     return VS_OK;
   }
-  if (r->kind == kKindScores) {   // the region's reported rows -- the rows the weights are keyed by, in report order
+  if (r->kind == kKindScores || r->kind == kKindScoreMatrix) {   // the region's reported rows -- the rows the weights are keyed by, in report order
     const VariantRow* rows;
     if (r->have_headers) rows = r->h_rows.data() + a0;
     else if (r->raw_rows) rows = r->raw_rows + a0;
@@ -4947,6 +5127,23 @@ int vs_result_get_sample_scores(vs_result* r, uint64_t* n_cols, uint32_t* n_scor
   if (n_scores) *n_scores = r->n_scores;
   if (col_ids) *col_ids = r->h_cols.data();
   if (shift) *shift = r->score_shift.data();
+  return VS_OK;
+}
+
+int vs_result_get_score_matrix(vs_result* r, uint64_t* n_cols, uint32_t* n_scores, const uint32_t** col_ids, const int32_t** shift, uint32_t* limbs,
+                               const int64_t** sums, const double** scores) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!sums && !scores) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindScoreMatrix) return fail(VS_ERR_ARG, "not a score-matrix result (vs_query_score_matrix)");
+  const size_t cells = r->h_cols.size() * r->n_scores;
+  VS_TRY(array_to_host(r, r->d_sums, cells * 16, &r->cells_pin, "score matrix"));
+  if (sums) *sums = (const int64_t*)r->cells_pin.p;
+  if (scores) *scores = (const double*)((const int64_t*)r->cells_pin.p + cells);
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_scores) *n_scores = r->n_scores;
+  if (col_ids) *col_ids = r->h_cols.data();
+  if (shift) *shift = r->score_shift.data();
+  if (limbs) *limbs = r->sm_limbs;
   return VS_OK;
 }
 
@@ -5172,6 +5369,15 @@ int vs_result_assoc_matrix_device(vs_result* r, uint64_t* n_rows, uint64_t* n_co
 
 int vs_result_sample_scores_device(vs_result* r, uint64_t* n_cols, uint32_t* n_scores, const void** dev_sums, const void** dev_scores) {
   VS_TRY(device_matrix_ready(r, dev_scores, kKindScores, "not a per-sample score result (vs_query_sample_scores)"));
+  *dev_scores = r->d_score_out;
+  if (dev_sums) *dev_sums = r->d_sums;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_scores) *n_scores = r->n_scores;
+  return VS_OK;
+}
+
+int vs_result_score_matrix_device(vs_result* r, uint64_t* n_cols, uint32_t* n_scores, const void** dev_sums, const void** dev_scores) {
+  VS_TRY(device_matrix_ready(r, dev_scores, kKindScoreMatrix, "not a score-matrix result (vs_query_score_matrix)"));
   *dev_scores = r->d_score_out;
   if (dev_sums) *dev_sums = r->d_sums;
   if (n_cols) *n_cols = r->h_cols.size();

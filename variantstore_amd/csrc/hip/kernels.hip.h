@@ -88,6 +88,12 @@
 //  k_ibs_n_used         int32 accumulators: the pairwise genotype-state counts D^T D cannot give; the rows the duplicate rule kept;
 //  k_ibs_finish         IBS0 / IBS2 and the KING-robust kinship from exact integers (vs_query_sample_ibs: no reference counterpart;
 //                       DESIGN 5j)
+// k_score_matrix        D^T W over the same dosages: samples x K weighted sums (K up to 65,536) over the rows a batch reports, the
+//  k_score_matrix_weights  wide form of k_sample_scores.  The report-keyed weights become per-row totals of fixed-point integers
+//  k_score_matrix_limbs    (64-bit atomics), the totals a panel of four or five int8 limbs; 128 columns x 16 or 32 scores x a chunk
+//  k_score_matrix_finish   of rows per workgroup, k_sample_gram's transposing stage, the limb sums combined in int64 and added to
+//                       the sums with 64-bit integer atomics: exact and order-free (vs_query_score_matrix: no reference counterpart;
+//                       DESIGN 5m)
 #pragma once
 #include "k_image.hip.h"
 #include "k_sites.hip.h"
@@ -112,3 +118,4 @@
 #include "k_gram.hip.h"
 #include "k_assoc_matrix.hip.h"
 #include "k_ibs.hip.h"
+#include "k_score_matrix.hip.h"
