@@ -554,6 +554,59 @@ int vs_result_get_ld_matrix(vs_result* r, uint64_t* n_regions, uint64_t* n_rows,
  * The engine has synchronised its stream when this returns: the caller needs no event. */
 int vs_result_ld_matrix_device(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const void** dev_counts,
                                const void** dev_block_begin, const void** dev_cells);
+/* LD pruning over regions: the forward greedy r2 pruning of every region on the device -- the step in front of a GRM, a PCA or a
+ * kinship table, which are meaningful on an LD-pruned variant set only (no reference counterpart).  The table T, its A rows,
+ * row_begin / row_count, the column set S with n columns and the count records are those of vs_query_ld_band over the same regions
+ * and ids.
+ * For a table row i: ac_i = alt_alleles, Sx = ac_i, Sxx = ac_i + 2 hom_alt_i, v_i = n Sxx - Sx^2 in int64.  For a pair of rows: Sxy
+ * the exact dosage dot product, cov = n Sxy - Sx Sy.
+ * Threshold: an integer T in 0 .. 2^20 (threshold_q20); the r2 bound is T / 2^20.
+ * Hit: the pair is a hit exactly when v_i > 0, v_j > 0 and cov^2 2^20 > T v_i v_j.  The comparison is evaluated in unsigned 128-bit
+ * integers; no floating-point value takes part.  With n < 2^21 both sides stay below 2^108; a column set of 2^21 or more is refused
+ * with VS_ERR_UNSUPPORTED.  T = 2^20 can never hit.
+ * Eligible: a row is eligible when the duplicate rule did not drop it, v_i > 0 and min_ac <= ac_i <= max_ac (0 and UINT32_MAX admit
+ * every row, as for vs_query_sample_burden).
+ * Greedy: for region q, walk its table rows i = row_begin[q] .. row_begin[q] + row_count[q] - 1 in ascending order.  Row i is kept
+ * when it is eligible and no already kept row j of the same walk satisfies all of 1 <= i - j <= window, max_bp == 0 or
+ * |pos_i - pos_j| <= max_bp, and hit(j, i).  A pruned or ineligible row blocks nothing: the forward greedy with a sliding window of
+ * SNPRelate's LD pruning, "the later row loses".  (MAF-priority removal and p-value clumping are other procedures.)
+ * Regions are independent: each walk starts with an empty kept set at its own first row; overlapping or identical regions each get
+ * their own verdicts over the shared rows, as vs_query_ld_matrix gives each region its own block.
+ * Result: keep_begin[n + 1] (uint64), the exclusive scan of row_count; state[keep_begin[q] + a] (uint8), the verdict for table row
+ * row_begin[q] + a: VS_PRUNE_PRUNED, VS_PRUNE_KEPT, VS_PRUNE_INELIGIBLE or VS_PRUNE_DROPPED; n_kept[q] (uint64) per region; the count
+ * record of every table row over S, the column ids, and window, max_bp, T, min_ac, max_ac.  Every byte of `state` is stored exactly
+ * once by a kernel.
+ * Checked on the host, in this order, before the handle's device is asked for (a handle opened without a device reports them first
+ * and VS_ERR_NO_DEVICE otherwise): n == 0, sample_ids == NULL with n_ids != 0, non-NULL sample_ids with n_ids == 0 -> VS_ERR_ARG;
+ * window == 0 or window > 256 -> VS_ERR_ARG ("window" in the message); threshold_q20 > 2^20 -> VS_ERR_ARG ("threshold" in the
+ * message); min_ac > max_ac -> VS_ERR_ARG; id 0 or id >= num_samples -> VS_ERR_UNKNOWN_SAMPLE.
+ * The verdicts are formed from a temporary genotype matrix and temporary hit masks (ceil(window / 32) words of 4 bytes per table
+ * row), which leave the result as an LD batch's matrix does; the matrix, the masks, `state` and the per-region arrays together may
+ * not exceed option "matrix_max_mib" MiB (default 32 GiB): beyond it the call is refused with VS_ERR_ARG before anything is
+ * allocated for them; the message names rows, columns, window and bytes.  The size of `state` is known on the device only: the
+ * call may wait once for a small scan over the per-region row counts, in front of the kernels vs_result_fill_ms times (the counts,
+ * the temporary matrix, the mask kernel and the walk).  The batch is never speculative and leaves the handle's type-6 state as it
+ * was.  vs_result_get_raw / vs_result_get_view with with_carriers = 0, vs_result_layout, vs_result_totals (n_carriers = the nonzero
+ * cells of the matrix) and vs_result_fill_ms work as for an LD result; vs_result_format_region gives "Pos\tRef\tAlt\tAC\tState\n",
+ * then one line per reported, non-dropped row of the region, State one of keep, pruned, skip.  What an LD result refuses this
+ * result refuses with the same codes; the other results' getters refuse it with VS_ERR_ARG. */
+#define VS_PRUNE_PRUNED 0u
+#define VS_PRUNE_KEPT 1u
+#define VS_PRUNE_INELIGIBLE 2u
+#define VS_PRUNE_DROPPED 3u
+#define VS_PRUNE_THRESHOLD_ONE (1u << 20)
+int vs_query_ld_prune(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t window,
+                      uint32_t max_bp, uint32_t threshold_q20, uint32_t min_ac, uint32_t max_ac, vs_result** out);
+/* The verdicts of a pruning result copied into page-locked memory owned by the result: state[keep_begin[q] + a], keep_begin[n_regions
+ * + 1], n_kept[n_regions], counts[i] the count record of table row i over S, col_ids[c] the sample id of column c, and params[5] =
+ * {window, max_bp, threshold_q20, min_ac, max_ac}.  Every out-pointer but `state` may be NULL.  VS_ERR_ARG on any other result. */
+int vs_result_get_ld_prune(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint32_t* params, const uint32_t** col_ids,
+                           const vs_allele_counts** counts, const uint64_t** keep_begin, const uint64_t** n_kept, const uint8_t** state);
+/* State (keep_begin[n_regions] bytes), keep_begin (n_regions + 1 uint64), n_kept (n_regions uint64) and counts (n_rows records of 16
+ * bytes) as they lie in HBM, valid until vs_result_free.  The engine has synchronised its stream when this returns: the caller
+ * needs no event. */
+int vs_result_ld_prune_device(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, const void** dev_counts,
+                              const void** dev_keep_begin, const void** dev_n_kept, const void** dev_state);
 /* Sample Gram matrix / GRM over regions: D^T D, the samples x samples product of the dosages -- what a GRM, kinship, IBS-type sharing
  * and the PCA of a cohort start from, and the one product of the dosage matrix the other column queries leave out (D Y:
  * vs_query_assoc_scan, D^T W: vs_query_sample_scores, the band of D D^T: vs_query_ld_band; no reference counterpart).  T, its rows, S

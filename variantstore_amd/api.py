@@ -72,6 +72,18 @@ def quantise_traits(y):
     return q, shift
 
 
+PRUNE_THRESHOLD_ONE = 1 << 20   # VS_PRUNE_THRESHOLD_ONE: the integer threshold of r2 = 1
+
+
+def quantise_r2(r2):
+    """The integer threshold T of an r2 bound for VariantStore.ld_prune: floor(r2 * 2**20 + 0.5), 0 .. 2**20.  The pruning decides
+    r2 > T / 2**20 in exact integers.  ValueError outside [0, 1]."""
+    r2 = float(r2)
+    if not 0.0 <= r2 <= 1.0:   # (a NaN fails both comparisons)
+        raise ValueError(f"r2 {r2!r}: a bound between 0 and 1")
+    return int(math.floor(r2 * PRUNE_THRESHOLD_ONE + 0.5))
+
+
 def _regions_array(regions):
     if isinstance(regions, DeviceArray):
         return regions, C.cast(C.c_void_p(regions.ptr), C.POINTER(Region)), regions.n
@@ -570,6 +582,58 @@ class QueryResult:
         return (int(pb.value or 0), int(pc.value or 0), int(a.value), int(c.value), int(w.value),
                 "r2" if st.value == self.LD_STATS["r2"] else "dot")
 
+    PRUNE_STATES = {"pruned": 0, "kept": 1, "ineligible": 2, "dropped": 3}   # VS_PRUNE_*
+
+    def ld_prune(self):
+        """A pruning result (VariantStore.ld_prune) as numpy arrays: `state` (uint8, a verdict per reported row: PRUNE_STATES),
+        `keep_begin` (uint64[Q + 1], the exclusive scan of row_count: region q's verdicts are state[keep_begin[q] :
+        keep_begin[q + 1]], for the table rows row_begin[q] .. + row_count[q]), `n_kept` (uint64[Q]), `threshold` (the exact
+        T / 2**20 the walk used), `threshold_q20` (T), `window`, `max_bp`, `min_ac`, `max_ac`, `counts` (structured as for
+        allele_counts: the count record of every table row over the query's samples), `columns` (uint32[C], the sample ids), the
+        table's `rows` and per region `row_begin` and `row_count`.  Copies, valid after the result is closed."""
+        nq, a, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        params = (C.c_uint32 * 5)()
+        cols = C.POINTER(C.c_uint32)()
+        cnt = C.POINTER(_lib.AlleleCounts)()
+        kb, nk = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        p = C.POINTER(C.c_uint8)()
+        _check(self._lib.vs_result_get_ld_prune(self._h, C.byref(nq), C.byref(a), C.byref(c), params, C.byref(cols), C.byref(cnt),
+                                                C.byref(kb), C.byref(nk), C.byref(p)), "vs_result_get_ld_prune")
+        q, na, nc = int(nq.value), int(a.value), int(c.value)
+        keep_begin = np.ctypeslib.as_array(kb, shape=(q + 1,)).copy()
+        n_kept = np.ctypeslib.as_array(nk, shape=(q,)).copy() if q else np.zeros(0, np.uint64)
+        total = int(keep_begin[q])
+        state = np.ctypeslib.as_array(p, shape=(total,)).copy() if total else np.zeros(0, np.uint8)
+        counts = (np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint8)), shape=(na * 16,)).view(self.COUNT_DTYPE).copy() if na
+                  else np.zeros(0, self.COUNT_DTYPE))
+        raw = self.raw(with_carriers=False)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "columns": np.ctypeslib.as_array(cols, shape=(nc,)).copy(), "counts": counts, "state": state, "keep_begin": keep_begin,
+                "n_kept": n_kept, "threshold": int(params[2]) / PRUNE_THRESHOLD_ONE, "threshold_q20": int(params[2]),
+                "window": int(params[0]), "max_bp": int(params[1]), "min_ac": int(params[3]), "max_ac": int(params[4])}
+
+    def ld_prune_device(self):
+        """(state address, keep_begin address, n_kept address, counts address, n_regions, n_rows, n_cols) of a pruning result as it
+        lies in this GPU's memory: keep_begin[n_regions] verdict bytes, n_regions + 1 and n_regions uint64 words and n_rows count
+        records of four uint32, complete when this returns and valid until the result is closed."""
+        nq, a, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        pc, pb, pn, ps = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_ld_prune_device(self._h, C.byref(nq), C.byref(a), C.byref(c), C.byref(pc), C.byref(pb), C.byref(pn),
+                                                   C.byref(ps)), "vs_result_ld_prune_device")
+        return (int(ps.value or 0), int(pb.value or 0), int(pn.value or 0), int(pc.value or 0), int(nq.value), int(a.value),
+                int(c.value))
+
+    def region_kept(self, q):
+        """The rows region q of a pruning result keeps: a list of (pos, ref, alt), in the table's order."""
+        out = []
+        for line in self.region_text(q).split("\n")[1:]:
+            if not line:
+                continue
+            pos, ref, alt, _ac, state = line.split("\t")
+            if state == "keep":
+                out.append((int(pos), ref, alt))
+        return out
+
     def region_ld(self, q):
         """The pairs region q of an LD result reports: a list of dicts with `a` and `b` (each (pos, ref, alt)) and `value` (int under
         "dot", float under "r2") for every pair of the region's reported rows at most the window apart in the table."""
@@ -1053,6 +1117,25 @@ class VariantStore:
             window = 0
         _check(self._lib.vs_query_ld_band(self._h, ptr, n, ids_ptr, n_ids, window, int(stat) & 0xFFFFFFFF, C.byref(h)),
                "vs_query_ld_band")
+        return QueryResult(self, h)
+
+    def ld_prune(self, regions, samples=None, window=64, r2=0.2, max_bp=0, min_ac=0, max_ac=None) -> QueryResult:
+        """LD pruning over regions (vs_query_ld_prune): for every region the forward greedy pruning of its table rows, in table
+        order -- a row is kept when it is polymorphic over `samples` (names or ids, taken as a set; None: the whole cohort), its
+        alternate-allele count lies in [min_ac, max_ac] (max_ac None: no upper limit), and no kept row among the `window`
+        (1 .. 256) rows before it (at most `max_bp` positions away; 0: no limit) has a squared dosage correlation with it above
+        `r2`.  `r2` is quantised to T = quantise_r2(r2) and r2 > T / 2**20 is decided in exact integers: the verdicts do not
+        depend on rounding.  Regions are independent.  `regions` as for allele_counts.  Read the result with
+        QueryResult.ld_prune / ld_prune_device / region_kept / region_text."""
+        threshold = quantise_r2(r2)
+        arr, ptr, n = _regions_array(regions)
+        h = C.c_void_p()
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        window = int(window)
+        if not 0 <= window <= 0xFFFFFFFF:   # (ctypes would wrap it: 0 is refused by the C ABI like any window outside 1 .. 256)
+            window = 0
+        _check(self._lib.vs_query_ld_prune(self._h, ptr, n, ids_ptr, n_ids, window, int(max_bp) & 0xFFFFFFFF, threshold, int(min_ac),
+                                           0xFFFFFFFF if max_ac is None else int(max_ac), C.byref(h)), "vs_query_ld_prune")
         return QueryResult(self, h)
 
     def ld_matrix(self, regions, samples=None, stat="r2") -> QueryResult:

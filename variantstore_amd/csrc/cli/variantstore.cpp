@@ -117,6 +117,7 @@ struct Args {
   uint32_t min_ac = 0, max_ac = UINT32_MAX;   // `burden`: the alternate-allele-count window of the rows that count
   uint32_t ld_window = 64;   // `ld`: every row against the next ld_window rows; --dot: dot products instead of r^2
   bool ld_dot = false;
+  uint32_t prune_max_bp = 0, prune_threshold = 209715;   // `prune`: --bp, and --r2 as floor(r2 * 2^20 + 0.5) (0.2 by default)
   bool gram_grm = false;      // `gram`: the GRM (float64) instead of the dosage products (int64)
   bool ibs_king = false;      // `ibs`: the kinship column beside the counts; --min-kinship X: only pairs with kinship >= X (implies --king)
   bool ibs_have_min = false;
@@ -1195,7 +1196,21 @@ int ldmatrix_usage() {
   return EXIT_FAILURE;
 }
 
-int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false, bool ldmatrix = false) {
+// `variantstore prune`: greedy LD pruning of every region (vs_query_ld_prune) over the same samples.  Output as `counts`:
+// "#region <i> <x>:<y>", then the region's text ("Pos Ref Alt AC State", a line per reported row: keep, pruned or skip).
+int prune_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore prune -p <output-prefix> -r <region> [-S <sample-name-file>] [-w <window>] [--r2 <bound>] [--bp <n>]\n"
+               "                           [--min-ac <n>] [--max-ac <n>] [-o <outfile>] [--device <n>]\n\n"
+               "        For every region the forward greedy LD pruning of its variants (as query type 6 reports them), in order: a\n"
+               "        variant is kept unless a kept variant among the <window> rows before it (1 .. 256, 64 by default; at most --bp\n"
+               "        positions away) has a squared dosage correlation with it above --r2 (0 .. 1, 0.2 by default), over the whole\n"
+               "        cohort or the samples named in the file.  Variants that are monomorphic there or whose alternate-allele\n"
+               "        count lies outside [--min-ac, --max-ac] are skipped.\n";
+  return EXIT_FAILURE;
+}
+
+int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false, bool ldmatrix = false, bool prune = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
   if (rc != VS_OK) die(rc, "load");
@@ -1220,12 +1235,13 @@ int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool
   std::vector<vs_region> batch;
   for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
   vs_result* res = nullptr;
-  if (ldmatrix) rc = vs_query_ld_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_dot ? VS_LD_DOT : VS_LD_R2, &res);
+  if (prune) rc = vs_query_ld_prune(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_window, a.prune_max_bp, a.prune_threshold, a.min_ac, a.max_ac, &res);
+  else if (ldmatrix) rc = vs_query_ld_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_dot ? VS_LD_DOT : VS_LD_R2, &res);
   else if (ld) rc = vs_query_ld_band(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_window, a.ld_dot ? VS_LD_DOT : VS_LD_R2, &res);
   else if (genotypes) rc = vs_query_genotype_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
   else if (burden) rc = vs_query_sample_burden(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.min_ac, a.max_ac, &res);
   else rc = vs_query_allele_counts(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
-  if (rc != VS_OK) die(rc, ldmatrix ? "ldmatrix" : ld ? "ld" : genotypes ? "genotypes" : burden ? "burden" : "counts");
+  if (rc != VS_OK) die(rc, prune ? "prune" : ldmatrix ? "ldmatrix" : ld ? "ld" : genotypes ? "genotypes" : burden ? "burden" : "counts");
   std::ofstream file;
   if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
   std::ostream& out = a.outfile.empty() ? std::cout : file;
@@ -1283,12 +1299,20 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "prune" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
-      else if (a.cmd == "burden" && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
-      else if (a.cmd == "burden" && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
-      else if (a.cmd == "ld" && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if ((a.cmd == "burden" || a.cmd == "prune") && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if ((a.cmd == "burden" || a.cmd == "prune") && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if ((a.cmd == "ld" || a.cmd == "prune") && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if ((a.cmd == "ld" || a.cmd == "ldmatrix") && f == "--dot") a.ld_dot = true;
+      else if (a.cmd == "prune" && f == "--bp") a.prune_max_bp = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if (a.cmd == "prune" && f == "--r2") {
+        const std::string v = need(i);
+        char* end = nullptr;
+        const double r2 = strtod(v.c_str(), &end);
+        if (v.empty() || *end != '\0' || !(r2 >= 0.0 && r2 <= 1.0)) { std::cerr << "--r2 takes a bound between 0 and 1, not '" << v << "'\n"; return prune_usage(); }
+        a.prune_threshold = (uint32_t)std::floor(r2 * 1048576.0 + 0.5);
+      }
       else if (a.cmd == "gram" && f == "--grm") a.gram_grm = true;
       else if (a.cmd == "ibs" && f == "--king") a.ibs_king = true;
       else if (a.cmd == "ibs" && f == "--min-kinship") {
@@ -1340,6 +1364,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "genotypes") {
     if (a.prefix.empty() || a.region.empty()) return genotypes_usage();
     return counts_main(a, /*burden=*/false, /*genotypes=*/true);
+  }
+  if (a.cmd == "prune") {
+    if (a.prefix.empty() || a.region.empty()) return prune_usage();
+    return counts_main(a, /*burden=*/false, /*genotypes=*/false, /*ld=*/false, /*ldmatrix=*/false, /*prune=*/true);
   }
   if (a.cmd == "ldmatrix") {
     if (a.prefix.empty() || a.region.empty()) return ldmatrix_usage();

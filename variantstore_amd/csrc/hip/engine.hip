@@ -248,7 +248,7 @@ struct vs_result {
                  // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts; kKindAssoc: association scan;
                  // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM; kKindIbs: pairwise IBS counts / KING kinship;
                  // kKindLdMatrix: the full LD block of every region; kKindAssocMatrix: trait-matrix association scan;
-                 // kKindScoreMatrix: score matrix
+                 // kKindScoreMatrix: score matrix; kKindPrune: LD pruning verdicts
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -306,6 +306,15 @@ struct vs_result {
   uint64_t* d_ldm_meta = nullptr;
   uint64_t ldm_cells = 0, ldm_wgs = 0;
   std::vector<uint64_t> h_block_begin;
+  // pruning results (vs_query_ld_prune): a verdict byte per reported row in HBM (d_state, prune_states of them), one buffer of 8-byte
+  // words beside it -- keep_begin [Q + 1], n_kept [Q + 1, the last unused], the scan's summary (two words), the nonzero cells of the
+  // (temporary) genotype matrix (d_cell_total, two words) --, counts and column ids as for an LD result, ld_window and the other
+  // parameters of the walk; the state's page-locked host copy is cells_pin, the per-region words' host copy h_prune_meta
+  uint8_t* d_state = nullptr;
+  uint64_t* d_prune_meta = nullptr;
+  uint64_t prune_states = 0;
+  uint32_t prune_max_bp = 0, prune_T = 0, prune_min_ac = 0, prune_max_ac = UINT32_MAX;
+  std::vector<uint64_t> h_prune_meta;
   // Gram results (vs_query_sample_gram): one buffer of 8-byte words in HBM -- gram [n x n] int64, col_weighted [n] int64, C, H, the
   // nonzero cells of the (temporary) genotype matrix (d_cell_total, two words), then from gram_grm_off on grm [n x n] float64 under
   // VS_GRAM_GRM -- copied to cells_pin in one piece; the count record of every table row in d_counts / counts_pin, the column ids h_cols
@@ -341,8 +350,9 @@ constexpr int kKindIbs = 16;     // ... of an IBS result: the rows of type 6, sa
 constexpr int kKindLdMatrix = 17;   // ... of an LD-matrix result: the rows of type 6, a square block of pair statistics per region instead of carrier lists
 constexpr int kKindAssocMatrix = 18;   // ... of a trait-matrix association result: the rows of type 6, a score per row and trait (up to VS_TRAIT_MATRIX_MAX traits) instead of carrier lists
 constexpr int kKindScoreMatrix = 19;   // ... of a score-matrix result: the rows of type 6, a columns x scores matrix of weighted dosage sums (up to VS_SCORE_MATRIX_MAX scores) instead of carrier lists
+constexpr int kKindPrune = 20;   // ... of a pruning result: the rows of type 6, a verdict byte per reported row instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
+  return r->kind == kKindPrune || r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
          r->kind == kKindScores;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
@@ -363,6 +373,8 @@ static int refuse_no_lists(const vs_result* r, const char* what) {
     return fail(VS_ERR_UNSUPPORTED, "%s: an IBS result holds samples x samples matrices of genotype-state counts, no carrier lists (vs_result_get_sample_ibs)", what);
   if (r->kind == kKindLdMatrix)
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD-matrix result holds a square block of pair statistics per region, no carrier lists (vs_result_get_ld_matrix)", what);
+  if (r->kind == kKindPrune)
+    return fail(VS_ERR_UNSUPPORTED, "%s: a pruning result holds a verdict per reported row, no carrier lists (vs_result_get_ld_prune)", what);
   if (r->kind == kKindLd)
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD result holds a rows x window band of pair statistics, no carrier lists (vs_result_get_ld_band)", what);
   if (r->kind == kKindMatrix)
@@ -1228,7 +1240,8 @@ static int capture_totals(vs_result* r) {
 // the device once the batch has passed the size limit: assoc_matrix_upload); the traits and the statistic.
 // ScoreMatrix: mask, rank and n_cols as for the matrix; `weights` (host memory), n_weights and n_scores as for Scores; `sm_shift`: f_k
 // per weight column, formed on the host.
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix };
+// Prune: as LD (ld_window) with the walk's parameters: prune_max_bp, prune_T (0 .. 2^20), prune_min_ac, prune_max_ac.
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix, Prune };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1236,6 +1249,7 @@ struct SharedReq {
   const uint32_t* rank = nullptr;
   uint32_t n_cols = 0, min_ac = 0, max_ac = UINT32_MAX;
   uint32_t ld_window = 0, ld_stat = 0, gram_stat = 0, ibs_stat = 0;
+  uint32_t prune_max_bp = 0, prune_T = 0, prune_min_ac = 0, prune_max_ac = UINT32_MAX;
   const uint64_t* pheno = nullptr;
   size_t pheno_words = 0;
   uint32_t n_traits = 0, assoc_stat = 0;
@@ -1616,6 +1630,9 @@ static int launch_ibs(vs_index* idx, vs_result* r, const uint8_t* cells, uint64_
 //                      Ibs: the same two, then k_ibs_n_used, k_sample_ibs and k_ibs_finish (launch_ibs) |
 //                      LdMatrix: in front of them k_ld_block_scan over the per-region row counts and one host wait for its totals
 //                      (ld_matrix_tables: the size limit, the temporary matrix, the cells); behind them k_ld_block (launch_ld_block)
+//                      Prune: in front of them k_prune_scan over the per-region row counts and one host wait for its total
+//                      (prune_tables: the size limit, the temporary matrix and masks, the state); behind them k_prune_hits and
+//                      k_prune_greedy (launch_prune)
 //   shared_finish      enqueued: the completion event | synchronous: k_post_done, a word in mapped host memory, the host spins on it
 // A column request is never speculative, has no arena, and leaves the handle's type-6 state (size hints, sort hint) as it found
 // it: count batches interleaved with type-6 batches change none of theirs.
@@ -1657,10 +1674,11 @@ struct SharedCtx {
   bool async_fill = false, fused = false, lean = false;
   uint32_t* u_site = nullptr;   // shared_rows: the site of every shared row (a column request: of every row)
   uint8_t* ld_matrix = nullptr; // shared_tables: the temporary genotype matrix of an LD batch (ld_tmp); an LD-matrix batch: ld_matrix_tables
+  uint32_t* prune_hits = nullptr;   // prune_tables: a pruning batch's hit masks (ld_tmp)
   uint64_t* am_dev = nullptr;   // shared_tables: a trait-matrix batch's Sy, vy, shifts and limb panel on the device (ld_tmp)
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix || q.kind == ReqKind::Prune) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -1935,6 +1953,24 @@ static int assoc_matrix_fits(SharedCtx& c) {
               (unsigned long long)r->d.A, c.req.n_cols, c.req.n_traits, (unsigned long long)(r->d.A * row_bytes + panel_bytes), (unsigned long long)(r->d.A * r->mx_pitch),
               (unsigned long long)(r->d.A * 8 * K), (unsigned long long)(r->d.A * 16), (unsigned long long)panel_bytes, (unsigned long long)(cap >> 20));
 }
+// A pruning batch: the temporary matrix, the hit masks, the state bytes and the per-region words together, under the same limit.
+// `states`: the number of verdicts, 0 while the scan has not given it (shared_tables: what is known by then already decides most
+// refusals, before anything is allocated).
+static int prune_fits(SharedCtx& c, uint64_t states) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  r->mx_pitch = ((uint64_t)c.req.n_cols + 15) & ~15ull;
+  const uint64_t mask_row = 4ull * ((c.req.ld_window + 31) / 32), row_bytes = r->mx_pitch + mask_row;
+  const uint64_t region_bytes = 8 * (2 * (r->d.Q + 1) + 4);   // (Q < 2^32)
+  if (region_bytes <= cap && states <= cap - region_bytes && r->d.A <= (cap - region_bytes - states) / row_bytes) return VS_OK;
+  (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+  (void)hipStreamSynchronize(idx->stream);
+  return fail(VS_ERR_ARG, "an LD pruning of %llu regions over %llu rows x %u columns with window %u takes %llu bytes (%llu of the genotype matrix it is formed from, "
+              "%llu of the hit masks, %llu of the verdicts, %llu of the per-region arrays), more than the limit of %llu MiB (option matrix_max_mib): split the batch",
+              (unsigned long long)r->d.Q, (unsigned long long)r->d.A, c.req.n_cols, c.req.ld_window, (unsigned long long)(r->d.A * row_bytes + states + region_bytes),
+              (unsigned long long)(r->d.A * r->mx_pitch), (unsigned long long)(r->d.A * mask_row), (unsigned long long)states, (unsigned long long)region_bytes,
+              (unsigned long long)(cap >> 20));
+}
 // Reads the totals (*pt) or the speculation.  Leaves U / n_slow / n_runs, the result's sizes and bookkeeping, a speculative batch
 // registered with its slot, what the request's kind allocates, and the form of the rows and the expansion (n_fill .. lean).
 static int shared_tables(SharedCtx& c) {
@@ -2052,6 +2088,15 @@ static int shared_tables(SharedCtx& c) {
       r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_ldm_meta + 2 * (d.Q + 1) + 4);
       r->ld_stat = q.ld_stat;
       break;
+    case ReqKind::Prune:   // (the temporary matrix, the masks and the state wait for the number of verdicts: prune_tables, behind the permutation)
+      VS_TRY(prune_fits(c, 0));
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      VS_TRY(ralloc(r, 2 * (size_t)(d.Q + 1) + 4, &r->d_prune_meta));
+      r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_prune_meta + 2 * (d.Q + 1) + 2);
+      r->ld_window = q.ld_window;
+      r->prune_max_bp = q.prune_max_bp; r->prune_T = q.prune_T; r->prune_min_ac = q.prune_min_ac; r->prune_max_ac = q.prune_max_ac;
+      break;
   }
   c.async_fill = c.allow_async && idx->opts.async_fill && c.n_fill > 0;
   c.fused = idx->opts.fill_fused && c.lists && !c.resident && !c.async_fill;
@@ -2166,11 +2211,14 @@ static int ld_matrix_tables(SharedCtx& c);
 static int assoc_matrix_upload(SharedCtx& c);
 static int launch_assoc_matrix(SharedCtx& c);
 static int launch_ld_block(vs_index* idx, vs_result* r, const uint8_t* cells, const SharedReq& lq);
+static int prune_tables(SharedCtx& c);
+static int launch_prune(SharedCtx& c);
 static int shared_columns(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
   if (!c.behind_perm && !r->d.A) return VS_OK;
   if (c.req.kind == ReqKind::LdMatrix) VS_TRY(ld_matrix_tables(c));   // (its one host wait in front of the pair of events: they time kernels only)
   if (c.req.kind == ReqKind::AssocMatrix) VS_TRY(assoc_matrix_upload(c));   // (in front of the pair of events as well)
+  if (c.req.kind == ReqKind::Prune) VS_TRY(prune_tables(c));   // (its one host wait in front of the pair of events as well)
   VS_TRY(result_events(r));
   HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
   if (c.req.kind == ReqKind::Groups) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, r->d_counts);
@@ -2187,6 +2235,9 @@ static int shared_columns(SharedCtx& c) {
   } else if (c.req.kind == ReqKind::LdMatrix) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_ld_block(idx, r, c.ld_matrix, c.req));
+  } else if (c.req.kind == ReqKind::Prune) {
+    VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+    VS_TRY(launch_prune(c));
   } else if (c.req.kind == ReqKind::AssocMatrix) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_assoc_matrix(c));
@@ -2451,6 +2502,65 @@ static int launch_ld_block(vs_index* idx, vs_result* r, const uint8_t* cells, co
   a.counts = r->d_counts; a.out = r->d_ldm;
   if (lq.ld_stat == VS_LD_R2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_block<true>), dim3((unsigned)r->ldm_wgs), dim3(256), 0, idx->stream, a);
   else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_block<false>), dim3((unsigned)r->ldm_wgs), dim3(256), 0, idx->stream, a);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+
+// A pruning batch behind the permutation (the per-region arrays are in the caller's order): keep_begin from the per-region row counts
+// by one small scan; the number of verdicts comes back in ONE host wait (the batch is never speculative).  The temporary matrix,
+// the masks, the state and the per-region words together are held against option matrix_max_mib here, before the first three are
+// allocated.
+static int prune_tables(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  uint64_t* meta = r->d_prune_meta;
+  hipLaunchKernelGGL(k_prune_scan, dim3(1), dim3(kPruneScanThreads), 0, idx->stream, (const uint64_t*)d.q_nvar, d.Q, meta, meta + 2 * (d.Q + 1));
+  HIP_TRY(hipGetLastError());
+  uint64_t sum[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(sum, meta + 2 * (d.Q + 1), sizeof sum, hipMemcpyDeviceToHost, idx->stream));
+  HIP_TRY(hipStreamSynchronize(idx->stream));
+  VS_TRY(prune_fits(c, sum[0]));
+  r->prune_states = sum[0];
+  const uint32_t words = (c.req.ld_window + 31) / 32;
+  VS_TRY(dev_alloc(idx, (size_t)(d.A * r->mx_pitch), (void**)&c.ld_matrix, &c.ld_tmp.bufs));
+  VS_TRY(dev_alloc(idx, (size_t)(d.A * words) * 4, (void**)&c.prune_hits, &c.ld_tmp.bufs));
+  VS_TRY(ralloc(r, (size_t)sum[0], &r->d_state));
+  return VS_OK;
+}
+
+// The verdicts of a pruning batch from its temporary genotype matrix and the table's counts: k_prune_hits over blocks of kLdRows
+// table rows, as the band kernel, then k_prune_greedy, one wave per region, all regions in one launch.
+template <int MAXT>
+static int launch_prune_hits(vs_index* idx, const PruneHitArgs& p, unsigned blocks, size_t lds) {
+  if (lds > (48 << 10)) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_prune_hits<MAXT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_prune_hits<MAXT>), dim3(blocks), dim3(256), lds, idx->stream, p);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+static int launch_prune(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  const SharedReq& q = c.req;
+  const uint32_t words = (q.ld_window + 31) / 32;
+  if (d.A) {
+    PruneHitArgs p{};
+    p.ld.cells = c.ld_matrix; p.ld.A = d.A; p.ld.pitch = (uint32_t)r->mx_pitch; p.ld.n_cols = q.n_cols;
+    p.ld.window = q.ld_window; p.ld.n_tiles = (q.ld_window + 15) / 16 + 1;
+    p.ld.counts = r->d_counts; p.ld.band = nullptr;
+    p.rows = (const VariantRow*)d.rows; p.hits = c.prune_hits; p.words = words; p.max_bp = q.prune_max_bp; p.threshold = q.prune_T;
+    const uint64_t blocks = (d.A + kLdRows - 1) / kLdRows;
+    if (blocks > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu row blocks)", (unsigned long long)blocks);
+    const size_t lds = (size_t)(kLdRows + 16 * (p.ld.n_tiles - 1)) * kLdStride;
+    if (p.ld.n_tiles <= kLdSmallTiles) VS_TRY(launch_prune_hits<(int)kLdSmallTiles>(idx, p, (unsigned)blocks, lds));
+    else VS_TRY(launch_prune_hits<(int)kLdMaxTiles>(idx, p, (unsigned)blocks, lds));
+  }
+  PruneGreedyArgs g{};
+  g.Q = d.Q; g.row_begin = (const uint64_t*)d.var_begin; g.row_count = (const uint64_t*)d.q_nvar;
+  g.keep_begin = r->d_prune_meta; g.rows = (const VariantRow*)d.rows; g.counts = r->d_counts; g.hits = c.prune_hits;
+  g.words = words; g.n_cols = q.n_cols; g.min_ac = q.prune_min_ac; g.max_ac = q.prune_max_ac;
+  g.state = r->d_state; g.n_kept = r->d_prune_meta + (d.Q + 1);
+  if (d.Q > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu regions)", (unsigned long long)d.Q);
+  hipLaunchKernelGGL(k_prune_greedy, dim3((unsigned)d.Q), dim3(64), 0, idx->stream, g);
   HIP_TRY(hipGetLastError());
   return VS_OK;
 }
@@ -4257,6 +4367,29 @@ int vs_query_ld_matrix(vs_index* idx, const vs_region* regions, uint64_t n, cons
   });
 }
 
+int vs_query_ld_prune(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t window, uint32_t max_bp,
+                      uint32_t threshold_q20, uint32_t min_ac, uint32_t max_ac, vs_result** out) {
+  VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "an LD-pruning"));
+  if (window == 0 || window > kLdMaxWindow) return fail(VS_ERR_ARG, "an LD-pruning window of %u rows (1 .. %u)", window, kLdMaxWindow);
+  if (threshold_q20 > kPruneThresholdOne)
+    return fail(VS_ERR_ARG, "an LD-pruning threshold of %u / 2^20 (0 .. %u: r2 between 0 and 1)", threshold_q20, kPruneThresholdOne);
+  if (min_ac > max_ac) return fail(VS_ERR_ARG, "an empty allele-count window [%u, %u]", min_ac, max_ac);
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));
+  if (cols.size() >= (1ull << 21))
+    return fail(VS_ERR_UNSUPPORTED, "an LD pruning over %llu columns: the exact comparison takes fewer than 2^21", (unsigned long long)cols.size());
+  if (mask.size() * 8 > kMatrixMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", idx->g.num_samples);
+  SharedReq req = column_request(ReqKind::Prune, mask, rank, cols.size());
+  req.ld_window = window;
+  req.prune_max_bp = max_bp; req.prune_T = threshold_q20; req.prune_min_ac = min_ac; req.prune_max_ac = max_ac;
+  return make_result(idx, kKindPrune, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
 int vs_query_sample_gram(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t stat, vs_result** out) {
   VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "a Gram"));
   if (stat != VS_GRAM_DOT && stat != VS_GRAM_GRM) return fail(VS_ERR_ARG, "Gram statistic %u is neither VS_GRAM_DOT nor VS_GRAM_GRM", stat);
@@ -4427,6 +4560,14 @@ static int array_to_host(vs_result* r, const void* dev, size_t bytes, DevBuf* pi
 static int ld_block_begin_to_host(vs_result* r) {
   if (!r->h_block_begin.empty()) return VS_OK;
   VS_TRY(fetch(r->idx, r->h_block_begin, (const uint64_t*)r->d_ldm_meta, (size_t)r->d.Q + 1));
+  HIP_TRY(hipStreamSynchronize(r->idx->stream));
+  return VS_OK;
+}
+// keep_begin [Q + 1] and n_kept of a pruning result (the walk writes n_kept: the batch must have finished)
+static int prune_meta_to_host(vs_result* r) {
+  if (!r->h_prune_meta.empty()) return VS_OK;
+  VS_TRY(result_ready(r));
+  VS_TRY(fetch(r->idx, r->h_prune_meta, (const uint64_t*)r->d_prune_meta, 2 * ((size_t)r->d.Q + 1)));
   HIP_TRY(hipStreamSynchronize(r->idx->stream));
   return VS_OK;
 }
@@ -4624,7 +4765,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
         for (uint64_t a = r->h_var_begin[q] * G, e = a + r->h_nvar[q] * G; a < e; ++a) nc += c[a].x;
       r->n_carriers_kept = nc;
     }
-    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
+    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindPrune || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
       VS_TRY(result_ready(r));
       uint64_t nc = 0;
       HIP_TRY(hipMemcpyAsync(&nc, r->d_cell_total, 8, hipMemcpyDeviceToHost, idx->stream));
@@ -4777,6 +4918,39 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
         } else snprintf(num, sizeof num, "%d\n", (int)cell);
         out += num;
       }
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
+  if (r->kind == kKindPrune) {   // the region's reported rows with their verdicts
+    const VariantRow* rows;
+    if (r->have_headers) rows = r->h_rows.data() + a0;
+    else if (r->raw_rows) rows = r->raw_rows + a0;
+    else {
+      VS_TRY(fetch(idx, r->sl_rows, (const VariantRow*)r->d.rows + a0, (size_t)(a1 - a0)));
+      rows = r->sl_rows.data();
+    }
+    VS_TRY(array_to_host(r, r->d_state, (size_t)r->prune_states, &r->cells_pin, "pruning verdicts"));
+    VS_TRY(counts_to_host(r));
+    VS_TRY(prune_meta_to_host(r));
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    const uint8_t* st = (const uint8_t*)r->cells_pin.p + r->h_prune_meta[q];
+    const uint4* cnt = (const uint4*)r->counts_pin.p + a0;
+    std::string& out = r->text;
+    out = "Pos\tRef\tAlt\tAC\tState\n";
+    for (uint64_t a = a0; a < a1; ++a) {
+      const VariantRow& v = rows[a - a0];
+      if (v.count_flags & kRowDropped) continue;
+      out += std::to_string(v.pos);
+      out += '\t';
+      out.append(idx->seq_chars, v.ref_off, v.ref_len);
+      out += '\t';
+      out.append(idx->seq_chars, v.alt_off, v.alt_len);
+      out += '\t';
+      out += std::to_string(cnt[a - a0].y);
+      const uint8_t verdict = st[a - a0];
+      out += verdict == kPruneKept ? "\tkeep\n" : verdict == kPrunePruned ? "\tpruned\n" : "\tskip\n";
     }
     *text = out.c_str();
     if (len) *len = out.size();
@@ -5267,6 +5441,39 @@ int vs_result_ld_matrix_device(vs_result* r, uint64_t* n_regions, uint64_t* n_ro
   if (n_rows) *n_rows = r->d.A;
   if (n_cols) *n_cols = r->h_cols.size();
   if (stat) *stat = r->ld_stat;
+  return VS_OK;
+}
+
+int vs_result_get_ld_prune(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint32_t* params, const uint32_t** col_ids,
+                           const vs_allele_counts** counts, const uint64_t** keep_begin, const uint64_t** n_kept, const uint8_t** state) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!state) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindPrune) return fail(VS_ERR_ARG, "not a pruning result (vs_query_ld_prune)");
+  VS_TRY(array_to_host(r, r->d_state, (size_t)r->prune_states, &r->cells_pin, "pruning verdicts"));
+  VS_TRY(counts_to_host(r));
+  VS_TRY(prune_meta_to_host(r));
+  *state = (const uint8_t*)r->cells_pin.p;
+  if (counts) *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (keep_begin) *keep_begin = r->h_prune_meta.data();
+  if (n_kept) *n_kept = r->h_prune_meta.data() + (r->d.Q + 1);
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (params) { params[0] = r->ld_window; params[1] = r->prune_max_bp; params[2] = r->prune_T; params[3] = r->prune_min_ac; params[4] = r->prune_max_ac; }
+  if (col_ids) *col_ids = r->h_cols.data();
+  return VS_OK;
+}
+
+int vs_result_ld_prune_device(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, const void** dev_counts, const void** dev_keep_begin,
+                              const void** dev_n_kept, const void** dev_state) {
+  VS_TRY(device_matrix_ready(r, dev_state, kKindPrune, "not a pruning result (vs_query_ld_prune)"));
+  *dev_state = r->d_state;
+  if (dev_counts) *dev_counts = r->d_counts;
+  if (dev_keep_begin) *dev_keep_begin = r->d_prune_meta;
+  if (dev_n_kept) *dev_n_kept = r->d_prune_meta + (r->d.Q + 1);
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
   return VS_OK;
 }
 

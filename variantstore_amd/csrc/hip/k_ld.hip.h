@@ -68,19 +68,19 @@ __device__ __forceinline__ float ld_r2(int64_t n, int32_t sxy, int64_t sx, int64
   return (float)(cov * cov / ((double)vx * (double)vy));
 }
 
-template <int MAXT, bool R2>
-__global__ void __launch_bounds__(256) k_ld_band(LdArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t s_ld[];
+// The products of a workgroup of the band: acc[t] = the wave's 16-row tile against column tile t, summed over all columns.  Returns
+// the column tiles of this wave that hold a row of the table at all (wave-uniform).  k_ld_band and k_prune_hits (k_prune.hip.h)
+// share it: staging, fragments and MFMAs are one piece of code, the epilogues differ.
+template <int MAXT>
+__device__ __forceinline__ uint32_t ld_band_products(const LdArgs& a, uint8_t* s_ld, ld_i32x4 (&acc)[MAXT]) {
   const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const uint64_t row0 = (uint64_t)blockIdx.x * kLdRows;
-  if (row0 >= a.A) return;
-  const uint32_t W = a.window, nt = a.n_tiles;
+  const uint32_t nt = a.n_tiles;
   const uint32_t n_rows = kLdRows + 16 * (nt - 1);   // LDS rows: the block's and the halo's
   const uint32_t words = n_rows * (kLdChunk / 16);
   const uint64_t iw = row0 + 16 * wid;               // the wave's row tile
   // column tiles of this wave that hold a row of the table at all (wave-uniform)
   const uint32_t ntw = iw >= a.A ? 0u : (uint32_t)((a.A - iw + 15) / 16 < nt ? (a.A - iw + 15) / 16 : nt);
-  ld_i32x4 acc[MAXT];
 #pragma unroll
   for (int t = 0; t < MAXT; ++t) acc[t] = ld_i32x4{0, 0, 0, 0};
   const uint32_t frag = (16 * wid + (lane & 15)) * kLdStride + 16 * (lane >> 4);   // the lane's A fragment of k-step 0
@@ -109,6 +109,19 @@ __global__ void __launch_bounds__(256) k_ld_band(LdArgs a) {
         }
     }
   }
+  return ntw;
+}
+
+template <int MAXT, bool R2>
+__global__ void __launch_bounds__(256) k_ld_band(LdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t s_ld[];
+  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const uint64_t row0 = (uint64_t)blockIdx.x * kLdRows;
+  if (row0 >= a.A) return;
+  const uint32_t W = a.window;
+  const uint64_t iw = row0 + 16 * wid;               // the wave's row tile
+  ld_i32x4 acc[MAXT];
+  const uint32_t ntw = ld_band_products<MAXT>(a, s_ld, acc);
   // ---- epilogue: register g of the lane is the pair (row iw + 4 (lane >> 4) + g, column tile row lane & 15) ----
   const uint64_t i_first = iw + 4 * (lane >> 4);
   const int64_t n = (int64_t)a.n_cols;

@@ -76,6 +76,11 @@
 // k_ld_block            D D^T in full per region: the m x m block of every region of a batch, a pair of 64-row tiles per workgroup,
 //  k_ld_block_scan       found by bisection over the scan of the regions' workgroups; k_ld_band's staging, fragments and r^2, both
 //                       triangles stored once with plain stores (vs_query_ld_matrix: no reference counterpart)
+// k_prune_hits          greedy LD pruning of every region: k_ld_band's products (ld_band_products) with a third epilogue -- a bit per
+//  k_prune_scan          pair, r^2 > T / 2^20 decided in unsigned 128-bit integers, the mask rows assembled in LDS and stored once --,
+//  k_prune_greedy        the scan of the regions' row counts, and the walk: a wave per region, a 256-bit wave-uniform register of
+//                       blocked rows, the masks of 64 rows loaded ahead and taken with v_readlane, a state byte per row
+//                       (vs_query_ld_prune: no reference counterpart)
 // k_assoc_matrix        D Y over the same dosages: table rows x K traits (K up to 65,536) given as four int8 limbs of a fixed-point
 //                       value, 64 rows x 16 traits per workgroup, k_ld_band's staging and fragments, four MFMAs per 64-column step,
 //                       the limb sums combined in int64: exact dot products or the score test from 128-bit integers
@@ -114,6 +119,7 @@
 #include "k_matrix.hip.h"
 #include "k_ld.hip.h"
 #include "k_ld_block.hip.h"
+#include "k_prune.hip.h"
 #include "k_int128.hip.h"
 #include "k_gram.hip.h"
 #include "k_assoc_matrix.hip.h"
