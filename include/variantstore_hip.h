@@ -607,6 +607,63 @@ int vs_result_get_ld_prune(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, 
  * needs no event. */
 int vs_result_ld_prune_device(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, const void** dev_counts,
                               const void** dev_keep_begin, const void** dev_n_kept, const void** dev_state);
+/* LD clumping over regions: p-value-ordered greedy clumps of every region on the device, as `plink --clump` forms them -- how a
+ * scan becomes a list of independent loci, and how variants are chosen for a polygenic score (no reference counterpart).  The table
+ * T, its A rows, row_begin / row_count, the column set S with n columns, the count records, hit(i, j) with the threshold T / 2^20
+ * and keep_begin are exactly those of vs_query_ld_prune over the same regions and ids; hit is symmetric.
+ * P-values: pvalues[i] (float64) belongs to table row i, in table order -- the rows a vs_query_allele_counts batch over the same
+ * regions returns; there are A of them.  A p-value belongs to the variant: regions that share a row share it.  NaN: the row has no
+ * p-value.  The host turns each p-value into a 64-bit key, the bit pattern of the non-negative double (-0.0 counts as 0), which is
+ * monotone in p; p1 and p2 become keys the same way.  Priority is the pair (key, table row), ascending: ties go to the earlier row.
+ * The device compares unsigned integers only; no floating-point value takes part in any verdict.
+ * Candidates: row i is a candidate when it is not dropped, v_i > 0, it has a p-value and key_i <= key(p2); index-eligible when also
+ * key_i <= key(p1).
+ * Procedure, for every region on its own rows: walk the index-eligible candidates in priority order.  A row not yet assigned
+ * becomes an INDEX and owns itself; every not yet assigned candidate j of the region with 1 <= |i - j| <= window, max_bp == 0 or
+ * |pos_i - pos_j| <= max_bp, and hit(i, j) becomes a MEMBER with owner i (the window reaches both ways).  A candidate between p1 and
+ * p2 can only join.  Candidates left at the end are UNCLUMPED.  Equivalently: the INDEX rows are the lexicographically first maximal
+ * independent set of the index-eligible candidates under hit, in priority order, and the owner of any other candidate is the INDEX
+ * row of the highest priority that hits it inside the window.  Regions are independent, as for vs_query_ld_prune.
+ * Result: keep_begin[n + 1]; state[keep_begin[q] + a] (uint8): VS_CLUMP_MEMBER, VS_CLUMP_INDEX, VS_CLUMP_INELIGIBLE (no variance, no
+ * p-value, or a p-value above p2), VS_CLUMP_DROPPED or VS_CLUMP_UNCLUMPED; owner[keep_begin[q] + a] (uint32): the region-relative
+ * row of the index, VS_CLUMP_NO_OWNER for a row that is neither INDEX nor MEMBER; n_index[q] (uint64); the count records, the column
+ * ids and the parameters.  rounds[q] (uint64) is a diagnostic: the parallel rounds the region's greedy took; it is no part of the
+ * answer and may differ between runs.
+ * Checked on the host, in this order, before the handle's device is asked for (a handle opened without a device reports them first
+ * and VS_ERR_NO_DEVICE otherwise): n == 0, sample_ids == NULL with n_ids != 0, non-NULL sample_ids with n_ids == 0 -> VS_ERR_ARG;
+ * window == 0 or window > 256 -> VS_ERR_ARG ("window" in the message); threshold_q20 > 2^20 -> VS_ERR_ARG ("threshold"); pvalues ==
+ * NULL -> VS_ERR_ARG ("pvalues"); p1, then p2, NaN or outside [0, 1] -> VS_ERR_ARG ("p1" / "p2"); p1 > p2 -> VS_ERR_ARG ("above");
+ * a p-value that is neither NaN nor in [0, 1] -> VS_ERR_ARG (the message names the table row); id 0 or id >= num_samples ->
+ * VS_ERR_UNKNOWN_SAMPLE.  A is known on the device only: after the call's one host wait, n_pvalues != A -> VS_ERR_ARG with both
+ * numbers in the message.
+ * The uploaded keys (8 A bytes), the classes (A bytes), the temporary genotype matrix, the hit masks, the blocker masks (two masks of
+ * ceil(window / 32) words per verdict), `state`, `owner` and the per-region words together may not exceed option "matrix_max_mib"
+ * MiB: beyond it the call is refused with VS_ERR_ARG before anything is allocated for them; the message names regions, rows,
+ * columns, window and the parts in bytes.  The batch is never speculative and leaves the handle's type-6 state as it was.  What works
+ * on a pruning result works here; vs_result_format_region gives "Pos\tRef\tAlt\tAC\tP\tState\tIndex\n", then one line per reported,
+ * non-dropped row of the region: P as %.6g or "." without a p-value, State one of index, clumped, unclumped, skip, Index the owner
+ * as Pos:Ref:Alt or ".".  What a pruning result refuses this result refuses with the same codes; the other results' getters refuse
+ * it, and its getters refuse the others, with VS_ERR_ARG. */
+#define VS_CLUMP_MEMBER 0u
+#define VS_CLUMP_INDEX 1u
+#define VS_CLUMP_INELIGIBLE 2u
+#define VS_CLUMP_DROPPED 3u
+#define VS_CLUMP_UNCLUMPED 4u
+#define VS_CLUMP_NO_OWNER 0xFFFFFFFFu
+int vs_query_ld_clump(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, const double* pvalues,
+                      uint64_t n_pvalues, uint32_t window, uint32_t max_bp, uint32_t threshold_q20, double p1, double p2, vs_result** out);
+/* The verdicts of a clumping result copied into page-locked memory owned by the result: state and owner [keep_begin[n_regions]],
+ * keep_begin[n_regions + 1], n_index[n_regions], rounds[n_regions], counts[i] the count record of table row i over S, col_ids[c] the
+ * sample id of column c, params[3] = {window, max_bp, threshold_q20}, p_keys[2] the keys of p1 and p2 and p_bounds[2] the doubles.
+ * Every out-pointer but `state` and `owner` may be NULL.  VS_ERR_ARG on any other result. */
+int vs_result_get_ld_clump(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint32_t* params, uint64_t* p_keys, double* p_bounds,
+                           const uint32_t** col_ids, const vs_allele_counts** counts, const uint64_t** keep_begin, const uint64_t** n_index,
+                           const uint64_t** rounds, const uint8_t** state, const uint32_t** owner);
+/* State (keep_begin[n_regions] bytes), owner (as many uint32), keep_begin (n_regions + 1 uint64), n_index (n_regions uint64) and
+ * counts (n_rows records of 16 bytes) as they lie in HBM, valid until vs_result_free.  The engine has synchronised its stream when
+ * this returns: the caller needs no event. */
+int vs_result_ld_clump_device(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, const void** dev_counts,
+                              const void** dev_keep_begin, const void** dev_n_index, const void** dev_state, const void** dev_owner);
 /* Sample Gram matrix / GRM over regions: D^T D, the samples x samples product of the dosages -- what a GRM, kinship, IBS-type sharing
  * and the PCA of a cohort start from, and the one product of the dosage matrix the other column queries leave out (D Y:
  * vs_query_assoc_scan, D^T W: vs_query_sample_scores, the band of D D^T: vs_query_ld_band; no reference counterpart).  T, its rows, S

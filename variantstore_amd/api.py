@@ -84,6 +84,22 @@ def quantise_r2(r2):
     return int(math.floor(r2 * PRUNE_THRESHOLD_ONE + 0.5))
 
 
+CLUMP_NO_KEY = 0xFFFFFFFFFFFFFFFF   # the key of "no p-value" (NaN): above the key of every p-value
+
+
+def pvalue_keys(p):
+    """The 64-bit keys VariantStore.ld_clump orders p-values by: the bit pattern of each non-negative double (-0.0 counts as 0),
+    which is monotone in p; NaN ("no p-value") gives CLUMP_NO_KEY.  uint64, of p's shape.  ValueError for any other value outside
+    [0, 1]."""
+    p = np.asarray(p, dtype=np.float64)
+    nan = np.isnan(p)
+    if not np.all(nan | ((p >= 0.0) & (p <= 1.0))):
+        raise ValueError("p-values lie between 0 and 1 (NaN: none)")
+    keys = np.where(nan, 0.0, np.abs(p)).astype(np.float64).view(np.uint64).copy()   # (abs: -0.0)
+    keys[nan] = CLUMP_NO_KEY
+    return keys
+
+
 def _regions_array(regions):
     if isinstance(regions, DeviceArray):
         return regions, C.cast(C.c_void_p(regions.ptr), C.POINTER(Region)), regions.n
@@ -633,6 +649,80 @@ class QueryResult:
             if state == "keep":
                 out.append((int(pos), ref, alt))
         return out
+
+    CLUMP_STATES = {"member": 0, "index": 1, "ineligible": 2, "dropped": 3, "unclumped": 4}   # VS_CLUMP_*
+    CLUMP_NO_OWNER = 0xFFFFFFFF   # VS_CLUMP_NO_OWNER
+
+    def ld_clump(self):
+        """A clumping result (VariantStore.ld_clump) as numpy arrays: `state` (uint8, a verdict per reported row: CLUMP_STATES),
+        `owner` (uint32, the region-relative row of the verdict's index row, CLUMP_NO_OWNER for a row that is neither index nor
+        member), `keep_begin` (uint64[Q + 1]: region q's verdicts are state[keep_begin[q] : keep_begin[q + 1]], for the table rows
+        row_begin[q] .. + row_count[q]), `n_index` (uint64[Q]), `rounds` (uint64[Q], a diagnostic: the parallel rounds each region
+        took; not part of the answer), `pvalues` (float64 per table row, as the query took them), `threshold` / `threshold_q20`,
+        `window`, `max_bp`, `p1`, `p2`, `p1_key`, `p2_key`, `counts`, `columns`, the table's `rows` and per region `row_begin` and
+        `row_count`.  Copies, valid after the result is closed."""
+        nq, a, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        params = (C.c_uint32 * 3)()
+        pkeys, pb = (C.c_uint64 * 2)(), (C.c_double * 2)()
+        cols = C.POINTER(C.c_uint32)()
+        cnt = C.POINTER(_lib.AlleleCounts)()
+        kb, ni, rd = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        p, o = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint32)()
+        _check(self._lib.vs_result_get_ld_clump(self._h, C.byref(nq), C.byref(a), C.byref(c), params, pkeys, pb, C.byref(cols), C.byref(cnt),
+                                                C.byref(kb), C.byref(ni), C.byref(rd), C.byref(p), C.byref(o)), "vs_result_get_ld_clump")
+        q, na, nc = int(nq.value), int(a.value), int(c.value)
+        keep_begin = np.ctypeslib.as_array(kb, shape=(q + 1,)).copy()
+        n_index = np.ctypeslib.as_array(ni, shape=(q,)).copy() if q else np.zeros(0, np.uint64)
+        rounds = np.ctypeslib.as_array(rd, shape=(q,)).copy() if q else np.zeros(0, np.uint64)
+        total = int(keep_begin[q])
+        state = np.ctypeslib.as_array(p, shape=(total,)).copy() if total else np.zeros(0, np.uint8)
+        owner = np.ctypeslib.as_array(o, shape=(total,)).copy() if total else np.zeros(0, np.uint32)
+        counts = (np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint8)), shape=(na * 16,)).view(self.COUNT_DTYPE).copy() if na
+                  else np.zeros(0, self.COUNT_DTYPE))
+        raw = self.raw(with_carriers=False)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "columns": np.ctypeslib.as_array(cols, shape=(nc,)).copy(), "counts": counts, "state": state, "owner": owner,
+                "keep_begin": keep_begin, "n_index": n_index, "rounds": rounds, "pvalues": getattr(self, "_clump_pvalues", None),
+                "threshold": int(params[2]) / PRUNE_THRESHOLD_ONE, "threshold_q20": int(params[2]), "window": int(params[0]),
+                "max_bp": int(params[1]), "p1": float(pb[0]), "p2": float(pb[1]), "p1_key": int(pkeys[0]), "p2_key": int(pkeys[1])}
+
+    def ld_clump_device(self):
+        """(state address, owner address, keep_begin address, n_index address, counts address, n_regions, n_rows, n_cols) of a
+        clumping result as it lies in this GPU's memory: keep_begin[n_regions] verdict bytes and as many uint32 owners, n_regions + 1
+        and n_regions uint64 words and n_rows count records of four uint32, complete when this returns and valid until the result
+        is closed."""
+        nq, a, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        pc, pb, pn, ps, po = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_ld_clump_device(self._h, C.byref(nq), C.byref(a), C.byref(c), C.byref(pc), C.byref(pb), C.byref(pn),
+                                                   C.byref(ps), C.byref(po)), "vs_result_ld_clump_device")
+        return (int(ps.value or 0), int(po.value or 0), int(pb.value or 0), int(pn.value or 0), int(pc.value or 0), int(nq.value),
+                int(a.value), int(c.value))
+
+    def region_clumps(self, q):
+        """The clumps of region q of a clumping result: a list of ((pos, ref, alt), p, [member keys in table order]), one per index
+        row, in priority order (p ascending, ties by table order)."""
+        clumps, order = {}, []
+        for k, line in enumerate(self.region_text(q).split("\n")[1:]):
+            if not line:
+                continue
+            pos, ref, alt, _ac, p, state, index = line.split("\t")
+            key = (int(pos), ref, alt)
+            if state == "index":
+                clumps.setdefault(key, [None, []])[0] = float(p)
+                order.append((float(p), k, key))
+            elif state == "clumped":
+                ipos, iref, ialt = index.split(":")
+                clumps.setdefault((int(ipos), iref, ialt), [None, []])[1].append(key)
+        if not order:
+            return []
+        # (the text prints p with six digits: the order comes from the p-values the query took)
+        got = self.ld_clump()
+        a0, m, o = int(got["row_begin"][q]), int(got["row_count"][q]), int(got["keep_begin"][q])
+        live = [a for a in range(a0, a0 + m) if got["state"][o + a - a0] != self.CLUMP_STATES["dropped"]]
+        exact = pvalue_keys(got["pvalues"][live]) if got["pvalues"] is not None else None
+        ranked = sorted(order, key=lambda t: ((int(exact[t[1]]) if exact is not None else t[0]), t[1]))
+        pv = got["pvalues"]
+        return [(key, float(pv[live[k]]) if pv is not None else clumps[key][0], clumps[key][1]) for _p, k, key in ranked]
 
     def region_ld(self, q):
         """The pairs region q of an LD result reports: a list of dicts with `a` and `b` (each (pos, ref, alt)) and `value` (int under
@@ -1363,6 +1453,73 @@ class VariantStore:
                 w[i] = v
                 seen.add(key)
         return w, [key for key in table if key not in seen]
+
+    def _table_keys(self, regions):
+        """The (pos, ref, alt) of every table row of a batch, in table order (None for a row under the duplicate rule, which no
+        region reports), through an allele_counts batch over the same regions."""
+        counts = self.allele_counts(regions)
+        try:
+            got = counts.allele_counts()
+            dropped = (got["rows"]["count_flags"] >> 31) != 0
+            keys = [None] * got["rows"].shape[0]
+            for q in range(got["row_begin"].shape[0]):
+                a0, m = int(got["row_begin"][q]), int(got["row_count"][q])
+                live = [a for a in range(a0, a0 + m) if not dropped[a]]
+                if all(keys[a] is not None for a in live):
+                    continue
+                lines = [line for line in counts.region_text(q).split("\n")[1:] if line]
+                assert len(lines) == len(live)
+                for a, line in zip(live, lines):
+                    f = line.split("\t")
+                    keys[a] = (int(f[0]), f[1], f[2])
+        finally:
+            counts.close()
+        return keys
+
+    def _pvalues_from_mapping(self, regions, mapping):
+        """The float64 array in table order of a {(pos, ref, alt): p} mapping (NaN for a row without a key), and the keys that
+        matched no row."""
+        table = {(int(k[0]), str(k[1]), str(k[2])): float(v) for k, v in mapping.items()}
+        keys = self._table_keys(regions)
+        seen = set()
+        pv = np.full(len(keys), np.nan, np.float64)
+        for i, key in enumerate(keys):
+            if key in table:
+                pv[i] = table[key]
+                seen.add(key)
+        return pv, [key for key in table if key not in seen]
+
+    def ld_clump(self, regions, pvalues, samples=None, window=256, r2=0.5, max_bp=250_000, p1=1e-4, p2=1e-2) -> QueryResult:
+        """LD clumping over regions (vs_query_ld_clump), as `plink --clump`: for every region its rows are taken in order of
+        significance; the best one with p <= `p1` becomes an index row, every row with p <= `p2` among the `window` (1 .. 256) rows
+        on either side of it (at most `max_bp` positions away; 0: no limit) whose squared dosage correlation with it over `samples`
+        is above `r2` joins its clump; the next best row that is still unclaimed starts the next clump.  `pvalues`: an array of A
+        float64 in table order (the rows an allele_counts batch over the same regions returns; NaN: no p-value), or a mapping
+        {(pos, ref, alt): p}, resolved through an allele_counts batch: rows without a key get NaN, keys that matched no row come
+        back as `result.unmatched`.  The p-values become 64-bit keys (pvalue_keys) and r2 the integer T = quantise_r2(r2): the
+        device compares integers only, ties go to the earlier row.  Regions are independent.  Read the result with
+        QueryResult.ld_clump / ld_clump_device / region_clumps / region_text."""
+        threshold = quantise_r2(r2)
+        unmatched = None
+        if isinstance(pvalues, dict):
+            pv, unmatched = self._pvalues_from_mapping(regions, pvalues)
+        else:
+            pv = np.ascontiguousarray(np.asarray(pvalues, dtype=np.float64))
+            if pv.ndim != 1:
+                raise ValueError("pvalues: one float64 per table row")
+        arr, ptr, n = _regions_array(regions)
+        h = C.c_void_p()
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        window = int(window)
+        if not 0 <= window <= 0xFFFFFFFF:   # (ctypes would wrap it: 0 is refused by the C ABI like any window outside 1 .. 256)
+            window = 0
+        buf = pv if pv.shape[0] else np.zeros(1, np.float64)   # (the C ABI refuses NULL)
+        _check(self._lib.vs_query_ld_clump(self._h, ptr, n, ids_ptr, n_ids, buf.ctypes.data_as(C.POINTER(C.c_double)), pv.shape[0], window,
+                                           int(max_bp) & 0xFFFFFFFF, threshold, float(p1), float(p2), C.byref(h)), "vs_query_ld_clump")
+        res = QueryResult(self, h)
+        res.unmatched = unmatched
+        res._clump_pvalues = pv.copy()
+        return res
 
     def get_sample_var_in_ref(self, regions, sample) -> QueryResult:
         """Query type 4 for one sample over a batch of regions (query.h:618-729)."""

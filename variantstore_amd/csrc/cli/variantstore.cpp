@@ -41,6 +41,7 @@
 #include <fstream>
 #include <iostream>
 #include <map>
+#include <sstream>
 #include <string>
 #include <thread>
 #include <tuple>
@@ -118,6 +119,8 @@ struct Args {
   uint32_t ld_window = 64;   // `ld`: every row against the next ld_window rows; --dot: dot products instead of r^2
   bool ld_dot = false;
   uint32_t prune_max_bp = 0, prune_threshold = 209715;   // `prune`: --bp, and --r2 as floor(r2 * 2^20 + 0.5) (0.2 by default)
+  std::string pvalues_file;   // `clump`: -A, lines of "pos ref alt p"; --p1, --p2: the bounds of the index rows and of the clumped rows
+  double clump_p1 = 1e-4, clump_p2 = 1e-2;
   bool gram_grm = false;      // `gram`: the GRM (float64) instead of the dosage products (int64)
   bool ibs_king = false;      // `ibs`: the kinship column beside the counts; --min-kinship X: only pairs with kinship >= X (implies --king)
   bool ibs_have_min = false;
@@ -1210,7 +1213,65 @@ int prune_usage() {
   return EXIT_FAILURE;
 }
 
-int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false, bool ldmatrix = false, bool prune = false) {
+// `variantstore clump`: p-value clumping of every region (vs_query_ld_clump) over the same samples.  Output as `prune`: "#region
+// <i> <x>:<y>", then the region's text ("Pos Ref Alt AC P State Index", a line per reported row: index, clumped, unclumped or skip).
+int clump_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore clump -p <output-prefix> -r <region> -A <p-value-file> [-S <sample-name-file>] [-w <window>] [--r2 <bound>]\n"
+               "                           [--bp <n>] [--p1 <bound>] [--p2 <bound>] [-o <outfile>] [--device <n>]\n\n"
+               "        For every region the clumps of its variants (as query type 6 reports them), as `plink --clump` forms them: the\n"
+               "        variants are taken in order of their p-values (lines of \"pos ref alt p\" in the file, an empty allele written as\n"
+               "        - or .; variants without a line have no p-value and are skipped); the best one with p <=\n"
+               "        --p1 (0.0001 by default) becomes an index variant, every variant with p <= --p2 (0.01 by default) among the\n"
+               "        <window> rows on either side of it (1 .. 256, 256 by default; at most --bp positions away, 250000 by default, 0:\n"
+               "        no limit) whose squared dosage correlation with it is above --r2 (0 .. 1, 0.5 by default) joins its clump; the\n"
+               "        next best unclaimed variant starts the next clump.  Over the whole cohort or the samples named in the file.\n";
+  return EXIT_FAILURE;
+}
+
+// The p-value of every table row of the batch, in table order, from the lines of "pos ref alt p" (NaN: no line names the row); the
+// rows through a count batch over the same regions.  Lines that matched no row are counted for the warning.
+int clump_pvalues(vs_index* idx, const std::vector<vs_region>& batch, const std::string& path, std::vector<double>& pvalues, size_t& unmatched) {
+  std::ifstream in(path);
+  if (!in) { error("cannot open p-value file " + path); return EXIT_FAILURE; }
+  std::map<std::string, std::pair<double, bool>> table;   // "pos\tref\talt" -> (p, matched)
+  std::string line;
+  size_t lineno = 0;
+  while (std::getline(in, line)) {
+    ++lineno;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    if (line.empty() || line[0] == '#') continue;
+    std::istringstream ls(line);
+    std::string pos, ref, alt, pv;
+    if (!(ls >> pos >> ref >> alt >> pv)) { error("p-value file line " + std::to_string(lineno) + ": expected \"pos ref alt p\""); return EXIT_FAILURE; }
+    char* end = nullptr;
+    const double p = strtod(pv.c_str(), &end);
+    if (*end != '\0' || !(std::isnan(p) || (p >= 0.0 && p <= 1.0))) { error("p-value file line " + std::to_string(lineno) + ": '" + pv + "' is no p-value between 0 and 1"); return EXIT_FAILURE; }
+    const auto allele = [](const std::string& x) { return x == "-" || x == "." ? std::string() : x; };   // (an empty allele, as for `score`)
+    table[pos + "\t" + allele(ref) + "\t" + allele(alt)] = {p, false};
+  }
+  vs_result* res = nullptr;
+  int rc = vs_query_allele_counts(idx, batch.data(), batch.size(), nullptr, 0, &res);
+  if (rc != VS_OK) die(rc, "clump");
+  vs_result_raw raw;
+  rc = vs_result_get_raw(res, 0, &raw);
+  if (rc != VS_OK) die(rc, "clump");
+  pvalues.assign(raw.n_rows, std::nan(""));
+  for (uint64_t i = 0; i < raw.n_rows; ++i) {
+    const vs_variant_row& v = raw.rows[i];
+    if (VS_ROW_DROPPED(v)) continue;
+    const auto it = table.find(std::to_string(v.pos) + "\t" + std::string(raw.seq_pool + v.ref_off, v.ref_len) + "\t" + std::string(raw.seq_pool + v.alt_off, v.alt_len));
+    if (it == table.end()) continue;
+    pvalues[i] = it->second.first;
+    it->second.second = true;
+  }
+  vs_result_free(res);
+  unmatched = 0;
+  for (const auto& kv : table) unmatched += !kv.second.second;
+  return EXIT_SUCCESS;
+}
+
+int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false, bool ldmatrix = false, bool prune = false, bool clump = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
   if (rc != VS_OK) die(rc, "load");
@@ -1235,13 +1296,22 @@ int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool
   std::vector<vs_region> batch;
   for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
   vs_result* res = nullptr;
-  if (prune) rc = vs_query_ld_prune(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_window, a.prune_max_bp, a.prune_threshold, a.min_ac, a.max_ac, &res);
+  if (clump) {
+    std::vector<double> pvalues;
+    size_t unmatched = 0;
+    if (clump_pvalues(idx, batch, a.pvalues_file, pvalues, unmatched) != EXIT_SUCCESS) { vs_index_close(idx); return EXIT_FAILURE; }
+    if (unmatched) std::cerr << "warning: " << unmatched << " line(s) of " << a.pvalues_file << " name no variant of the regions\n";
+    const double none = 0.0;   // (an empty table: the C ABI takes no NULL)
+    rc = vs_query_ld_clump(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), pvalues.empty() ? &none : pvalues.data(), pvalues.size(),
+                           a.ld_window, a.prune_max_bp, a.prune_threshold, a.clump_p1, a.clump_p2, &res);
+  }
+  else if (prune) rc = vs_query_ld_prune(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_window, a.prune_max_bp, a.prune_threshold, a.min_ac, a.max_ac, &res);
   else if (ldmatrix) rc = vs_query_ld_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_dot ? VS_LD_DOT : VS_LD_R2, &res);
   else if (ld) rc = vs_query_ld_band(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_window, a.ld_dot ? VS_LD_DOT : VS_LD_R2, &res);
   else if (genotypes) rc = vs_query_genotype_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
   else if (burden) rc = vs_query_sample_burden(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.min_ac, a.max_ac, &res);
   else rc = vs_query_allele_counts(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
-  if (rc != VS_OK) die(rc, prune ? "prune" : ldmatrix ? "ldmatrix" : ld ? "ld" : genotypes ? "genotypes" : burden ? "burden" : "counts");
+  if (rc != VS_OK) die(rc, clump ? "clump" : prune ? "prune" : ldmatrix ? "ldmatrix" : ld ? "ld" : genotypes ? "genotypes" : burden ? "burden" : "counts");
   std::ofstream file;
   if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
   std::ostream& out = a.outfile.empty() ? std::cout : file;
@@ -1269,6 +1339,7 @@ int main(int argc, char** argv) {
     if (i + 1 >= argc) { std::cerr << "missing value for " << argv[i] << "\n"; exit(EXIT_FAILURE); }
     return argv[++i];
   };
+  if (a.cmd == "clump") { a.ld_window = 256; a.prune_max_bp = 250000; a.prune_threshold = 524288; }   // plink's defaults: 250 kb, r2 0.5
   for (int i = 2; i < argc; ++i) {
     std::string f = argv[i];
     if (a.cmd == "construct") {
@@ -1299,18 +1370,26 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "prune" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "prune" || a.cmd == "clump" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if ((a.cmd == "burden" || a.cmd == "prune") && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if ((a.cmd == "burden" || a.cmd == "prune") && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
-      else if ((a.cmd == "ld" || a.cmd == "prune") && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if ((a.cmd == "ld" || a.cmd == "prune" || a.cmd == "clump") && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if ((a.cmd == "ld" || a.cmd == "ldmatrix") && f == "--dot") a.ld_dot = true;
-      else if (a.cmd == "prune" && f == "--bp") a.prune_max_bp = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
-      else if (a.cmd == "prune" && f == "--r2") {
+      else if ((a.cmd == "prune" || a.cmd == "clump") && f == "--bp") a.prune_max_bp = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if (a.cmd == "clump" && (f == "-A" || f == "--pvalues")) a.pvalues_file = need(i);
+      else if (a.cmd == "clump" && (f == "--p1" || f == "--p2")) {
+        const std::string v = need(i);
+        char* end = nullptr;
+        const double p = strtod(v.c_str(), &end);
+        if (v.empty() || *end != '\0' || !(p >= 0.0 && p <= 1.0)) { std::cerr << f << " takes a bound between 0 and 1, not '" << v << "'\n"; return clump_usage(); }
+        (f == "--p1" ? a.clump_p1 : a.clump_p2) = p;
+      }
+      else if ((a.cmd == "prune" || a.cmd == "clump") && f == "--r2") {
         const std::string v = need(i);
         char* end = nullptr;
         const double r2 = strtod(v.c_str(), &end);
-        if (v.empty() || *end != '\0' || !(r2 >= 0.0 && r2 <= 1.0)) { std::cerr << "--r2 takes a bound between 0 and 1, not '" << v << "'\n"; return prune_usage(); }
+        if (v.empty() || *end != '\0' || !(r2 >= 0.0 && r2 <= 1.0)) { std::cerr << "--r2 takes a bound between 0 and 1, not '" << v << "'\n"; return a.cmd == "clump" ? clump_usage() : prune_usage(); }
         a.prune_threshold = (uint32_t)std::floor(r2 * 1048576.0 + 0.5);
       }
       else if (a.cmd == "gram" && f == "--grm") a.gram_grm = true;
@@ -1368,6 +1447,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "prune") {
     if (a.prefix.empty() || a.region.empty()) return prune_usage();
     return counts_main(a, /*burden=*/false, /*genotypes=*/false, /*ld=*/false, /*ldmatrix=*/false, /*prune=*/true);
+  }
+  if (a.cmd == "clump") {
+    if (a.prefix.empty() || a.region.empty() || a.pvalues_file.empty()) return clump_usage();
+    return counts_main(a, /*burden=*/false, /*genotypes=*/false, /*ld=*/false, /*ldmatrix=*/false, /*prune=*/false, /*clump=*/true);
   }
   if (a.cmd == "ldmatrix") {
     if (a.prefix.empty() || a.region.empty()) return ldmatrix_usage();

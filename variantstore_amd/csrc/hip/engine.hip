@@ -248,7 +248,7 @@ struct vs_result {
                  // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts; kKindAssoc: association scan;
                  // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM; kKindIbs: pairwise IBS counts / KING kinship;
                  // kKindLdMatrix: the full LD block of every region; kKindAssocMatrix: trait-matrix association scan;
-                 // kKindScoreMatrix: score matrix; kKindPrune: LD pruning verdicts
+                 // kKindScoreMatrix: score matrix; kKindPrune: LD pruning verdicts; kKindClump: p-value clumping verdicts
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -315,6 +315,16 @@ struct vs_result {
   uint64_t prune_states = 0;
   uint32_t prune_max_bp = 0, prune_T = 0, prune_min_ac = 0, prune_max_ac = UINT32_MAX;
   std::vector<uint64_t> h_prune_meta;
+  // clumping results (vs_query_ld_clump): d_state, d_prune_meta, prune_states, ld_window, prune_max_bp and prune_T as for a pruning
+  // result -- the words are keep_begin [Q + 1], n_index [Q + 1, the last unused], the scan's summary, d_cell_total, then the rounds
+  // every region took [Q + 1, the last unused] --, an owner per verdict beside the state (d_owner, its page-locked copy owner_pin),
+  // the keys of the table rows as the caller's p-values gave them (h_clump_keys: the batch uploads them, the text prints them), p1
+  // and p2 with their keys
+  uint32_t* d_owner = nullptr;
+  DevBuf owner_pin{nullptr, 0};
+  std::vector<uint64_t> h_clump_keys;
+  double clump_p[2] = {0.0, 0.0};
+  uint64_t clump_key[2] = {0, 0};
   // Gram results (vs_query_sample_gram): one buffer of 8-byte words in HBM -- gram [n x n] int64, col_weighted [n] int64, C, H, the
   // nonzero cells of the (temporary) genotype matrix (d_cell_total, two words), then from gram_grm_off on grm [n x n] float64 under
   // VS_GRAM_GRM -- copied to cells_pin in one piece; the count record of every table row in d_counts / counts_pin, the column ids h_cols
@@ -351,8 +361,9 @@ constexpr int kKindLdMatrix = 17;   // ... of an LD-matrix result: the rows of t
 constexpr int kKindAssocMatrix = 18;   // ... of a trait-matrix association result: the rows of type 6, a score per row and trait (up to VS_TRAIT_MATRIX_MAX traits) instead of carrier lists
 constexpr int kKindScoreMatrix = 19;   // ... of a score-matrix result: the rows of type 6, a columns x scores matrix of weighted dosage sums (up to VS_SCORE_MATRIX_MAX scores) instead of carrier lists
 constexpr int kKindPrune = 20;   // ... of a pruning result: the rows of type 6, a verdict byte per reported row instead of carrier lists
+constexpr int kKindClump = 21;   // ... of a clumping result: the rows of type 6, a verdict byte and an owner per reported row instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindPrune || r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
+  return r->kind == kKindClump || r->kind == kKindPrune || r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
          r->kind == kKindScores;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
@@ -373,6 +384,8 @@ static int refuse_no_lists(const vs_result* r, const char* what) {
     return fail(VS_ERR_UNSUPPORTED, "%s: an IBS result holds samples x samples matrices of genotype-state counts, no carrier lists (vs_result_get_sample_ibs)", what);
   if (r->kind == kKindLdMatrix)
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD-matrix result holds a square block of pair statistics per region, no carrier lists (vs_result_get_ld_matrix)", what);
+  if (r->kind == kKindClump)
+    return fail(VS_ERR_UNSUPPORTED, "%s: a clumping result holds a verdict and an owner per reported row, no carrier lists (vs_result_get_ld_clump)", what);
   if (r->kind == kKindPrune)
     return fail(VS_ERR_UNSUPPORTED, "%s: a pruning result holds a verdict per reported row, no carrier lists (vs_result_get_ld_prune)", what);
   if (r->kind == kKindLd)
@@ -1241,7 +1254,9 @@ static int capture_totals(vs_result* r) {
 // ScoreMatrix: mask, rank and n_cols as for the matrix; `weights` (host memory), n_weights and n_scores as for Scores; `sm_shift`: f_k
 // per weight column, formed on the host.
 // Prune: as LD (ld_window) with the walk's parameters: prune_max_bp, prune_T (0 .. 2^20), prune_min_ac, prune_max_ac.
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix, Prune };
+// Clump: as Prune without the allele-count window; `clump_keys` (host memory, owned by the result), n_pvalues of them, held against
+// the number of table rows once the plan has given it; clump_key: the keys of p1 and p2.
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix, Prune, Clump };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1250,6 +1265,8 @@ struct SharedReq {
   uint32_t n_cols = 0, min_ac = 0, max_ac = UINT32_MAX;
   uint32_t ld_window = 0, ld_stat = 0, gram_stat = 0, ibs_stat = 0;
   uint32_t prune_max_bp = 0, prune_T = 0, prune_min_ac = 0, prune_max_ac = UINT32_MAX;
+  const uint64_t* clump_keys = nullptr;
+  uint64_t n_pvalues = 0, clump_key[2] = {0, 0};
   const uint64_t* pheno = nullptr;
   size_t pheno_words = 0;
   uint32_t n_traits = 0, assoc_stat = 0;
@@ -1633,6 +1650,8 @@ static int launch_ibs(vs_index* idx, vs_result* r, const uint8_t* cells, uint64_
 //                      Prune: in front of them k_prune_scan over the per-region row counts and one host wait for its total
 //                      (prune_tables: the size limit, the temporary matrix and masks, the state); behind them k_prune_hits and
 //                      k_prune_greedy (launch_prune)
+//                      Clump: as Prune up to k_prune_hits (clump_tables also uploads the keys); behind it k_clump_class,
+//                      k_clump_blockers and k_clump_rounds (launch_clump)
 //   shared_finish      enqueued: the completion event | synchronous: k_post_done, a word in mapped host memory, the host spins on it
 // A column request is never speculative, has no arena, and leaves the handle's type-6 state (size hints, sort hint) as it found
 // it: count batches interleaved with type-6 batches change none of theirs.
@@ -1675,10 +1694,13 @@ struct SharedCtx {
   uint32_t* u_site = nullptr;   // shared_rows: the site of every shared row (a column request: of every row)
   uint8_t* ld_matrix = nullptr; // shared_tables: the temporary genotype matrix of an LD batch (ld_tmp); an LD-matrix batch: ld_matrix_tables
   uint32_t* prune_hits = nullptr;   // prune_tables: a pruning batch's hit masks (ld_tmp)
+  uint64_t* clump_keys = nullptr;   // clump_tables: a clumping batch's keys, classes and blocker masks (ld_tmp)
+  uint8_t* clump_cls = nullptr;
+  uint32_t* clump_blockers = nullptr;
   uint64_t* am_dev = nullptr;   // shared_tables: a trait-matrix batch's Sy, vy, shifts and limb panel on the device (ld_tmp)
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix || q.kind == ReqKind::Prune) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix || q.kind == ReqKind::Prune || q.kind == ReqKind::Clump) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -1971,6 +1993,26 @@ static int prune_fits(SharedCtx& c, uint64_t states) {
               (unsigned long long)(r->d.A * r->mx_pitch), (unsigned long long)(r->d.A * mask_row), (unsigned long long)states, (unsigned long long)region_bytes,
               (unsigned long long)(cap >> 20));
 }
+// A clumping batch: per table row the temporary matrix, the hit masks, the key (8 bytes) and the class (1 byte); per verdict the
+// state (1 byte), the owner (4 bytes) and the blocker masks (two masks); the per-region words.  All together under the same limit,
+// `states` as for prune_fits.
+static int clump_fits(SharedCtx& c, uint64_t states) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  r->mx_pitch = ((uint64_t)c.req.n_cols + 15) & ~15ull;
+  const uint64_t mask_row = 4ull * ((c.req.ld_window + 31) / 32), row_bytes = r->mx_pitch + mask_row + 9, slot_bytes = 5 + 2 * mask_row;
+  const uint64_t region_bytes = 8 * (3 * (r->d.Q + 1) + 4);   // (Q < 2^32)
+  if (region_bytes <= cap && states <= (cap - region_bytes) / slot_bytes && r->d.A <= (cap - region_bytes - states * slot_bytes) / row_bytes) return VS_OK;
+  (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+  (void)hipStreamSynchronize(idx->stream);
+  return fail(VS_ERR_ARG, "an LD clumping of %llu regions over %llu rows x %u columns with window %u takes %llu bytes (%llu of the genotype matrix it is formed from, "
+              "%llu of the hit masks, %llu of the keys and classes, %llu of the blocker masks, %llu of the verdicts and owners, %llu of the per-region arrays), more than "
+              "the limit of %llu MiB (option matrix_max_mib): split the batch",
+              (unsigned long long)r->d.Q, (unsigned long long)r->d.A, c.req.n_cols, c.req.ld_window,
+              (unsigned long long)(r->d.A * row_bytes + states * slot_bytes + region_bytes), (unsigned long long)(r->d.A * r->mx_pitch),
+              (unsigned long long)(r->d.A * mask_row), (unsigned long long)(r->d.A * 9), (unsigned long long)(states * 2 * mask_row), (unsigned long long)(states * 5),
+              (unsigned long long)region_bytes, (unsigned long long)(cap >> 20));
+}
 // Reads the totals (*pt) or the speculation.  Leaves U / n_slow / n_runs, the result's sizes and bookkeeping, a speculative batch
 // registered with its slot, what the request's kind allocates, and the form of the rows and the expansion (n_fill .. lean).
 static int shared_tables(SharedCtx& c) {
@@ -2097,6 +2139,15 @@ static int shared_tables(SharedCtx& c) {
       r->ld_window = q.ld_window;
       r->prune_max_bp = q.prune_max_bp; r->prune_T = q.prune_T; r->prune_min_ac = q.prune_min_ac; r->prune_max_ac = q.prune_max_ac;
       break;
+    case ReqKind::Clump:   // (as Prune: the keys, the temporaries, the state and the owners wait for clump_tables, behind the permutation)
+      VS_TRY(clump_fits(c, 0));
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      VS_TRY(ralloc(r, 3 * (size_t)(d.Q + 1) + 4, &r->d_prune_meta));
+      r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_prune_meta + 2 * (d.Q + 1) + 2);
+      r->ld_window = q.ld_window;
+      r->prune_max_bp = q.prune_max_bp; r->prune_T = q.prune_T;
+      break;
   }
   c.async_fill = c.allow_async && idx->opts.async_fill && c.n_fill > 0;
   c.fused = idx->opts.fill_fused && c.lists && !c.resident && !c.async_fill;
@@ -2213,12 +2264,15 @@ static int launch_assoc_matrix(SharedCtx& c);
 static int launch_ld_block(vs_index* idx, vs_result* r, const uint8_t* cells, const SharedReq& lq);
 static int prune_tables(SharedCtx& c);
 static int launch_prune(SharedCtx& c);
+static int clump_tables(SharedCtx& c);
+static int launch_clump(SharedCtx& c);
 static int shared_columns(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
   if (!c.behind_perm && !r->d.A) return VS_OK;
   if (c.req.kind == ReqKind::LdMatrix) VS_TRY(ld_matrix_tables(c));   // (its one host wait in front of the pair of events: they time kernels only)
   if (c.req.kind == ReqKind::AssocMatrix) VS_TRY(assoc_matrix_upload(c));   // (in front of the pair of events as well)
   if (c.req.kind == ReqKind::Prune) VS_TRY(prune_tables(c));   // (its one host wait in front of the pair of events as well)
+  if (c.req.kind == ReqKind::Clump) VS_TRY(clump_tables(c));   // (the same wait, and the upload of the keys)
   VS_TRY(result_events(r));
   HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
   if (c.req.kind == ReqKind::Groups) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, r->d_counts);
@@ -2238,6 +2292,9 @@ static int shared_columns(SharedCtx& c) {
   } else if (c.req.kind == ReqKind::Prune) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_prune(c));
+  } else if (c.req.kind == ReqKind::Clump) {
+    VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+    VS_TRY(launch_clump(c));
   } else if (c.req.kind == ReqKind::AssocMatrix) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_assoc_matrix(c));
@@ -2561,6 +2618,81 @@ static int launch_prune(SharedCtx& c) {
   g.state = r->d_state; g.n_kept = r->d_prune_meta + (d.Q + 1);
   if (d.Q > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu regions)", (unsigned long long)d.Q);
   hipLaunchKernelGGL(k_prune_greedy, dim3((unsigned)d.Q), dim3(64), 0, idx->stream, g);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+
+// A clumping batch behind the permutation: prune_tables' scan and its ONE host wait; then the number of p-values is held against
+// the table's rows and everything the batch takes against option matrix_max_mib, before any of it is allocated.  The keys go up
+// from the result's own copy.
+static int clump_tables(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  uint64_t* meta = r->d_prune_meta;
+  hipLaunchKernelGGL(k_prune_scan, dim3(1), dim3(kPruneScanThreads), 0, idx->stream, (const uint64_t*)d.q_nvar, d.Q, meta, meta + 2 * (d.Q + 1));
+  HIP_TRY(hipGetLastError());
+  uint64_t sum[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(sum, meta + 2 * (d.Q + 1), sizeof sum, hipMemcpyDeviceToHost, idx->stream));
+  HIP_TRY(hipStreamSynchronize(idx->stream));
+  if (c.req.n_pvalues != d.A) {
+    (void)hipStreamSynchronize(c.ps);   // (as prune_fits: the plan's last kernels still read the call's temporaries)
+    return fail(VS_ERR_ARG, "%llu p-values for the %llu rows of the regions' table: one p-value per table row, in table order",
+                (unsigned long long)c.req.n_pvalues, (unsigned long long)d.A);
+  }
+  VS_TRY(clump_fits(c, sum[0]));
+  r->prune_states = sum[0];
+  const uint32_t words = (c.req.ld_window + 31) / 32;
+  VS_TRY(dev_alloc(idx, (size_t)(d.A * r->mx_pitch), (void**)&c.ld_matrix, &c.ld_tmp.bufs));
+  VS_TRY(dev_alloc(idx, (size_t)(d.A * words) * 4, (void**)&c.prune_hits, &c.ld_tmp.bufs));
+  VS_TRY(dev_alloc(idx, (size_t)d.A * 8, (void**)&c.clump_keys, &c.ld_tmp.bufs));
+  VS_TRY(dev_alloc(idx, (size_t)d.A, (void**)&c.clump_cls, &c.ld_tmp.bufs));
+  VS_TRY(dev_alloc(idx, (size_t)(sum[0] * words) * 8, (void**)&c.clump_blockers, &c.ld_tmp.bufs));
+  VS_TRY(ralloc(r, (size_t)sum[0], &r->d_state));
+  VS_TRY(ralloc(r, (size_t)sum[0], &r->d_owner));
+  if (d.A) {
+    HIP_TRY(hipMemcpyAsync(c.clump_keys, c.req.clump_keys, (size_t)d.A * 8, hipMemcpyHostToDevice, idx->stream));
+    HIP_TRY(hipStreamSynchronize(idx->stream));   // (in front of the pair of events: they time kernels only)
+  }
+  return VS_OK;
+}
+
+// The verdicts of a clumping batch: k_prune_hits as for a pruning batch, then the classes of the table rows, the blocker masks of
+// the verdict slots and the rounds, one workgroup per region, all regions in one launch.
+static int launch_clump(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  const SharedReq& q = c.req;
+  const uint32_t words = (q.ld_window + 31) / 32;
+  ClumpArgs g{};
+  g.Q = d.Q; g.A = d.A; g.states = r->prune_states;
+  g.row_begin = (const uint64_t*)d.var_begin; g.row_count = (const uint64_t*)d.q_nvar; g.keep_begin = r->d_prune_meta;
+  g.rows = (const VariantRow*)d.rows; g.counts = r->d_counts; g.keys = c.clump_keys; g.hits = c.prune_hits;
+  g.cls = c.clump_cls; g.blockers = c.clump_blockers;
+  g.words = words; g.window = q.ld_window; g.n_cols = q.n_cols; g.key1 = q.clump_key[0]; g.key2 = q.clump_key[1];
+  g.state = r->d_state; g.owner = r->d_owner; g.n_index = r->d_prune_meta + (d.Q + 1); g.rounds = r->d_prune_meta + 2 * (d.Q + 1) + 4;
+  if (d.A) {
+    PruneHitArgs p{};
+    p.ld.cells = c.ld_matrix; p.ld.A = d.A; p.ld.pitch = (uint32_t)r->mx_pitch; p.ld.n_cols = q.n_cols;
+    p.ld.window = q.ld_window; p.ld.n_tiles = (q.ld_window + 15) / 16 + 1;
+    p.ld.counts = r->d_counts; p.ld.band = nullptr;
+    p.rows = (const VariantRow*)d.rows; p.hits = c.prune_hits; p.words = words; p.max_bp = q.prune_max_bp; p.threshold = q.prune_T;
+    const uint64_t blocks = (d.A + kLdRows - 1) / kLdRows;
+    if (blocks > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu row blocks)", (unsigned long long)blocks);
+    const size_t lds = (size_t)(kLdRows + 16 * (p.ld.n_tiles - 1)) * kLdStride;
+    if (p.ld.n_tiles <= kLdSmallTiles) VS_TRY(launch_prune_hits<(int)kLdSmallTiles>(idx, p, (unsigned)blocks, lds));
+    else VS_TRY(launch_prune_hits<(int)kLdMaxTiles>(idx, p, (unsigned)blocks, lds));
+    hipLaunchKernelGGL(k_clump_class, dim3((unsigned)std::min<uint64_t>((d.A + kClumpBuildThreads - 1) / kClumpBuildThreads, 1u << 20)), dim3(kClumpBuildThreads), 0,
+                       idx->stream, g);
+    HIP_TRY(hipGetLastError());
+  }
+  if (g.states) {
+    const uint64_t blocks = (g.states * 2 * words + kClumpBuildThreads - 1) / kClumpBuildThreads;
+    if (blocks > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu blocks of verdict words)", (unsigned long long)blocks);
+    hipLaunchKernelGGL(k_clump_blockers, dim3((unsigned)blocks), dim3(kClumpBuildThreads), 0, idx->stream, g);
+    HIP_TRY(hipGetLastError());
+  }
+  if (d.Q > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu regions)", (unsigned long long)d.Q);
+  hipLaunchKernelGGL(k_clump_rounds, dim3((unsigned)d.Q), dim3(kClumpThreads), 0, idx->stream, g);
   HIP_TRY(hipGetLastError());
   return VS_OK;
 }
@@ -3946,6 +4078,7 @@ void vs_result_free(vs_result* r) {
     pin_release(r->idx, r->raw_pin);
     pin_release(r->idx, r->counts_pin);
     pin_release(r->idx, r->cells_pin);
+    pin_release(r->idx, r->owner_pin);
     for (auto& b : r->old_pins) pin_release(r->idx, b);
     r->idx->live_results--;
     if (r->idx->close_pending && r->idx->live_results == 0 && r->idx->live_comms == 0) vs_index_close(r->idx);
@@ -4390,6 +4523,53 @@ int vs_query_ld_prune(vs_index* idx, const vs_region* regions, uint64_t n, const
   });
 }
 
+// The key of a p-value in [0, 1]: the bit pattern of the non-negative double (-0.0 counts as 0), monotone in p.  False outside
+// [0, 1] and for a NaN.
+static bool clump_key(double p, uint64_t* key) {
+  if (!(p >= 0.0 && p <= 1.0)) return false;
+  memcpy(key, &p, 8);
+  *key &= ~(1ull << 63);   // (-0.0)
+  return true;
+}
+
+int vs_query_ld_clump(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, const double* pvalues, uint64_t n_pvalues,
+                      uint32_t window, uint32_t max_bp, uint32_t threshold_q20, double p1, double p2, vs_result** out) {
+  VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "an LD-clumping"));
+  if (window == 0 || window > kLdMaxWindow) return fail(VS_ERR_ARG, "an LD-clumping window of %u rows (1 .. %u)", window, kLdMaxWindow);
+  if (threshold_q20 > kPruneThresholdOne)
+    return fail(VS_ERR_ARG, "an LD-clumping threshold of %u / 2^20 (0 .. %u: r2 between 0 and 1)", threshold_q20, kPruneThresholdOne);
+  if (!pvalues) return fail(VS_ERR_ARG, "null argument: a clumping batch takes a p-value per table row (pvalues)");
+  uint64_t key1 = 0, key2 = 0;
+  if (!clump_key(p1, &key1)) return fail(VS_ERR_ARG, "an index p-value bound p1 of %g (0 .. 1)", p1);
+  if (!clump_key(p2, &key2)) return fail(VS_ERR_ARG, "a clump p-value bound p2 of %g (0 .. 1)", p2);
+  if (key1 > key2) return fail(VS_ERR_ARG, "p1 = %g above p2 = %g: the bound of the index rows may not exceed the bound of the clumped rows", p1, p2);
+  std::vector<uint64_t> keys((size_t)n_pvalues);
+  for (uint64_t i = 0; i < n_pvalues; ++i) {
+    const double p = pvalues[i];
+    if (p != p) keys[i] = kClumpNoKey;
+    else if (!clump_key(p, &keys[i])) return fail(VS_ERR_ARG, "the p-value of table row %llu is %g: a p-value lies in 0 .. 1 (NaN: none)", (unsigned long long)i, p);
+  }
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));
+  if (cols.size() >= (1ull << 21))
+    return fail(VS_ERR_UNSUPPORTED, "an LD clumping over %llu columns: the exact comparison takes fewer than 2^21", (unsigned long long)cols.size());
+  if (mask.size() * 8 > kMatrixMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", idx->g.num_samples);
+  SharedReq req = column_request(ReqKind::Clump, mask, rank, cols.size());
+  req.ld_window = window;
+  req.prune_max_bp = max_bp; req.prune_T = threshold_q20;
+  req.n_pvalues = n_pvalues; req.clump_key[0] = key1; req.clump_key[1] = key2;
+  return make_result(idx, kKindClump, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    r->h_clump_keys = std::move(keys);
+    r->clump_key[0] = key1; r->clump_key[1] = key2;
+    memcpy(r->clump_p, r->clump_key, 16);
+    req.clump_keys = r->h_clump_keys.data();
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
 int vs_query_sample_gram(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t stat, vs_result** out) {
   VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "a Gram"));
   if (stat != VS_GRAM_DOT && stat != VS_GRAM_GRM) return fail(VS_ERR_ARG, "Gram statistic %u is neither VS_GRAM_DOT nor VS_GRAM_GRM", stat);
@@ -4567,7 +4747,8 @@ static int ld_block_begin_to_host(vs_result* r) {
 static int prune_meta_to_host(vs_result* r) {
   if (!r->h_prune_meta.empty()) return VS_OK;
   VS_TRY(result_ready(r));
-  VS_TRY(fetch(r->idx, r->h_prune_meta, (const uint64_t*)r->d_prune_meta, 2 * ((size_t)r->d.Q + 1)));
+  // (a clumping result: n_index in n_kept's place, and behind the scan's summary and the cell total the rounds of every region)
+  VS_TRY(fetch(r->idx, r->h_prune_meta, (const uint64_t*)r->d_prune_meta, r->kind == kKindClump ? 3 * ((size_t)r->d.Q + 1) + 4 : 2 * ((size_t)r->d.Q + 1)));
   HIP_TRY(hipStreamSynchronize(r->idx->stream));
   return VS_OK;
 }
@@ -4765,7 +4946,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
         for (uint64_t a = r->h_var_begin[q] * G, e = a + r->h_nvar[q] * G; a < e; ++a) nc += c[a].x;
       r->n_carriers_kept = nc;
     }
-    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindPrune || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
+    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindPrune || r->kind == kKindClump || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
       VS_TRY(result_ready(r));
       uint64_t nc = 0;
       HIP_TRY(hipMemcpyAsync(&nc, r->d_cell_total, 8, hipMemcpyDeviceToHost, idx->stream));
@@ -4951,6 +5132,58 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
       out += std::to_string(cnt[a - a0].y);
       const uint8_t verdict = st[a - a0];
       out += verdict == kPruneKept ? "\tkeep\n" : verdict == kPrunePruned ? "\tpruned\n" : "\tskip\n";
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
+  if (r->kind == kKindClump) {   // the region's reported rows with their p-values, verdicts and index rows
+    const VariantRow* rows;
+    if (r->have_headers) rows = r->h_rows.data() + a0;
+    else if (r->raw_rows) rows = r->raw_rows + a0;
+    else {
+      VS_TRY(fetch(idx, r->sl_rows, (const VariantRow*)r->d.rows + a0, (size_t)(a1 - a0)));
+      rows = r->sl_rows.data();
+    }
+    VS_TRY(array_to_host(r, r->d_state, (size_t)r->prune_states, &r->cells_pin, "clumping verdicts"));
+    VS_TRY(array_to_host(r, r->d_owner, (size_t)r->prune_states * 4, &r->owner_pin, "clump owners"));
+    VS_TRY(counts_to_host(r));
+    VS_TRY(prune_meta_to_host(r));
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    const uint8_t* st = (const uint8_t*)r->cells_pin.p + r->h_prune_meta[q];
+    const uint32_t* own = (const uint32_t*)r->owner_pin.p + r->h_prune_meta[q];
+    const uint4* cnt = (const uint4*)r->counts_pin.p + a0;
+    const auto name = [&](std::string& out, const VariantRow& v, char sep) {
+      out += std::to_string(v.pos);
+      out += sep;
+      out.append(idx->seq_chars, v.ref_off, v.ref_len);
+      out += sep;
+      out.append(idx->seq_chars, v.alt_off, v.alt_len);
+    };
+    std::string& out = r->text;
+    out = "Pos\tRef\tAlt\tAC\tP\tState\tIndex\n";
+    char num[40];
+    for (uint64_t a = a0; a < a1; ++a) {
+      const VariantRow& v = rows[a - a0];
+      if (v.count_flags & kRowDropped) continue;
+      name(out, v, '\t');
+      out += '\t';
+      out += std::to_string(cnt[a - a0].y);
+      out += '\t';
+      const uint64_t key = r->h_clump_keys[a];
+      if (key == kClumpNoKey) out += '.';
+      else {
+        double p;
+        memcpy(&p, &key, 8);
+        snprintf(num, sizeof num, "%.6g", p);
+        out += num;
+      }
+      const uint8_t verdict = st[a - a0];
+      out += verdict == kClumpIndex ? "\tindex\t" : verdict == kClumpMember ? "\tclumped\t" : verdict == kClumpUnclumped ? "\tunclumped\t" : "\tskip\t";
+      const uint32_t o = own[a - a0];
+      if (o == kClumpNoOwner || o >= a1 - a0) out += '.';
+      else name(out, rows[o], ':');
+      out += '\n';
     }
     *text = out.c_str();
     if (len) *len = out.size();
@@ -5471,6 +5704,46 @@ int vs_result_ld_prune_device(vs_result* r, uint64_t* n_regions, uint64_t* n_row
   if (dev_counts) *dev_counts = r->d_counts;
   if (dev_keep_begin) *dev_keep_begin = r->d_prune_meta;
   if (dev_n_kept) *dev_n_kept = r->d_prune_meta + (r->d.Q + 1);
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  return VS_OK;
+}
+
+int vs_result_get_ld_clump(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint32_t* params, uint64_t* p_keys, double* p_bounds,
+                           const uint32_t** col_ids, const vs_allele_counts** counts, const uint64_t** keep_begin, const uint64_t** n_index, const uint64_t** rounds,
+                           const uint8_t** state, const uint32_t** owner) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!state || !owner) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindClump) return fail(VS_ERR_ARG, "not a clumping result (vs_query_ld_clump)");
+  VS_TRY(array_to_host(r, r->d_state, (size_t)r->prune_states, &r->cells_pin, "clumping verdicts"));
+  VS_TRY(array_to_host(r, r->d_owner, (size_t)r->prune_states * 4, &r->owner_pin, "clump owners"));
+  VS_TRY(counts_to_host(r));
+  VS_TRY(prune_meta_to_host(r));
+  *state = (const uint8_t*)r->cells_pin.p;
+  *owner = (const uint32_t*)r->owner_pin.p;
+  if (counts) *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (keep_begin) *keep_begin = r->h_prune_meta.data();
+  if (n_index) *n_index = r->h_prune_meta.data() + (r->d.Q + 1);
+  if (rounds) *rounds = r->h_prune_meta.data() + 2 * (r->d.Q + 1) + 4;
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (params) { params[0] = r->ld_window; params[1] = r->prune_max_bp; params[2] = r->prune_T; }
+  if (p_keys) { p_keys[0] = r->clump_key[0]; p_keys[1] = r->clump_key[1]; }
+  if (p_bounds) { p_bounds[0] = r->clump_p[0]; p_bounds[1] = r->clump_p[1]; }
+  if (col_ids) *col_ids = r->h_cols.data();
+  return VS_OK;
+}
+
+int vs_result_ld_clump_device(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, const void** dev_counts, const void** dev_keep_begin,
+                              const void** dev_n_index, const void** dev_state, const void** dev_owner) {
+  VS_TRY(device_matrix_ready(r, dev_state, kKindClump, "not a clumping result (vs_query_ld_clump)"));
+  *dev_state = r->d_state;
+  if (dev_owner) *dev_owner = r->d_owner;
+  if (dev_counts) *dev_counts = r->d_counts;
+  if (dev_keep_begin) *dev_keep_begin = r->d_prune_meta;
+  if (dev_n_index) *dev_n_index = r->d_prune_meta + (r->d.Q + 1);
   if (n_regions) *n_regions = r->d.Q;
   if (n_rows) *n_rows = r->d.A;
   if (n_cols) *n_cols = r->h_cols.size();

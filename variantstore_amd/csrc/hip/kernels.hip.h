@@ -81,6 +81,12 @@
 //  k_prune_greedy        the scan of the regions' row counts, and the walk: a wave per region, a 256-bit wave-uniform register of
 //                       blocked rows, the masks of 64 rows loaded ahead and taken with v_readlane, a state byte per row
 //                       (vs_query_ld_prune: no reference counterpart)
+// k_clump_class         p-value clumping of every region over k_prune_hits' masks: the greedy in priority order -- (key of the
+//  k_clump_blockers      p-value, table row) ascending, unsigned integers only -- decided in parallel rounds.  A class per table row,
+//  k_clump_rounds        per verdict slot the mask of the hitting rows that outrank it (both directions of the window), then one
+//                       workgroup per region: a row is a member once a blocker is an index, an index once every blocker is
+//                       decided and none is; in-place updates, no host wait between rounds; owners and n_index in a last pass
+//                       (vs_query_ld_clump: no reference counterpart)
 // k_assoc_matrix        D Y over the same dosages: table rows x K traits (K up to 65,536) given as four int8 limbs of a fixed-point
 //                       value, 64 rows x 16 traits per workgroup, k_ld_band's staging and fragments, four MFMAs per 64-column step,
 //                       the limb sums combined in int64: exact dot products or the score test from 128-bit integers
@@ -120,6 +126,7 @@
 #include "k_ld.hip.h"
 #include "k_ld_block.hip.h"
 #include "k_prune.hip.h"
+#include "k_clump.hip.h"
 #include "k_int128.hip.h"
 #include "k_gram.hip.h"
 #include "k_assoc_matrix.hip.h"
