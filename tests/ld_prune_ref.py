@@ -34,23 +34,50 @@ def row_counts(cells):
     return d.sum(axis=1), (d == 2).sum(axis=1)
 
 
-def hit_band(cells, window, T):
-    """bool (rows, window): [i, k] = hit(i, i + 1 + k), False past the last row.  The sums in int64, the comparison in Python
-    integers (object arrays): exact."""
+def _band_sides(cells, window, T):
+    """For k = 0 .. window - 1: (k, m, cov^2 2^20, T v_i v_j, v_i > 0 and v_j > 0) of the pairs (i, i + 1 + k), i < m.  The sums in
+    int64 (exact: |cov|, v <= 4 n^2 < 2^63 for every n the engine admits), the two sides in Python integers from n = 800 on."""
     d = dosage(cells)
     a, n = d.shape
     ac, hom = row_counts(cells)
     # |cov|, v <= 4 n^2: below n = 800 both sides of the comparison stay under 2^20 * 16 n^4 < 2^63 and int64 is exact as well
     wide = np.int64 if n < 800 else object
     v = (np.int64(n) * (ac + 2 * hom) - ac * ac).astype(wide)
-    out = np.zeros((a, window), bool)
+    d8 = d.astype(np.int8)   # (the products of the dosages, summed in int64: the same integers from an eighth of the memory)
     for k in range(min(window, max(a - 1, 0))):
         m = a - 1 - k
-        sxy = (d[:m] * d[1 + k:]).sum(axis=1)
+        sxy = np.einsum("ij,ij->i", d8[:m], d8[1 + k:], dtype=np.int64)
         cov = (np.int64(n) * sxy - ac[:m] * ac[1 + k:]).astype(wide)
         vi, vj = v[:m], v[1 + k:]
-        big = (cov * cov * ONE) > (vi * vj * int(T))
-        out[:m, k] = np.asarray(big, bool) & np.asarray(vi > 0, bool) & np.asarray(vj > 0, bool)
+        yield k, m, cov * cov * ONE, vi * vj * int(T), np.asarray(vi > 0, bool) & np.asarray(vj > 0, bool)
+
+
+def hit_band(cells, window, T):
+    """bool (rows, window): [i, k] = hit(i, i + 1 + k), False past the last row.  The sums in int64, the comparison in Python
+    integers (object arrays): exact."""
+    out = np.zeros((np.asarray(cells).shape[0], window), bool)
+    for k, m, lhs, rhs, live in _band_sides(cells, window, T):
+        out[:m, k] = np.asarray(lhs > rhs, bool) & live
+    return out
+
+
+def side_band(cells, window, T):
+    """(lhs, rhs), object (rows, window): the two sides cov^2 2^20 and T v_i v_j of hit_band's comparison as Python integers, 0
+    past the last row -- for the conditions the tests put on their inputs (how many bits a pair needs, whether it is a tie)."""
+    a = np.asarray(cells).shape[0]
+    lhs, rhs = np.zeros((a, window), object), np.zeros((a, window), object)
+    for k, m, left, right, _live in _band_sides(cells, window, T):
+        lhs[:m, k], rhs[:m, k] = left.astype(object), right.astype(object)
+    return lhs, rhs
+
+
+def hit_band_wrapped64(cells, window, T):
+    """hit_band with both sides of the comparison reduced mod 2^64 before they are compared: what a kernel that multiplied in
+    64-bit integers would give.  NEVER an expected value: it only states that an input can tell such a kernel from the exact one."""
+    out = np.zeros((np.asarray(cells).shape[0], window), bool)
+    mask = (1 << 64) - 1
+    for k, m, lhs, rhs, live in _band_sides(cells, window, T):
+        out[:m, k] = np.asarray((lhs.astype(object) & mask) > (rhs.astype(object) & mask), bool) & live
     return out
 
 
@@ -121,13 +148,18 @@ def prune_text(heads, ac, state):
 BASES = "ACGT"
 
 
-def write_ld_block_cohort(dirpath, seed, n_sites=300, n_samples=40, ref_len=6000):
+def write_ld_block_cohort(dirpath, seed, n_sites=300, n_samples=40, ref_len=6000, p_two_alt=0.06):
     """FASTA + VCF of an "LD-block" cohort: runs of 2 .. 9 sites that are near-copies of one base genotype pattern -- a third of
-    them exact copies, the others with one to four flipped calls --, about a tenth of the calls unphased and a few two-ALT records.
-    Sites are 4 .. 24 bases apart.  Returns (fasta, vcf, names, the last site's position)."""
+    them exact copies, the others with one to four flipped calls --, about a tenth of the calls unphased and a few two-ALT records
+    (a share p_two_alt of the sites: the draw is made whatever it is, so the default writes the bytes it always wrote, and with 0
+    every record is a single-ALT SNP that vcf_truth.TextOracle predicts).  Sites are 4 .. 24 bases apart.  The sample names are
+    zero-padded to the width of the largest (three digits up to 999 samples, as ever), so the columns are in name order at every
+    width: where they are not, the reference permutes the genotype strings among a site's carriers and the VCF
+    text alone no longer says what a row holds.  Returns (fasta, vcf, names, the last site's position)."""
     rng = np.random.default_rng(seed)
     ref = "".join(BASES[i] for i in rng.integers(0, 4, size=ref_len))
-    names = [f"B{i + 1:03d}" for i in range(n_samples)]
+    digits = max(3, len(str(n_samples)))
+    names = [f"B{i + 1:0{digits}d}" for i in range(n_samples)]
     fasta, vcf = os.path.join(dirpath, f"ldblock{seed}.fa"), os.path.join(dirpath, f"ldblock{seed}.vcf")
     with open(fasta, "w") as f:
         f.write(">c1 ldblock\n")
@@ -149,7 +181,7 @@ def write_ld_block_cohort(dirpath, seed, n_sites=300, n_samples=40, ref_len=6000
             r0 = ref[p - 1]
             others = [b for b in BASES if b != r0]
             alt = others[int(rng.integers(0, 3))]
-            two = rng.random() < 0.06
+            two = rng.random() < p_two_alt
             if two:
                 alt += "," + [b for b in others if b != alt][0]
                 g = np.where((g == 1) & (rng.random(g.shape) < 0.3), 2, g)
@@ -160,3 +192,61 @@ def write_ld_block_cohort(dirpath, seed, n_sites=300, n_samples=40, ref_len=6000
         f.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join(names) + "\n")
         f.write("".join(lines))
     return fasta, vcf, names, p
+
+
+# Pairs of short dosage patterns whose r^2 is the fraction (num, den) exactly, found by brute force over patterns of length 4 and 6.
+# Repeating a pattern c times multiplies cov, v_i and v_j by c^2 each, so cov^2 2^20 == T v_i v_j holds for T = 2^20 num / den at
+# every number of columns that is a multiple of the pattern's length.
+TIE_PAIRS = (
+    ((1, 16), (0, 0, 0, 0, 1, 1), (0, 0, 0, 1, 0, 1)),
+    ((1, 8), (0, 0, 1, 1, 2, 2), (0, 1, 1, 2, 1, 1)),
+    ((3, 16), (0, 0, 0, 0, 1, 1), (0, 0, 1, 2, 1, 2)),
+    ((1, 4), (0, 1, 1, 2), (0, 1, 2, 1)),
+    ((3, 8), (0, 0, 0, 0, 1, 1), (0, 1, 1, 1, 1, 2)),
+    ((1, 2), (0, 0, 1, 1), (0, 1, 1, 2)),
+    ((9, 16), (0, 0, 1, 1, 2, 2), (0, 0, 1, 2, 1, 2)),
+    ((5, 8), (0, 0, 0, 0, 1, 1), (0, 0, 0, 1, 1, 2)),
+    ((3, 4), (0, 0, 0, 0, 1, 1), (0, 0, 1, 1, 2, 2)),
+    ((1, 1), (0, 1, 1, 2), (2, 1, 1, 0)),   # cov < 0
+    ((1, 1), (0, 1, 1, 2), (0, 1, 1, 2)),   # cov > 0
+)
+TIE_REF_LEN = 2400
+
+
+def tie_threshold(fraction):
+    """T = 2^20 num / den of a TIE_PAIRS fraction, an integer."""
+    num, den = fraction
+    assert (ONE * num) % den == 0
+    return ONE * num // den
+
+
+def write_tie_cohort(dirpath, n_samples, seed):
+    """FASTA + VCF (tie.fa, tie.vcf) of the TIE_PAIRS: rows 2 k and 2 k + 1 are pair k, single-ALT SNPs 100 bases apart, each
+    pattern repeated across the n_samples columns (a multiple of 12), then ONE seeded permutation of the columns applied to every
+    row, which leaves every moment as it was.  Dosage 1 is written as 0|1 or 1|0, 2 as 1|1.  Returns (fasta, vcf, names (sorted: the
+    column order is the engine's id order), pos int64 [22], the fractions [11], the dosage matrix written uint8 (22, n_samples),
+    source int64 [n_samples]: the position column c had before the permutation -- the columns with source < m, m a multiple of
+    12, are m columns of whole patterns again)."""
+    assert n_samples % 12 == 0
+    rng = np.random.default_rng(seed)
+    ref = "".join(BASES[i] for i in rng.integers(0, 4, size=TIE_REF_LEN))
+    names = [f"T{i + 1:06d}" for i in range(n_samples)]
+    source = rng.permutation(n_samples).astype(np.int64)
+    rows = [np.tile(np.asarray(pat, np.uint8), n_samples // len(pat)) for _f, x, y in TIE_PAIRS for pat in (x, y)]
+    d = np.stack(rows)[:, source]
+    pos = 100 + 100 * np.arange(d.shape[0], dtype=np.int64)
+    fasta, vcf = os.path.join(dirpath, "tie.fa"), os.path.join(dirpath, "tie.vcf")
+    with open(fasta, "w") as f:
+        f.write(">c1 ties\n")
+        for i in range(0, TIE_REF_LEN, 60):
+            f.write(ref[i:i + 60] + "\n")
+    calls = np.array(["0|0", "0|1", "1|1", "1|0"])
+    with open(vcf, "w") as f:
+        f.write("##fileformat=VCFv4.1\n##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n")
+        f.write("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join(names) + "\n")
+        for i, p in enumerate(pos):
+            r0 = ref[int(p) - 1]
+            alt = [b for b in BASES if b != r0][int(rng.integers(0, 3))]
+            which = np.where((d[i] == 1) & (rng.random(n_samples) < 0.5), 3, d[i])
+            f.write(f"c1\t{int(p)}\t.\t{r0}\t{alt}\t99\t.\t.\tGT\t" + "\t".join(calls[which]) + "\n")
+    return fasta, vcf, names, pos, [f for f, _x, _y in TIE_PAIRS], d, source
