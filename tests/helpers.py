@@ -79,7 +79,7 @@ def write_random_cohort(dirpath, seed, ref_len=4000, n_rows=120, n_samples=6, sa
 SAT_REF_LEN = 20_000
 
 
-def write_saturated_cohort(dirpath, n_samples, seed, rows=150, two_alt=True, extremes=False):
+def write_saturated_cohort(dirpath, n_samples, seed, rows=150, two_alt=True, extremes=False, sparse_head=0):
     """FASTA + VCF (sat.fa, sat.vcf) of `rows` rows 120 - 129 bases apart (SNPs, 6 % insertions, 6 % deletions, 3 % two-ALT rows, a
     tenth of the carriers' calls moved on to 1|1, 1/0 or 1/1): row k is carried by all but k / 8 % 6 samples when k % 8 == 0 (rows 0,
     48, 96, 144: by every sample), else by a share of the samples drawn from [0.75, 0.99]; rows 4, 20, 36, ... keep only their
@@ -89,8 +89,16 @@ def write_saturated_cohort(dirpath, n_samples, seed, rows=150, two_alt=True, ext
     The options draw no random number, so the defaults and the rows they leave alone are the same bytes whatever they are:
       two_alt=False   the two-ALT records are written as SNPs of their first ALT
       extremes=True   the calls of rows 1..6 (single-ALT then) are overwritten: everybody 1/1, 1|1, 0|1, 1/0; everybody a carrier
-                      but sample 1; everybody but the last sample."""
+                      but sample 1; everybody but the last sample.
+      sparse_head=H   the calls of records 0..H-1 are thinned to max(1, n_samples // 50) carriers each, chosen by a generator of the
+                      option's own (seeded from `seed`): a kept sample keeps its call, everybody else becomes 0|0, and if every kept
+                      call is 0|0 one of them becomes 0|1.  Records H.. are untouched.  With H >= 100 the constructor, which looks
+                      at the carrier density of the first 99 records, opens the cohort with EXPLICIT sample ids -- and then meets
+                      carrier lists as long as the cohort.  extremes=True concerns rows 1..6, so it makes no sense together with
+                      sparse_head > 6 (asserted)."""
+    assert not (extremes and sparse_head > 6), "extremes rewrites rows 1..6, which sparse_head > 6 would thin again"
     rng = np.random.default_rng(seed)
+    thin = np.random.default_rng([int(seed), 0x5EAD]) if sparse_head else None   # (never the writer's generator: the defaults' bytes stay)
     ref = "".join(BASES[i] for i in rng.integers(0, 4, size=SAT_REF_LEN))
     names = [f"S{i + 1:05d}" for i in range(n_samples)]
     one_alt = np.array(["0|0", "1|0", "0|1", "1|1", "1/0", "1/1"])
@@ -130,6 +138,13 @@ def write_saturated_cohort(dirpath, n_samples, seed, rows=150, two_alt=True, ext
             elif extremes and k in (5, 6):
                 call = np.where(call == 0, 1 + np.arange(n_samples) % 5, call)
                 call[0 if k == 5 else n_samples - 1] = 0
+            if k < sparse_head:
+                kept = thin.choice(n_samples, size=max(1, n_samples // 50), replace=False)
+                thinned = np.zeros_like(call)
+                thinned[kept] = call[kept]
+                if not thinned.any():
+                    thinned[kept[0]] = 2                               # 0|1
+                call = thinned
             f.write(f"c1\t{p}\t.\t{refa}\t{alt}\t99\t.\t.\tGT\t" + "\t".join(calls[call]) + "\n")
     return fasta, vcf
 

@@ -7,6 +7,10 @@ Two legs per (cohort width, VS_LIST_MAX):
   text     two_alt=False, extremes=True against vcf_truth.TextOracle: the expected answer comes from the VCF TEXT alone, no
            constructor and no graph in the loop (tests/test_vcf_truth.py holds TextOracle to the oracle on the CPU)
   oracle   two_alt=True, extremes=True against the oracle, for the two-ALT rows the text does not fix (64, 4095, 4159 samples)
+and a third at 63, 300 and 4159 samples with VS_LIST_MAX unset:
+  explicit two_alt=False, sparse_head=100 against vcf_truth.TextOracle: the cohort opens with EXPLICIT sample ids (the constructor
+           looks at the first 99 records) and its records from 100 on are carried by 70 - 100 % of the samples -- the explicit side
+           of k_carriers.hip.h on lists hundreds of groups long.  No extreme rows: the checks that read them are left out.
 
 Widths (samples -> words per class row): 63 -> 1 (one full word, the ref bit included), 64 -> 2 (one bit in the second),
 4031 -> 63 (the widest non-WIDE row, its last word full), 4095 -> 64 (the 64-word form, full), 4159 -> 65 (a second round of the
@@ -50,6 +54,10 @@ VS_ERR_UNSUPPORTED = -7
 ROWS = {63: 150, 64: 150, 4031: 150, 4095: 150, 4159: 150, 8255: 70}   # (never below 65: one wave's rows plus one)
 CELLS = [(n, lm, leg) for n in ROWS for lm in ((None, 0, 64) if n in (4031, 4095, 4159) else (None, 0))
          for leg in (("text", "oracle") if n in (64, 4095, 4159) else ("text",))]
+# dense EXPLICIT-ID cohorts (sparse_head=100: the constructor chooses explicit sample ids from the first 99 records, the records from
+# 100 on are carried by 70 - 100 % of the samples): the explicit side of k_carriers.hip.h on lists hundreds of groups long, with
+# 16-bit (63, 300) and 32-bit (4159) carrier words
+CELLS += [(n, None, "explicit") for n in (63, 300, 4159)]
 
 
 def _open_with_list_max(fasta, vcf, list_max):
@@ -70,19 +78,21 @@ class _Cohort:
     oracle), the two batches, and the parsed expected texts every family's checker takes, each parsed at first use."""
 
     def __init__(self, n, list_max, leg, tmp, rows=None):
-        self.n, self.leg, self.rows = n, leg, ROWS[n] if rows is None else rows
-        fasta, vcf = write_saturated_cohort(str(tmp), n, 4400 + n, rows=self.rows, two_alt=leg == "oracle", extremes=True)
+        self.n, self.leg, self.rows = n, leg, ROWS.get(n, 150) if rows is None else rows
+        kw = dict(sparse_head=100, extremes=False) if leg == "explicit" else dict(extremes=True)
+        fasta, vcf = write_saturated_cohort(str(tmp), n, 4400 + n, rows=self.rows, two_alt=leg == "oracle", **kw)
         self.vs = _open_with_list_max(fasta, vcf, list_max)
         info = self.vs.info()
         self.list_max = 640 if list_max is None else list_max
         self.wpc = (n + 1 + 63) // 64
-        assert info.num_samples - 1 == n and info.use_bit_vector and info.list_max == self.list_max
+        assert info.num_samples - 1 == n and bool(info.use_bit_vector) == (leg != "explicit")
+        assert info.list_max == self.list_max or leg == "explicit"
         assert (info.num_samples + 63) // 64 == self.wpc and info.ref_length == SAT_REF_LEN
         self.names, self.recs = vt.read_vcf(vcf)
         assert self.names == sorted(self.names) and len(self.recs) == self.rows
         assert self.vs.sample_name(1) == self.names[0] and self.vs.sample_name(n) == self.names[-1]
         self.ids_of = {nm: i + 1 for i, nm in enumerate(self.names)}
-        if leg == "text":
+        if leg in ("text", "explicit"):
             self.orc = vt.TextOracle(vcf)
             assert len(self.orc.rows) == self.rows                 # the text leg leaves out no row
         else:
@@ -107,6 +117,10 @@ class _Cohort:
         n = self.n
         car = np.array([[g not in ("0|0", "0/0") for g in r[3]] for r in self.recs])
         self.carriers = car.sum(axis=1)
+        if self.leg == "explicit":    # (no extreme rows: the head is sparse, the tail dense, record 144 is carried by everybody)
+            assert self.carriers[:100].max() <= max(1, n // 50) and self.carriers[144] == n
+            assert (self.carriers[100:] >= (0.7 * n if n <= 2015 else 1500)).all()
+            return
         assert (self.carriers == n).sum() >= 2, "fewer than two rows carried by every sample"
         for k, call in ((1, "1/1"), (2, "1|1"), (3, "0|1"), (4, "1/0")):
             assert len(self.recs[k][2]) == 1 and set(self.recs[k][3]) == {call}, k
@@ -254,6 +268,9 @@ def test_sample_burden(cohort):
         below = _check_burden(c.vs, regions, parsed, valid, None, 0, 2 * n - 1)
         only = _check_burden(c.vs, regions, parsed, valid, None, 2 * n)
         assert np.array_equal(below + only, full)
+        if c.leg == "explicit":      # (no row everybody is hom-alt on)
+            assert not only.any()
+            continue
         q = regions.index(c.whole)
         assert (only[q] == [2, 4, 2, 1]).all(), "the whole reference: the all-1/1 and the all-1|1 row, for every sample"
         m = len(c.subset)
@@ -339,6 +356,8 @@ def test_sample_gram(cohort):
     got = _check_gram(c, regions, parsed, sub, ("dot", "grm"))
     assert got["H"] > 0 and got["grm"].any()
     _check_gram(c, c.batch["shuffled"], c.mparsed("shuffled"), c.subset, ("grm",))
+    if c.leg == "explicit":
+        return
     # only the rows everybody is 1/1 and 1|1 on: no variance anywhere, H = 0 and every GRM cell 0.0
     e = c.edges
     flat = [(e[1], e[2]), (e[2], e[3]), (e[1], e[3])]
