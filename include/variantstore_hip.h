@@ -664,6 +664,56 @@ int vs_result_get_ld_clump(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, 
  * this returns: the caller needs no event. */
 int vs_result_ld_clump_device(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, const void** dev_counts,
                               const void** dev_keep_begin, const void** dev_n_index, const void** dev_state, const void** dev_owner);
+/* LD scores over regions: for every table row of every region the sum of r2 with the rows of the same region within a distance of
+ * it -- the input of LD-score regression, of LDAK-style variant weights and of LD-aware annotation --, reduced on the device from
+ * the products an LD matrix is formed from, without the matrix: the window has no 256-row ceiling (no reference counterpart).  The
+ * table T, its A rows, row_begin / row_count, the column set S with n columns, the count records, v_i and cov are those of
+ * vs_query_ld_prune over the same regions and ids.  All arithmetic is integer: no floating-point value decides or is summed.
+ * Region q owns the table rows row_begin[q] + a, a < m_q = row_count[q], and the slots keep_begin[q] + a, keep_begin exactly
+ * vs_query_ld_prune's scan of the row counts; overlapping regions each get their own slots, regions are independent.
+ * Eligible: as for vs_query_ld_prune -- the duplicate rule did not drop the row, v = n Sxx - Sx^2 > 0 and min_ac <= alt_alleles <=
+ * max_ac.
+ * Per pair: for an eligible pair (a, b), q32(a, b) = floor(cov^2 2^32 / (v_a v_b)); 0 .. 2^32 by Cauchy-Schwarz, exactly 2^32 for
+ * a = b.
+ * Sum: for an eligible row a, sums[slot] = the sum of q32(a, b) over all eligible b of the same region, b = a INCLUDED (the LDSC
+ * convention), with |a - b| <= window in table rows (window = 0: no row limit) and, if max_bp is nonzero, |pos_a - pos_b| <=
+ * max_bp.  n_pairs[slot] = the number of b summed, self included.  Ineligible and dropped rows: sums = 0, n_pairs = 0.
+ * State: a byte per slot, VS_LDSCORE_SCORED, VS_LDSCORE_INELIGIBLE or VS_LDSCORE_DROPPED; n_scored[q] counts the scored rows.
+ * The score is sums / 2^32.  With n < 2^21: cov^2 2^32 < 2^120 and q v_a v_b < 2^121; a column set of 2^21 or more is refused with
+ * VS_ERR_UNSUPPORTED.  The sums are added with integer atomics: the same call gives the same bytes.
+ * Checked on the host, in this order, before the handle's device is asked for (a handle opened without a device reports them first
+ * and VS_ERR_NO_DEVICE otherwise): n == 0, sample_ids == NULL with n_ids != 0, non-NULL sample_ids with n_ids == 0 -> VS_ERR_ARG;
+ * min_ac > max_ac -> VS_ERR_ARG; id 0 or id >= num_samples -> VS_ERR_UNKNOWN_SAMPLE; 2^21 columns or more -> VS_ERR_UNSUPPORTED.
+ * The sums are formed from a temporary genotype matrix, which leaves the result as an LD batch's matrix does; the matrix, 13 bytes
+ * per slot (8 of the sum, 4 of the pair count, 1 of the state) and the per-region arrays together may not exceed option
+ * "matrix_max_mib" MiB (default 32 GiB): beyond it the call is refused with VS_ERR_ARG before anything is allocated for them; the
+ * message names rows, columns and bytes.  The number of slots is known on the device only: the call may wait once for a small scan
+ * over the per-region row counts, in front of the kernels vs_result_fill_ms times.  More than 2^31 - 1 workgroups (a region of t
+ * tiles of 64 rows takes t (B + 1), B = the tile distances the window reaches) are refused with VS_ERR_ARG.  The batch is never
+ * speculative and leaves the handle's type-6 state as it was.  vs_result_get_raw / vs_result_get_view with with_carriers = 0,
+ * vs_result_layout, vs_result_totals and vs_result_fill_ms work as for a pruning result; vs_result_format_region gives
+ * "Pos\tRef\tAlt\tAC\tPairs\tL2\tState\n", then one line per reported, non-dropped row of the region: L2 = sums / 2^32 as %.6f,
+ * State one of scored, skip.  What a pruning result refuses this result refuses with the same codes; the other results' getters
+ * refuse it, and its getters refuse the others, with VS_ERR_ARG. */
+#define VS_LDSCORE_SCORED 1u
+#define VS_LDSCORE_INELIGIBLE 2u
+#define VS_LDSCORE_DROPPED 3u
+#define VS_LDSCORE_ONE (1ull << 32)
+int vs_query_ld_scores(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t window, uint32_t max_bp,
+                       uint32_t min_ac, uint32_t max_ac, vs_result** out);
+/* The scores of an LD-score result copied into page-locked memory owned by the result: sums (uint64), n_pairs (uint32) and state
+ * (uint8), keep_begin[n_regions] of each, keep_begin[n_regions + 1], n_scored[n_regions], counts[i] the count record of table row i
+ * over S, col_ids[c] the sample id of column c, and params[4] = {window, max_bp, min_ac, max_ac}.  Every out-pointer but `sums` may
+ * be NULL.  VS_ERR_ARG on any other result. */
+int vs_result_get_ld_scores(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint32_t* params, const uint32_t** col_ids,
+                            const vs_allele_counts** counts, const uint64_t** keep_begin, const uint64_t** n_scored, const uint64_t** sums,
+                            const uint32_t** n_pairs, const uint8_t** state);
+/* Sums (n_slots uint64), n_pairs (n_slots uint32), state (n_slots bytes), keep_begin (n_regions + 1 uint64), n_scored (n_regions
+ * uint64) and counts (n_rows records of 16 bytes) as they lie in HBM, valid until vs_result_free; n_slots = keep_begin[n_regions].
+ * The engine has synchronised its stream when this returns: the caller needs no event. */
+int vs_result_ld_scores_device(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint64_t* n_slots, const void** dev_counts,
+                               const void** dev_keep_begin, const void** dev_n_scored, const void** dev_sums, const void** dev_n_pairs,
+                               const void** dev_state);
 /* Sample Gram matrix / GRM over regions: D^T D, the samples x samples product of the dosages -- what a GRM, kinship, IBS-type sharing
  * and the PCA of a cohort start from, and the one product of the dosage matrix the other column queries leave out (D Y:
  * vs_query_assoc_scan, D^T W: vs_query_sample_scores, the band of D D^T: vs_query_ld_band; no reference counterpart).  T, its rows, S

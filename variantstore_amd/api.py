@@ -724,6 +724,73 @@ class QueryResult:
         pv = got["pvalues"]
         return [(key, float(pv[live[k]]) if pv is not None else clumps[key][0], clumps[key][1]) for _p, k, key in ranked]
 
+    LDSCORE_STATES = {"scored": 1, "ineligible": 2, "dropped": 3}   # VS_LDSCORE_*
+    LDSCORE_ONE = 1 << 32                                            # VS_LDSCORE_ONE: the integer value of r2 = 1
+
+    def ld_scores(self):
+        """An LD-score result (VariantStore.ld_scores) as numpy arrays, one entry per slot -- region q's slots are keep_begin[q] :
+        keep_begin[q + 1], for the table rows row_begin[q] .. + row_count[q]: `sums` (uint64, the exact sum of floor(r2 * 2**32)
+        over the rows summed), `n_pairs` (uint32, how many were summed, the row itself included), `state` (uint8: LDSCORE_STATES),
+        `scores` (float64, sums / 2**32) and `scores_adj` (float64, the small-sample-adjusted score L - (n_pairs - L) / (n - 2):
+        r2 - (1 - r2) / (n - 2) summed; NaN for n <= 2; formed here from the two exact outputs).  `keep_begin` (uint64[Q + 1]),
+        `n_scored` (uint64[Q]), `counts` (structured as for allele_counts: the count record of every table row over the query's
+        samples), `col_ids` (uint32[C], the sample ids), `params` (dict: window, max_bp, min_ac, max_ac), the table's `rows` and per
+        region `row_begin` and `row_count`.  Copies, valid after the result is closed."""
+        nq, a, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        params = (C.c_uint32 * 4)()
+        cols = C.POINTER(C.c_uint32)()
+        cnt = C.POINTER(_lib.AlleleCounts)()
+        kb, ns, ps = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        pp = C.POINTER(C.c_uint32)()
+        pst = C.POINTER(C.c_uint8)()
+        _check(self._lib.vs_result_get_ld_scores(self._h, C.byref(nq), C.byref(a), C.byref(c), params, C.byref(cols), C.byref(cnt),
+                                                 C.byref(kb), C.byref(ns), C.byref(ps), C.byref(pp), C.byref(pst)), "vs_result_get_ld_scores")
+        q, na, nc = int(nq.value), int(a.value), int(c.value)
+        keep_begin = np.ctypeslib.as_array(kb, shape=(q + 1,)).copy()
+        n_scored = np.ctypeslib.as_array(ns, shape=(q,)).copy() if q else np.zeros(0, np.uint64)
+        total = int(keep_begin[q])
+        sums = np.ctypeslib.as_array(ps, shape=(total,)).copy() if total else np.zeros(0, np.uint64)
+        n_pairs = np.ctypeslib.as_array(pp, shape=(total,)).copy() if total else np.zeros(0, np.uint32)
+        state = np.ctypeslib.as_array(pst, shape=(total,)).copy() if total else np.zeros(0, np.uint8)
+        counts = (np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint8)), shape=(na * 16,)).view(self.COUNT_DTYPE).copy() if na
+                  else np.zeros(0, self.COUNT_DTYPE))
+        scores = sums.astype(np.float64) / float(self.LDSCORE_ONE)
+        if nc > 2:
+            scores_adj = scores - (n_pairs.astype(np.float64) - scores) / float(nc - 2)
+        else:
+            scores_adj = np.full(total, np.nan)
+        raw = self.raw(with_carriers=False)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "col_ids": np.ctypeslib.as_array(cols, shape=(nc,)).copy(), "counts": counts, "sums": sums, "n_pairs": n_pairs,
+                "state": state, "scores": scores, "scores_adj": scores_adj, "keep_begin": keep_begin, "n_scored": n_scored,
+                "params": {"window": int(params[0]), "max_bp": int(params[1]), "min_ac": int(params[2]), "max_ac": int(params[3])}}
+
+    def region_ld_scores(self, q, scores=None):
+        """Region q of an LD-score result: a dict of views into `scores` (ld_scores() of this result; taken now when None) --
+        `sums`, `n_pairs`, `state`, `scores`, `scores_adj` of the region's slots, and `rows` and `counts` of its table rows."""
+        got = self.ld_scores() if scores is None else scores
+        q = int(q)
+        if not 0 <= q < got["row_begin"].shape[0]:
+            raise IndexError(f"region {q} of {got['row_begin'].shape[0]}")
+        o, e = int(got["keep_begin"][q]), int(got["keep_begin"][q + 1])
+        a0 = int(got["row_begin"][q])
+        out = {k: got[k][o:e] for k in ("sums", "n_pairs", "state", "scores", "scores_adj")}
+        out["rows"], out["counts"] = got["rows"][a0:a0 + e - o], got["counts"][a0:a0 + e - o]
+        return out
+
+    def ld_scores_device(self):
+        """An LD-score result as it lies in this GPU's memory: a dict of the addresses `sums` (n_slots uint64), `n_pairs` (n_slots
+        uint32), `state` (n_slots bytes), `keep_begin` (n_regions + 1 uint64), `n_scored` (n_regions uint64) and `counts` (n_rows
+        records of four uint32), with `n_regions`, `n_rows`, `n_cols` and `n_slots`; complete when this returns and valid until
+        the result is closed."""
+        nq, a, c, s = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        pc, pb, pn, psum, pp, pst = (C.c_void_p() for _ in range(6))
+        _check(self._lib.vs_result_ld_scores_device(self._h, C.byref(nq), C.byref(a), C.byref(c), C.byref(s), C.byref(pc), C.byref(pb),
+                                                    C.byref(pn), C.byref(psum), C.byref(pp), C.byref(pst)), "vs_result_ld_scores_device")
+        return {"sums": int(psum.value or 0), "n_pairs": int(pp.value or 0), "state": int(pst.value or 0), "keep_begin": int(pb.value or 0),
+                "n_scored": int(pn.value or 0), "counts": int(pc.value or 0), "n_regions": int(nq.value), "n_rows": int(a.value),
+                "n_cols": int(c.value), "n_slots": int(s.value)}
+
     def region_ld(self, q):
         """The pairs region q of an LD result reports: a list of dicts with `a` and `b` (each (pos, ref, alt)) and `value` (int under
         "dot", float under "r2") for every pair of the region's reported rows at most the window apart in the table."""
@@ -1226,6 +1293,24 @@ class VariantStore:
             window = 0
         _check(self._lib.vs_query_ld_prune(self._h, ptr, n, ids_ptr, n_ids, window, int(max_bp) & 0xFFFFFFFF, threshold, int(min_ac),
                                            0xFFFFFFFF if max_ac is None else int(max_ac), C.byref(h)), "vs_query_ld_prune")
+        return QueryResult(self, h)
+
+    def ld_scores(self, regions, samples=None, window=0, max_bp=1_000_000, min_ac=0, max_ac=None) -> QueryResult:
+        """LD scores over regions (vs_query_ld_scores): for every table row of every region the sum of its squared dosage
+        correlation with the rows of the same region at most `window` table rows (0: no limit; there is no 256-row ceiling) and at
+        most `max_bp` positions (0: no limit) away, the row itself included, over `samples` (names or ids, taken as a set; None:
+        the whole cohort).  A row is scored when it is polymorphic there and its alternate-allele count lies in [min_ac, max_ac]
+        (max_ac None: no upper limit); the others are skipped and add to no sum.  Every r2 is floor(r2 * 2**32) in exact integers
+        and the sums are integers: the same call gives the same bytes.  Regions are independent.  `regions` as for
+        allele_counts.  Read the result with QueryResult.ld_scores / region_ld_scores / ld_scores_device / region_text."""
+        arr, ptr, n = _regions_array(regions)
+        h = C.c_void_p()
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        window, max_bp = int(window), int(max_bp)
+        if not 0 <= window <= 0xFFFFFFFF or not 0 <= max_bp <= 0xFFFFFFFF:
+            raise ValueError(f"window {window} / max_bp {max_bp}: 0 .. 2**32 - 1")
+        _check(self._lib.vs_query_ld_scores(self._h, ptr, n, ids_ptr, n_ids, window, max_bp, int(min_ac),
+                                            0xFFFFFFFF if max_ac is None else int(max_ac), C.byref(h)), "vs_query_ld_scores")
         return QueryResult(self, h)
 
     def ld_matrix(self, regions, samples=None, stat="r2") -> QueryResult:

@@ -1271,7 +1271,22 @@ int clump_pvalues(vs_index* idx, const std::vector<vs_region>& batch, const std:
   return EXIT_SUCCESS;
 }
 
-int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false, bool ldmatrix = false, bool prune = false, bool clump = false) {
+// `variantstore ldscore`: the LD score of every variant of every region (vs_query_ld_scores) over the same samples.  Output as
+// `prune`: "#region <i> <x>:<y>", then the region's text ("Pos Ref Alt AC Pairs L2 State", a line per reported row: scored or skip).
+int ldscore_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore ldscore -p <output-prefix> -r <region> [-S <sample-name-file>] [-w <window>] [--bp <n>]\n"
+               "                             [--min-ac <n>] [--max-ac <n>] [-o <outfile>] [--device <n>]\n\n"
+               "        For every region the LD score of its variants (as query type 6 reports them): the sum of the squared dosage\n"
+               "        correlation of a variant with every variant of the region at most <window> rows (0, the default: no limit)\n"
+               "        and at most --bp positions (1000000 by default; 0: no limit) away, itself included, over the whole cohort or\n"
+               "        the samples named in the file.  Pairs: the variants summed.  Variants that are monomorphic there or whose\n"
+               "        alternate-allele count lies outside [--min-ac, --max-ac] are skipped and add to no sum.\n";
+  return EXIT_FAILURE;
+}
+
+int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool ld = false, bool ldmatrix = false, bool prune = false, bool clump = false,
+                bool ldscore = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
   if (rc != VS_OK) die(rc, "load");
@@ -1305,13 +1320,14 @@ int counts_main(const Args& a, bool burden = false, bool genotypes = false, bool
     rc = vs_query_ld_clump(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), pvalues.empty() ? &none : pvalues.data(), pvalues.size(),
                            a.ld_window, a.prune_max_bp, a.prune_threshold, a.clump_p1, a.clump_p2, &res);
   }
+  else if (ldscore) rc = vs_query_ld_scores(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_window, a.prune_max_bp, a.min_ac, a.max_ac, &res);
   else if (prune) rc = vs_query_ld_prune(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_window, a.prune_max_bp, a.prune_threshold, a.min_ac, a.max_ac, &res);
   else if (ldmatrix) rc = vs_query_ld_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_dot ? VS_LD_DOT : VS_LD_R2, &res);
   else if (ld) rc = vs_query_ld_band(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.ld_window, a.ld_dot ? VS_LD_DOT : VS_LD_R2, &res);
   else if (genotypes) rc = vs_query_genotype_matrix(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
   else if (burden) rc = vs_query_sample_burden(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), a.min_ac, a.max_ac, &res);
   else rc = vs_query_allele_counts(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &res);
-  if (rc != VS_OK) die(rc, clump ? "clump" : prune ? "prune" : ldmatrix ? "ldmatrix" : ld ? "ld" : genotypes ? "genotypes" : burden ? "burden" : "counts");
+  if (rc != VS_OK) die(rc, ldscore ? "ldscore" : clump ? "clump" : prune ? "prune" : ldmatrix ? "ldmatrix" : ld ? "ld" : genotypes ? "genotypes" : burden ? "burden" : "counts");
   std::ofstream file;
   if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
   std::ostream& out = a.outfile.empty() ? std::cout : file;
@@ -1339,6 +1355,7 @@ int main(int argc, char** argv) {
     if (i + 1 >= argc) { std::cerr << "missing value for " << argv[i] << "\n"; exit(EXIT_FAILURE); }
     return argv[++i];
   };
+  if (a.cmd == "ldscore") { a.ld_window = 0; a.prune_max_bp = 1000000; }   // no row limit, 1 Mb
   if (a.cmd == "clump") { a.ld_window = 256; a.prune_max_bp = 250000; a.prune_threshold = 524288; }   // plink's defaults: 250 kb, r2 0.5
   for (int i = 2; i < argc; ++i) {
     std::string f = argv[i];
@@ -1370,13 +1387,13 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "prune" || a.cmd == "clump" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "prune" || a.cmd == "clump" || a.cmd == "ldscore" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
-      else if ((a.cmd == "burden" || a.cmd == "prune") && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
-      else if ((a.cmd == "burden" || a.cmd == "prune") && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
-      else if ((a.cmd == "ld" || a.cmd == "prune" || a.cmd == "clump") && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if ((a.cmd == "burden" || a.cmd == "prune" || a.cmd == "ldscore") && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if ((a.cmd == "burden" || a.cmd == "prune" || a.cmd == "ldscore") && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if ((a.cmd == "ld" || a.cmd == "prune" || a.cmd == "clump" || a.cmd == "ldscore") && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if ((a.cmd == "ld" || a.cmd == "ldmatrix") && f == "--dot") a.ld_dot = true;
-      else if ((a.cmd == "prune" || a.cmd == "clump") && f == "--bp") a.prune_max_bp = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
+      else if ((a.cmd == "prune" || a.cmd == "clump" || a.cmd == "ldscore") && f == "--bp") a.prune_max_bp = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if (a.cmd == "clump" && (f == "-A" || f == "--pvalues")) a.pvalues_file = need(i);
       else if (a.cmd == "clump" && (f == "--p1" || f == "--p2")) {
         const std::string v = need(i);
@@ -1447,6 +1464,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "prune") {
     if (a.prefix.empty() || a.region.empty()) return prune_usage();
     return counts_main(a, /*burden=*/false, /*genotypes=*/false, /*ld=*/false, /*ldmatrix=*/false, /*prune=*/true);
+  }
+  if (a.cmd == "ldscore") {
+    if (a.prefix.empty() || a.region.empty()) return ldscore_usage();
+    return counts_main(a, /*burden=*/false, /*genotypes=*/false, /*ld=*/false, /*ldmatrix=*/false, /*prune=*/false, /*clump=*/false, /*ldscore=*/true);
   }
   if (a.cmd == "clump") {
     if (a.prefix.empty() || a.region.empty() || a.pvalues_file.empty()) return clump_usage();

@@ -248,7 +248,7 @@ struct vs_result {
                  // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts; kKindAssoc: association scan;
                  // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM; kKindIbs: pairwise IBS counts / KING kinship;
                  // kKindLdMatrix: the full LD block of every region; kKindAssocMatrix: trait-matrix association scan;
-                 // kKindScoreMatrix: score matrix; kKindPrune: LD pruning verdicts; kKindClump: p-value clumping verdicts
+                 // kKindScoreMatrix: score matrix; kKindPrune: LD pruning verdicts; kKindClump: p-value clumping verdicts; kKindLdScore: LD scores
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -315,6 +315,13 @@ struct vs_result {
   uint64_t prune_states = 0;
   uint32_t prune_max_bp = 0, prune_T = 0, prune_min_ac = 0, prune_max_ac = UINT32_MAX;
   std::vector<uint64_t> h_prune_meta;
+  // LD-score results (vs_query_ld_scores): one buffer in HBM (d_ldscore) of prune_states slots -- sums [uint64], then n_pairs
+  // [uint32], then state [uint8], 13 bytes a slot --, copied to cells_pin in one piece; the 8-byte words beside it in d_prune_meta:
+  // keep_begin [Q + 1], wg_begin [Q + 1], n_scored [Q + 1, the last unused], the scan's summary (four words), the nonzero cells of
+  // the (temporary) genotype matrix (d_cell_total, two words); counts, column ids, ld_window (0: no limit), prune_max_bp,
+  // prune_min_ac and prune_max_ac as for a pruning result; ldscore_wgs: the score kernel's workgroups
+  uint8_t* d_ldscore = nullptr;
+  uint64_t ldscore_wgs = 0;
   // clumping results (vs_query_ld_clump): d_state, d_prune_meta, prune_states, ld_window, prune_max_bp and prune_T as for a pruning
   // result -- the words are keep_begin [Q + 1], n_index [Q + 1, the last unused], the scan's summary, d_cell_total, then the rounds
   // every region took [Q + 1, the last unused] --, an owner per verdict beside the state (d_owner, its page-locked copy owner_pin),
@@ -361,9 +368,10 @@ constexpr int kKindLdMatrix = 17;   // ... of an LD-matrix result: the rows of t
 constexpr int kKindAssocMatrix = 18;   // ... of a trait-matrix association result: the rows of type 6, a score per row and trait (up to VS_TRAIT_MATRIX_MAX traits) instead of carrier lists
 constexpr int kKindScoreMatrix = 19;   // ... of a score-matrix result: the rows of type 6, a columns x scores matrix of weighted dosage sums (up to VS_SCORE_MATRIX_MAX scores) instead of carrier lists
 constexpr int kKindPrune = 20;   // ... of a pruning result: the rows of type 6, a verdict byte per reported row instead of carrier lists
+constexpr int kKindLdScore = 22;   // ... of an LD-score result: the rows of type 6, a sum, a pair count and a state byte per reported row instead of carrier lists
 constexpr int kKindClump = 21;   // ... of a clumping result: the rows of type 6, a verdict byte and an owner per reported row instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindClump || r->kind == kKindPrune || r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
+  return r->kind == kKindLdScore || r->kind == kKindClump || r->kind == kKindPrune || r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
          r->kind == kKindScores;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
@@ -386,6 +394,8 @@ static int refuse_no_lists(const vs_result* r, const char* what) {
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD-matrix result holds a square block of pair statistics per region, no carrier lists (vs_result_get_ld_matrix)", what);
   if (r->kind == kKindClump)
     return fail(VS_ERR_UNSUPPORTED, "%s: a clumping result holds a verdict and an owner per reported row, no carrier lists (vs_result_get_ld_clump)", what);
+  if (r->kind == kKindLdScore)
+    return fail(VS_ERR_UNSUPPORTED, "%s: an LD-score result holds a sum of r2 per reported row, no carrier lists (vs_result_get_ld_scores)", what);
   if (r->kind == kKindPrune)
     return fail(VS_ERR_UNSUPPORTED, "%s: a pruning result holds a verdict per reported row, no carrier lists (vs_result_get_ld_prune)", what);
   if (r->kind == kKindLd)
@@ -1256,7 +1266,8 @@ static int capture_totals(vs_result* r) {
 // Prune: as LD (ld_window) with the walk's parameters: prune_max_bp, prune_T (0 .. 2^20), prune_min_ac, prune_max_ac.
 // Clump: as Prune without the allele-count window; `clump_keys` (host memory, owned by the result), n_pvalues of them, held against
 // the number of table rows once the plan has given it; clump_key: the keys of p1 and p2.
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix, Prune, Clump };
+// LdScore: as Prune without the threshold; ld_window = 0 stands for no row limit.
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix, Prune, Clump, LdScore };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1700,7 +1711,7 @@ struct SharedCtx {
   uint64_t* am_dev = nullptr;   // shared_tables: a trait-matrix batch's Sy, vy, shifts and limb panel on the device (ld_tmp)
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix || q.kind == ReqKind::Prune || q.kind == ReqKind::Clump) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix || q.kind == ReqKind::Prune || q.kind == ReqKind::Clump || q.kind == ReqKind::LdScore) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -2013,6 +2024,21 @@ static int clump_fits(SharedCtx& c, uint64_t states) {
               (unsigned long long)(r->d.A * mask_row), (unsigned long long)(r->d.A * 9), (unsigned long long)(states * 2 * mask_row), (unsigned long long)(states * 5),
               (unsigned long long)region_bytes, (unsigned long long)(cap >> 20));
 }
+// An LD-score batch: the temporary matrix, 13 bytes per slot (8 of the sum, 4 of the pair count, 1 of the state) and the per-region
+// words together, under the same limit.  `slots` as prune_fits' `states`.
+static int ldscore_fits(SharedCtx& c, uint64_t slots) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  r->mx_pitch = ((uint64_t)c.req.n_cols + 15) & ~15ull;
+  const uint64_t region_bytes = 8 * (3 * (r->d.Q + 1) + 6);   // (Q < 2^32)
+  if (region_bytes <= cap && slots <= (cap - region_bytes) / 13 && r->d.A <= (cap - region_bytes - slots * 13) / r->mx_pitch) return VS_OK;
+  (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+  (void)hipStreamSynchronize(idx->stream);
+  return fail(VS_ERR_ARG, "the LD scores of %llu regions over %llu rows x %u columns take %llu bytes (%llu of the genotype matrix they are formed from, "
+              "%llu of the sums, pair counts and states, %llu of the per-region arrays), more than the limit of %llu MiB (option matrix_max_mib): split the batch",
+              (unsigned long long)r->d.Q, (unsigned long long)r->d.A, c.req.n_cols, (unsigned long long)(r->d.A * r->mx_pitch + slots * 13 + region_bytes),
+              (unsigned long long)(r->d.A * r->mx_pitch), (unsigned long long)(slots * 13), (unsigned long long)region_bytes, (unsigned long long)(cap >> 20));
+}
 // Reads the totals (*pt) or the speculation.  Leaves U / n_slow / n_runs, the result's sizes and bookkeeping, a speculative batch
 // registered with its slot, what the request's kind allocates, and the form of the rows and the expansion (n_fill .. lean).
 static int shared_tables(SharedCtx& c) {
@@ -2148,6 +2174,15 @@ static int shared_tables(SharedCtx& c) {
       r->ld_window = q.ld_window;
       r->prune_max_bp = q.prune_max_bp; r->prune_T = q.prune_T;
       break;
+    case ReqKind::LdScore:   // (as Prune: the temporary matrix and the slots wait for ldscore_tables, behind the permutation)
+      VS_TRY(ldscore_fits(c, 0));
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      VS_TRY(ralloc(r, 3 * (size_t)(d.Q + 1) + 6, &r->d_prune_meta));
+      r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_prune_meta + 3 * (d.Q + 1) + 4);
+      r->ld_window = q.ld_window;
+      r->prune_max_bp = q.prune_max_bp; r->prune_min_ac = q.prune_min_ac; r->prune_max_ac = q.prune_max_ac;
+      break;
   }
   c.async_fill = c.allow_async && idx->opts.async_fill && c.n_fill > 0;
   c.fused = idx->opts.fill_fused && c.lists && !c.resident && !c.async_fill;
@@ -2266,6 +2301,8 @@ static int prune_tables(SharedCtx& c);
 static int launch_prune(SharedCtx& c);
 static int clump_tables(SharedCtx& c);
 static int launch_clump(SharedCtx& c);
+static int ldscore_tables(SharedCtx& c);
+static int launch_ldscore(SharedCtx& c);
 static int shared_columns(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
   if (!c.behind_perm && !r->d.A) return VS_OK;
@@ -2273,6 +2310,7 @@ static int shared_columns(SharedCtx& c) {
   if (c.req.kind == ReqKind::AssocMatrix) VS_TRY(assoc_matrix_upload(c));   // (in front of the pair of events as well)
   if (c.req.kind == ReqKind::Prune) VS_TRY(prune_tables(c));   // (its one host wait in front of the pair of events as well)
   if (c.req.kind == ReqKind::Clump) VS_TRY(clump_tables(c));   // (the same wait, and the upload of the keys)
+  if (c.req.kind == ReqKind::LdScore) VS_TRY(ldscore_tables(c));   // (the same wait)
   VS_TRY(result_events(r));
   HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
   if (c.req.kind == ReqKind::Groups) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, r->d_counts);
@@ -2295,6 +2333,9 @@ static int shared_columns(SharedCtx& c) {
   } else if (c.req.kind == ReqKind::Clump) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_clump(c));
+  } else if (c.req.kind == ReqKind::LdScore) {
+    VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+    VS_TRY(launch_ldscore(c));
   } else if (c.req.kind == ReqKind::AssocMatrix) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_assoc_matrix(c));
@@ -2559,6 +2600,54 @@ static int launch_ld_block(vs_index* idx, vs_result* r, const uint8_t* cells, co
   a.counts = r->d_counts; a.out = r->d_ldm;
   if (lq.ld_stat == VS_LD_R2) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_block<true>), dim3((unsigned)r->ldm_wgs), dim3(256), 0, idx->stream, a);
   else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ld_block<false>), dim3((unsigned)r->ldm_wgs), dim3(256), 0, idx->stream, a);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+
+// An LD-score batch behind the permutation (the per-region arrays are in the caller's order): keep_begin and the workgroups' prefix
+// from the per-region row counts by one small scan; the two totals come back in ONE host wait (the batch is never speculative).
+// The temporary matrix, the slots and the per-region words together are held against option matrix_max_mib here, before the first
+// two are allocated.
+static int ldscore_tables(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  uint64_t* meta = r->d_prune_meta;
+  hipLaunchKernelGGL(k_ld_score_scan, dim3(1), dim3(kLdBlockScanThreads), 0, idx->stream, (const uint64_t*)d.q_nvar, d.Q, meta, meta + (d.Q + 1), meta + 3 * (d.Q + 1),
+                     c.req.ld_window);
+  HIP_TRY(hipGetLastError());
+  uint64_t sum[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(sum, meta + 3 * (d.Q + 1), sizeof sum, hipMemcpyDeviceToHost, idx->stream));
+  HIP_TRY(hipStreamSynchronize(idx->stream));
+  VS_TRY(ldscore_fits(c, sum[0]));
+  if (sum[1] > 0x7FFFFFFFull) {
+    (void)hipStreamSynchronize(c.ps);
+    return fail(VS_ERR_ARG, "batch too large for one launch (%llu tile pairs)", (unsigned long long)sum[1]);
+  }
+  r->prune_states = sum[0]; r->ldscore_wgs = sum[1];
+  VS_TRY(dev_alloc(idx, (size_t)(d.A * r->mx_pitch), (void**)&c.ld_matrix, &c.ld_tmp.bufs));
+  VS_TRY(ralloc(r, (size_t)sum[0] * 13, &r->d_ldscore));
+  return VS_OK;
+}
+
+// The scores of an LD-score batch from its temporary genotype matrix and the table's counts: k_ld_score_init, a workgroup per
+// region, then k_ld_score, one workgroup per (region, tile, tile distance), all regions in one launch.
+static int launch_ldscore(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  const SharedReq& q = c.req;
+  LdScoreArgs a{};
+  a.cells = c.ld_matrix; a.pitch = (uint32_t)r->mx_pitch; a.n_cols = q.n_cols; a.Q = d.Q;
+  a.row_begin = (const uint64_t*)d.var_begin; a.row_count = (const uint64_t*)d.q_nvar;
+  a.keep_begin = r->d_prune_meta; a.wg_begin = r->d_prune_meta + (d.Q + 1);
+  a.rows = (const VariantRow*)d.rows; a.counts = r->d_counts;
+  a.window = q.ld_window; a.max_bp = q.prune_max_bp; a.min_ac = q.prune_min_ac; a.max_ac = q.prune_max_ac;
+  a.sums = reinterpret_cast<unsigned long long*>(r->d_ldscore);
+  a.n_pairs = reinterpret_cast<uint32_t*>(r->d_ldscore + 8 * r->prune_states);
+  a.state = r->d_ldscore + 12 * r->prune_states;
+  a.n_scored = r->d_prune_meta + 2 * (d.Q + 1);
+  if (d.Q > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu regions)", (unsigned long long)d.Q);
+  hipLaunchKernelGGL(k_ld_score_init, dim3((unsigned)d.Q), dim3(256), 0, idx->stream, a);
+  if (r->ldscore_wgs) hipLaunchKernelGGL(k_ld_score, dim3((unsigned)r->ldscore_wgs), dim3(256), 0, idx->stream, a);
   HIP_TRY(hipGetLastError());
   return VS_OK;
 }
@@ -4523,6 +4612,26 @@ int vs_query_ld_prune(vs_index* idx, const vs_region* regions, uint64_t n, const
   });
 }
 
+int vs_query_ld_scores(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, uint32_t window, uint32_t max_bp,
+                       uint32_t min_ac, uint32_t max_ac, vs_result** out) {
+  VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "an LD-score"));
+  if (min_ac > max_ac) return fail(VS_ERR_ARG, "an empty allele-count window [%u, %u]", min_ac, max_ac);
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));
+  if (cols.size() >= (1ull << 21))
+    return fail(VS_ERR_UNSUPPORTED, "LD scores over %llu columns: the exact quotient takes fewer than 2^21", (unsigned long long)cols.size());
+  if (mask.size() * 8 > kMatrixMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", idx->g.num_samples);
+  SharedReq req = column_request(ReqKind::LdScore, mask, rank, cols.size());
+  req.ld_window = window;
+  req.prune_max_bp = max_bp; req.prune_min_ac = min_ac; req.prune_max_ac = max_ac;
+  return make_result(idx, kKindLdScore, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
 // The key of a p-value in [0, 1]: the bit pattern of the non-negative double (-0.0 counts as 0), monotone in p.  False outside
 // [0, 1] and for a NaN.
 static bool clump_key(double p, uint64_t* key) {
@@ -4748,7 +4857,7 @@ static int prune_meta_to_host(vs_result* r) {
   if (!r->h_prune_meta.empty()) return VS_OK;
   VS_TRY(result_ready(r));
   // (a clumping result: n_index in n_kept's place, and behind the scan's summary and the cell total the rounds of every region)
-  VS_TRY(fetch(r->idx, r->h_prune_meta, (const uint64_t*)r->d_prune_meta, r->kind == kKindClump ? 3 * ((size_t)r->d.Q + 1) + 4 : 2 * ((size_t)r->d.Q + 1)));
+  VS_TRY(fetch(r->idx, r->h_prune_meta, (const uint64_t*)r->d_prune_meta, r->kind == kKindClump ? 3 * ((size_t)r->d.Q + 1) + 4 : r->kind == kKindLdScore ? 3 * ((size_t)r->d.Q + 1) : 2 * ((size_t)r->d.Q + 1)));
   HIP_TRY(hipStreamSynchronize(r->idx->stream));
   return VS_OK;
 }
@@ -4946,7 +5055,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
         for (uint64_t a = r->h_var_begin[q] * G, e = a + r->h_nvar[q] * G; a < e; ++a) nc += c[a].x;
       r->n_carriers_kept = nc;
     }
-    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindPrune || r->kind == kKindClump || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
+    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindPrune || r->kind == kKindClump || r->kind == kKindLdScore || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
       VS_TRY(result_ready(r));
       uint64_t nc = 0;
       HIP_TRY(hipMemcpyAsync(&nc, r->d_cell_total, 8, hipMemcpyDeviceToHost, idx->stream));
@@ -5132,6 +5241,47 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
       out += std::to_string(cnt[a - a0].y);
       const uint8_t verdict = st[a - a0];
       out += verdict == kPruneKept ? "\tkeep\n" : verdict == kPrunePruned ? "\tpruned\n" : "\tskip\n";
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
+  if (r->kind == kKindLdScore) {   // the region's reported rows with their pair counts and scores
+    const VariantRow* rows;
+    if (r->have_headers) rows = r->h_rows.data() + a0;
+    else if (r->raw_rows) rows = r->raw_rows + a0;
+    else {
+      VS_TRY(fetch(idx, r->sl_rows, (const VariantRow*)r->d.rows + a0, (size_t)(a1 - a0)));
+      rows = r->sl_rows.data();
+    }
+    VS_TRY(array_to_host(r, r->d_ldscore, (size_t)r->prune_states * 13, &r->cells_pin, "LD scores"));
+    VS_TRY(counts_to_host(r));
+    VS_TRY(prune_meta_to_host(r));
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    const uint8_t* base = (const uint8_t*)r->cells_pin.p;
+    const uint64_t kb = r->h_prune_meta[q];
+    const uint64_t* sums = (const uint64_t*)base + kb;
+    const uint32_t* pairs = (const uint32_t*)(base + 8 * r->prune_states) + kb;
+    const uint8_t* st = base + 12 * r->prune_states + kb;
+    const uint4* cnt = (const uint4*)r->counts_pin.p + a0;
+    std::string& out = r->text;
+    out = "Pos\tRef\tAlt\tAC\tPairs\tL2\tState\n";
+    char num[64];
+    for (uint64_t a = a0; a < a1; ++a) {
+      const VariantRow& v = rows[a - a0];
+      if (v.count_flags & kRowDropped) continue;
+      out += std::to_string(v.pos);
+      out += '\t';
+      out.append(idx->seq_chars, v.ref_off, v.ref_len);
+      out += '\t';
+      out.append(idx->seq_chars, v.alt_off, v.alt_len);
+      out += '\t';
+      out += std::to_string(cnt[a - a0].y);
+      out += '\t';
+      out += std::to_string(pairs[a - a0]);
+      snprintf(num, sizeof num, "\t%.6f", (double)sums[a - a0] / 4294967296.0);
+      out += num;
+      out += st[a - a0] == kLdScoreScored ? "\tscored\n" : "\tskip\n";
     }
     *text = out.c_str();
     if (len) *len = out.size();
@@ -5707,6 +5857,46 @@ int vs_result_ld_prune_device(vs_result* r, uint64_t* n_regions, uint64_t* n_row
   if (n_regions) *n_regions = r->d.Q;
   if (n_rows) *n_rows = r->d.A;
   if (n_cols) *n_cols = r->h_cols.size();
+  return VS_OK;
+}
+
+int vs_result_get_ld_scores(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint32_t* params, const uint32_t** col_ids,
+                            const vs_allele_counts** counts, const uint64_t** keep_begin, const uint64_t** n_scored, const uint64_t** sums, const uint32_t** n_pairs,
+                            const uint8_t** state) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!sums) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindLdScore) return fail(VS_ERR_ARG, "not an LD-score result (vs_query_ld_scores)");
+  VS_TRY(array_to_host(r, r->d_ldscore, (size_t)r->prune_states * 13, &r->cells_pin, "LD scores"));
+  VS_TRY(counts_to_host(r));
+  VS_TRY(prune_meta_to_host(r));
+  const uint8_t* base = (const uint8_t*)r->cells_pin.p;
+  *sums = (const uint64_t*)base;
+  if (n_pairs) *n_pairs = (const uint32_t*)(base + 8 * r->prune_states);
+  if (state) *state = base + 12 * r->prune_states;
+  if (counts) *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (keep_begin) *keep_begin = r->h_prune_meta.data();
+  if (n_scored) *n_scored = r->h_prune_meta.data() + 2 * (r->d.Q + 1);
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (params) { params[0] = r->ld_window; params[1] = r->prune_max_bp; params[2] = r->prune_min_ac; params[3] = r->prune_max_ac; }
+  if (col_ids) *col_ids = r->h_cols.data();
+  return VS_OK;
+}
+
+int vs_result_ld_scores_device(vs_result* r, uint64_t* n_regions, uint64_t* n_rows, uint64_t* n_cols, uint64_t* n_slots, const void** dev_counts,
+                               const void** dev_keep_begin, const void** dev_n_scored, const void** dev_sums, const void** dev_n_pairs, const void** dev_state) {
+  VS_TRY(device_matrix_ready(r, dev_sums, kKindLdScore, "not an LD-score result (vs_query_ld_scores)"));
+  *dev_sums = r->d_ldscore;
+  if (dev_n_pairs) *dev_n_pairs = r->d_ldscore + 8 * r->prune_states;
+  if (dev_state) *dev_state = r->d_ldscore + 12 * r->prune_states;
+  if (dev_counts) *dev_counts = r->d_counts;
+  if (dev_keep_begin) *dev_keep_begin = r->d_prune_meta;
+  if (dev_n_scored) *dev_n_scored = r->d_prune_meta + 2 * (r->d.Q + 1);
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_slots) *n_slots = r->prune_states;
   return VS_OK;
 }
 

@@ -53,10 +53,12 @@ __host__ __device__ __forceinline__ uint64_t ld_block_pairs(uint64_t m) {
   return t * (t + 1) / 2;
 }
 
-// block_begin[q], wg_begin[q] = the sums of m^2 and of the tile pairs over the regions in front of q; [Q]: the totals.
-// summary = {cells, workgroups, largest m, 0}.
-__global__ void __launch_bounds__(kLdBlockScanThreads) k_ld_block_scan(const uint64_t* __restrict__ row_count, uint64_t Q, uint64_t* __restrict__ block_begin,
-                                                                        uint64_t* __restrict__ wg_begin, uint64_t* __restrict__ summary) {
+// The two exclusive scans of a batch's per-region row counts by one workgroup of kLdBlockScanThreads threads: first[q], second[q] =
+// the sums of fa(m) and fb(m) over the regions in front of q; [Q]: the totals.  summary = {total of fa, total of fb, largest m, 0}.
+// k_ld_block_scan and k_ld_score_scan (k_ld_score.hip.h) share it.
+template <class FA, class FB>
+__device__ __forceinline__ void ld_region_scans(const uint64_t* __restrict__ row_count, uint64_t Q, uint64_t* __restrict__ first, uint64_t* __restrict__ second,
+                                                uint64_t* __restrict__ summary, FA fa, FB fb) {
   __shared__ uint64_t s_cells[kLdBlockScanThreads / 64], s_wgs[kLdBlockScanThreads / 64], s_max[kLdBlockScanThreads / 64];
   const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   uint64_t carry_c = 0, carry_w = 0, largest = 0;
@@ -66,7 +68,7 @@ __global__ void __launch_bounds__(kLdBlockScanThreads) k_ld_block_scan(const uin
 #pragma unroll
     for (uint32_t i = 0; i < kLdBlockScanItems; ++i) {
       m[i] = q0 + i < Q ? row_count[q0 + i] : 0;
-      sc += m[i] * m[i]; sw += ld_block_pairs(m[i]);
+      sc += fa(m[i]); sw += fb(m[i]);
       largest = m[i] > largest ? m[i] : largest;
     }
     uint64_t ic = sc, iw = sw;
@@ -87,8 +89,8 @@ __global__ void __launch_bounds__(kLdBlockScanThreads) k_ld_block_scan(const uin
     uint64_t ec = carry_c + before_c + ic - sc, ew = carry_w + before_w + iw - sw;
 #pragma unroll
     for (uint32_t i = 0; i < kLdBlockScanItems; ++i) {
-      if (q0 + i < Q) { block_begin[q0 + i] = ec; wg_begin[q0 + i] = ew; }
-      ec += m[i] * m[i]; ew += ld_block_pairs(m[i]);
+      if (q0 + i < Q) { first[q0 + i] = ec; second[q0 + i] = ew; }
+      ec += fa(m[i]); ew += fb(m[i]);
     }
     carry_c += total_c; carry_w += total_w;
   }
@@ -101,8 +103,52 @@ __global__ void __launch_bounds__(kLdBlockScanThreads) k_ld_block_scan(const uin
   __syncthreads();
   if (threadIdx.x == 0) {
     for (uint32_t w = 1; w < kLdBlockScanThreads / 64; ++w) largest = s_max[w] > largest ? s_max[w] : largest;
-    block_begin[Q] = carry_c; wg_begin[Q] = carry_w;
+    first[Q] = carry_c; second[Q] = carry_w;
     summary[0] = carry_c; summary[1] = carry_w; summary[2] = largest; summary[3] = 0;
+  }
+}
+
+// block_begin[q], wg_begin[q] = the sums of m^2 and of the tile pairs over the regions in front of q; [Q]: the totals.
+// summary = {cells, workgroups, largest m, 0}.
+__global__ void __launch_bounds__(kLdBlockScanThreads) k_ld_block_scan(const uint64_t* __restrict__ row_count, uint64_t Q, uint64_t* __restrict__ block_begin,
+                                                                        uint64_t* __restrict__ wg_begin, uint64_t* __restrict__ summary) {
+  ld_region_scans(row_count, Q, block_begin, wg_begin, summary, [](uint64_t m) { return m * m; }, [](uint64_t m) { return ld_block_pairs(m); });
+}
+
+// The products of a workgroup's tile pair: acc[t] = the wave's 16-row tile of panel ti (first row ai within the region) against the
+// 16-row tile t of panel tj (first row bj), summed over all columns.  k_ld_block and k_ld_score (k_ld_score.hip.h) share it:
+// staging, fragments and MFMAs are one piece of code, the epilogues differ.
+__device__ __forceinline__ void ld_block_products(const uint8_t* __restrict__ cells, uint32_t pitch, uint64_t r0, uint64_t m, uint64_t ai, uint64_t bj, bool diag,
+                                                  uint8_t* s_ld, ld_i32x4 (&acc)[4]) {
+  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const uint32_t words = (diag ? kLdBlockTile : 2 * kLdBlockTile) * (kLdChunk / 16);
+  const uint32_t b_base = diag ? 0u : kLdBlockTile * kLdStride;    // panel tj in LDS
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc[t] = ld_i32x4{0, 0, 0, 0};
+  const uint32_t frag = (lane & 15) * kLdStride + 16 * (lane >> 4);   // the lane's fragment of k-step 0 within a 16-row tile
+  for (uint32_t c0 = 0; c0 < pitch; c0 += kLdChunk) {
+    if (c0) __syncthreads();   // (the chunk before this one has been read)
+    // ---- staging: 16 bytes per thread and step, dosages on the way in ----
+#pragma unroll 4
+    for (uint32_t i = threadIdx.x; i < words; i += 256) {
+      const uint32_t r = i >> 4, col = c0 + 16 * (i & 15);
+      const uint64_t local = (r < kLdBlockTile ? ai : bj - kLdBlockTile) + r;   // the row within the region
+      uint4 v{0u, 0u, 0u, 0u};
+      if (local < m && col < pitch) v = ld_load_dosages(cells + (r0 + local) * pitch + col);
+      *reinterpret_cast<uint4*>(s_ld + r * kLdStride + 16 * (i & 15)) = v;
+    }
+    __syncthreads();
+    // ---- products: four MFMAs per 64-column step ----
+    const uint32_t left = pitch - c0;
+    const uint32_t ksteps = left >= kLdChunk ? kLdChunk / 64 : (left + 63) / 64;
+    for (uint32_t ks = 0; ks < ksteps; ++ks) {
+      const ld_i32x4 fa = *reinterpret_cast<const ld_i32x4*>(s_ld + 16 * wid * kLdStride + frag + 64 * ks);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const ld_i32x4 fb = *reinterpret_cast<const ld_i32x4*>(s_ld + b_base + (uint32_t)t * 16 * kLdStride + frag + 64 * ks);
+        acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa, fb, acc[t], 0, 0, 0);
+      }
+    }
   }
 }
 
@@ -128,36 +174,8 @@ __global__ void __launch_bounds__(256) k_ld_block(LdBlockArgs a) {
   const uint64_t ti = p - tj * (tj + 1) / 2;
   const bool diag = ti == tj;
   const uint64_t ai = ti * kLdBlockTile, bj = tj * kLdBlockTile;   // the panels' first rows within the region
-  const uint32_t words = (diag ? kLdBlockTile : 2 * kLdBlockTile) * (kLdChunk / 16);
-  const uint32_t b_base = diag ? 0u : kLdBlockTile * kLdStride;    // panel tj in LDS
   ld_i32x4 acc[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) acc[t] = ld_i32x4{0, 0, 0, 0};
-  const uint32_t frag = (lane & 15) * kLdStride + 16 * (lane >> 4);   // the lane's fragment of k-step 0 within a 16-row tile
-  for (uint32_t c0 = 0; c0 < a.pitch; c0 += kLdChunk) {
-    if (c0) __syncthreads();   // (the chunk before this one has been read)
-    // ---- staging: 16 bytes per thread and step, dosages on the way in ----
-#pragma unroll 4
-    for (uint32_t i = threadIdx.x; i < words; i += 256) {
-      const uint32_t r = i >> 4, col = c0 + 16 * (i & 15);
-      const uint64_t local = (r < kLdBlockTile ? ai : bj - kLdBlockTile) + r;   // the row within the region
-      uint4 v{0u, 0u, 0u, 0u};
-      if (local < m && col < a.pitch) v = ld_load_dosages(a.cells + (r0 + local) * a.pitch + col);
-      *reinterpret_cast<uint4*>(s_ld + r * kLdStride + 16 * (i & 15)) = v;
-    }
-    __syncthreads();
-    // ---- products: four MFMAs per 64-column step ----
-    const uint32_t left = a.pitch - c0;
-    const uint32_t ksteps = left >= kLdChunk ? kLdChunk / 64 : (left + 63) / 64;
-    for (uint32_t ks = 0; ks < ksteps; ++ks) {
-      const ld_i32x4 fa = *reinterpret_cast<const ld_i32x4*>(s_ld + 16 * wid * kLdStride + frag + 64 * ks);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const ld_i32x4 fb = *reinterpret_cast<const ld_i32x4*>(s_ld + b_base + (uint32_t)t * 16 * kLdStride + frag + 64 * ks);
-        acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa, fb, acc[t], 0, 0, 0);
-      }
-    }
-  }
+  ld_block_products(a.cells, a.pitch, r0, m, ai, bj, diag, s_ld, acc);
   // ---- epilogue: register g of the lane is the cell (a_first + g, b) ----
   const uint64_t a_first = ai + 16 * wid + 4 * (lane >> 4);
   const int64_t n = (int64_t)a.n_cols;

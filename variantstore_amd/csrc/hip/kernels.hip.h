@@ -87,6 +87,11 @@
 //                       workgroup per region: a row is a member once a blocker is an index, an index once every blocker is
 //                       decided and none is; in-place updates, no host wait between rounds; owners and n_index in a last pass
 //                       (vs_query_ld_clump: no reference counterpart)
+// k_ld_score            the LD score of every row of every region: k_ld_block's products (ld_block_products) with an epilogue that
+//  k_ld_score_scan       reduces the cells instead of storing them -- floor(cov^2 2^32 / (v_a v_b)) per eligible pair from 128-bit
+//  k_ld_score_init       integers (ld_score_q32), summed per row over a window of rows and positions with no 256-row ceiling, one
+//                       64-bit integer atomic per row and tile pair: exact and order-free; the scan of the regions' slots and
+//                       workgroups, and the state bytes (vs_query_ld_scores: no reference counterpart)
 // k_assoc_matrix        D Y over the same dosages: table rows x K traits (K up to 65,536) given as four int8 limbs of a fixed-point
 //                       value, 64 rows x 16 traits per workgroup, k_ld_band's staging and fragments, four MFMAs per 64-column step,
 //                       the limb sums combined in int64: exact dot products or the score test from 128-bit integers
@@ -127,6 +132,7 @@
 #include "k_ld_block.hip.h"
 #include "k_prune.hip.h"
 #include "k_clump.hip.h"
+#include "k_ld_score.hip.h"
 #include "k_int128.hip.h"
 #include "k_gram.hip.h"
 #include "k_assoc_matrix.hip.h"
