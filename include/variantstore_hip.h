@@ -232,6 +232,58 @@ int vs_result_get_group_counts(vs_result* r, uint64_t* n_rows, uint32_t* n_group
 /* The records as they lie in HBM: n_rows x n_groups records of 16 bytes, row-major, valid until vs_result_free.  The engine has
  * synchronised its stream when this returns: the caller needs no event. */
 int vs_result_group_counts_device(vs_result* r, uint64_t* n_rows, uint32_t* n_groups, const void** dev_counts);
+/* Window statistics: the grouped counts above reduced on the GPU per REGION and group, and per pair of groups, to the exact integers
+ * that nucleotide diversity pi, segregating sites, Watterson's theta, Tajima's D, dxy, Hudson's Fst, private alleles and fixed
+ * differences are formed from -- what `vcftools --window-pi / --TajimaD / --weir-fst-pop` or scikit-allel's windowed_* compute per
+ * window (no reference counterpart: what a caller would reduce on the host from vs_query_group_counts' rows x n_groups x 16 bytes).
+ * The arguments, their checks and the order of the checks are vs_query_group_counts's (the cohort limit of 32768 sample ids and
+ * argument errors before VS_ERR_NO_DEVICE included), with two additions: sample_ids == NULL with n_groups == 1 stands for the whole
+ * cohort as one group (group_of and n_ids are then ignored), and with_pairs may be 0 or 1 only (VS_ERR_ARG, checked right behind the
+ * range of n_groups).
+ * For every region q, in the caller's order, and every group g there is one vs_window_stats record, stats[q * n_groups + g], over
+ * the rows region q reports; a row the duplicate rule dropped is not a site and adds to nothing, `rows` included.  With `ac` a row's
+ * alt_alleles in g, N_g = 2 x group_size[g] and het = carriers - hom_alt in g: rows (reported, non-dropped rows, the same for every
+ * group), seg (0 < ac < N_g), singletons (ac == 1), doubletons (ac == 2), private_alleles (ac > 0 and no alternate allele in any
+ * other group; one group: ac > 0), fixed (N_g > 0 and ac == N_g), sum_ac, sum_ac2 (the sums of ac and ac^2) and obs_het (the sum of
+ * het).  With with_pairs every pair g < h adds one vs_window_pair_stats record, pair_stats[q * n_pairs + p], the pairs in the order
+ * (0,1), (0,2), ..., (n_groups-2, n_groups-1), n_pairs = n_groups (n_groups - 1) / 2 (at most 2016): sum_cross (the sum of
+ * ac_g x ac_h), seg_union (0 < ac_g + ac_h < N_g + N_h) and fixed_diff (both groups have members and one has ac == 0 while the
+ * other has ac == N).
+ * N_g is two allele copies per sample whatever the call's ploidy, as the GRM's 2n is; a multi-allelic site's ALT rows are separate
+ * sites with the index's genotype bits (a `1|2` call counts on both ALT rows), as in every column query here.
+ * The device sums integers only (ac <= 65534, so every product is below 2^32 and no 64-bit sum can overflow): the same call gives
+ * the same bytes.  pi, theta, Tajima's D, dxy and Fst are the caller's to form from them (the Python accessor and the command line do).
+ * The temporary rows x n_groups x 16 bytes and the n x (48 n_groups + 16 n_pairs) bytes of the answer together are held to option
+ * "matrix_max_mib": a larger request is refused with VS_ERR_ARG once the plan has given the rows and before anything is allocated.
+ * A region of more than option "window_chunk" rows is split between workgroups that add with integer atomics (same bytes).
+ * Every batch size takes the batch pipeline; the batch is never speculative and leaves the handle's type-6 state as it was.  The
+ * result holds the type-6 per-region arrays and variant table, no carrier arena, and the records: vs_result_get_raw /
+ * vs_result_get_view with with_carriers = 0, vs_result_layout (arena and lists 0), vs_result_fill_ms (the group kernel and the
+ * reduction, between the result's own pair of events), vs_result_totals (n_carriers as for a grouped-count result) and
+ * vs_result_format_region work -- integers only: "Group\tN\tRows\tSeg\tSingletons\tDoubletons\tPrivate\tFixed\tSumAC\tSumAC2\tObsHet\n",
+ * one line per group (Group is the group's name, or its decimal index without names; N its size in samples), then, when there are
+ * pair records, "GroupA\tGroupB\tSumCross\tSegUnion\tFixedDiff\n" and one line per pair --; with_carriers = 1, vs_result_digest,
+ * vs_result_pack_headers / _pack_regions and vs_comm_allgather_regions* fail with VS_ERR_UNSUPPORTED, the other kinds' getters with
+ * VS_ERR_ARG. */
+typedef struct vs_window_stats {
+  uint32_t rows, seg, singletons, doubletons, private_alleles, fixed;
+  uint64_t sum_ac, sum_ac2, obs_het;
+} vs_window_stats;
+typedef struct vs_window_pair_stats {
+  uint64_t sum_cross;
+  uint32_t seg_union, fixed_diff;
+} vs_window_pair_stats;
+int vs_query_window_stats(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, const uint32_t* group_of,
+                          uint64_t n_ids, uint32_t n_groups, const char* const* group_names, uint32_t with_pairs, vs_result** out);
+/* The records of a window-statistics result copied into page-locked memory owned by the result: stats[q * n_groups + g],
+ * pair_stats[q * n_pairs + p] (NULL without pair records), group_sizes[g] the number of distinct samples of group g, group_names the
+ * n_groups names (NULL when none were given).  Any may be NULL but `stats`.  VS_ERR_ARG on any other result. */
+int vs_result_get_window_stats(vs_result* r, uint64_t* n_regions, uint32_t* n_groups, uint32_t* n_pairs, const uint32_t** group_sizes,
+                               const char* const** group_names, const vs_window_stats** stats, const vs_window_pair_stats** pair_stats);
+/* The records as they lie in HBM: n_regions x n_groups records of 48 bytes, and n_regions x n_pairs pair records of 16 bytes (NULL
+ * without), valid until vs_result_free.  The engine has synchronised its stream when this returns: the caller needs no event. */
+int vs_result_window_stats_device(vs_result* r, uint64_t* n_regions, uint32_t* n_groups, uint32_t* n_pairs, const void** dev_stats,
+                                  const void** dev_pair_stats);
 /* Association scan: every row of the type-6 variant table scored against K phenotypes in one pass over its carriers -- "for the
  * variants in these regions, how does each one go with this trait?" (no reference counterpart: what a caller would get from
  * vs_query_genotype_matrix, a conversion of the cells to dosages and a matrix product, without the matrix).
@@ -1017,8 +1069,10 @@ void vs_comm_destroy(vs_comm* c);
  *                     the capacity of its recording walk (tests of that path)
  *   "burden_chunk"    rows of a region one workgroup of the burden kernel walks (vs_query_sample_burden): a region with more is
  *                     split between several, which add to its cells with atomics.  0 (default): 4096; else 64..65536
+ *   "window_chunk"    rows of a region one wave of the window-statistics kernel walks (vs_query_window_stats): a region with more is
+ *                     split between workgroups, which add to its records with integer atomics.  0 (default): 4096; else 64..65536
  *   "matrix_max_mib"  the largest genotype matrix (vs_query_genotype_matrix; also an LD batch's matrix + band, the records of
- *                     vs_query_group_counts, the cells + records of vs_query_assoc_scan and the buffers of vs_query_sample_scores), in MiB, a batch may ask for.  0 (default): 32 GiB
+ *                     vs_query_group_counts, the temporary counts + records of vs_query_window_stats, the cells + records of vs_query_assoc_scan and the buffers of vs_query_sample_scores), in MiB, a batch may ask for.  0 (default): 32 GiB
  *   "assoc_lds_max_kib" the largest phenotype table (columns x traits rounded up to 1, 2, 4 or 8, x 4 bytes) the kernel of
  *                     vs_query_assoc_scan stages in LDS, in KiB; a larger one is read through global memory.  0 (default): 32; else
  *                     1..128 (small cohorts reach the global form with 1).  The scores are the same bytes in either form

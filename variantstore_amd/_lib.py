@@ -103,6 +103,13 @@ SYMBOLS = {
     "vs_result_get_group_counts": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)),
                                              C.POINTER(C.POINTER(AlleleCounts))]),
     "vs_result_group_counts_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)]),
+    "vs_query_window_stats": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64,
+                                        C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(_P)]),
+    "vs_result_get_window_stats": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                             C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_void_p)]),
+    "vs_result_window_stats_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_void_p)]),
     "vs_query_assoc_scan": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_float), C.c_uint32,
                                       C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(_P)]),
     "vs_result_get_assoc_scan": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),

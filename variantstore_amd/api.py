@@ -100,6 +100,87 @@ def pvalue_keys(p):
     return keys
 
 
+def window_stats_derived(stats, pairs, group_sizes, lengths=None):
+    """The diversity statistics of a window-statistics result, formed in float64 from its exact integers (QueryResult.window_stats
+    calls this; `stats` (Q, G) and `pairs` (Q, P) are its structured arrays, `group_sizes` the G sizes in samples).  With n a
+    group's size, N = 2 n its allele copies (two per sample whatever the ploidy), S = seg, and per region:
+
+      pi          = 2 (N sum_ac - sum_ac2) / (N (N - 1))      the mean number of differences between two of the N copies, summed
+                                                              over the window's sites (sum over sites of 2 ac (N - ac) / (N (N - 1)));
+                                                              N sum_ac - sum_ac2 is formed exactly in uint64; NaN for N < 2
+      pi_per_bp   = pi / lengths[q]                           only with `lengths`
+      theta_w     = S / a1,  a1 = sum_{i=1}^{N-1} 1/i         Watterson's estimator; NaN for N < 2
+      tajima_d    = (pi - S / a1) / sqrt(e1 S + e2 S (S - 1)) Tajima 1989: a2 = sum 1/i^2, b1 = (N + 1) / (3 (N - 1)),
+                                                              b2 = 2 (N^2 + N + 3) / (9 N (N - 1)), c1 = b1 - 1 / a1,
+                                                              c2 = b2 - (N + 2) / (a1 N) + a2 / a1^2, e1 = c1 / a1,
+                                                              e2 = c2 / (a1^2 + a2); NaN for S = 0 and for N < 4 (the variance
+                                                              is identically zero at N = 2 and 3)
+      het_obs     = obs_het / (rows n)                        observed heterozygosity per site and sample; NaN for rows n = 0
+      dxy         = (N_h sum_ac_g + N_g sum_ac_h - 2 sum_cross) / (N_g N_h)
+                                                              the mean number of differences between a copy of g and a copy of h,
+                                                              summed over the window's sites; the numerator exact in uint64; NaN
+                                                              when either group is empty
+      fst_hudson  = 1 - ((pi_g + pi_h) / 2) / dxy             Hudson's Fst as the ratio of the window's sums (scikit-allel's
+                                                              hudson_fst); NaN where pi_g, pi_h or dxy is NaN or dxy = 0
+
+    An undefined quantity is NaN, never an exception.  Returns a dict with those arrays ((Q, G) and (Q, P)) and `pair_index`
+    ((P, 2): the groups g < h of pair p, in the order (0,1), (0,2), ..., (G-2,G-1))."""
+    stats, pairs = np.asarray(stats), np.asarray(pairs)
+    q, ng = stats.shape
+    n = [int(x) for x in np.asarray(group_sizes).reshape(-1)]
+    nan = np.full((q, ng), np.nan)
+    pi, theta, taj, het = nan.copy(), nan.copy(), nan.copy(), nan.copy()
+    big = q > 0 and int(stats["rows"].max()) >= 1 << 31   # (only then can a numerator leave 64 bits: Python integers instead)
+    wide = (lambda a: a.astype(object)) if big else (lambda a: a.astype(np.uint64))
+    sum_ac, sum_ac2 = wide(stats["sum_ac"]), wide(stats["sum_ac2"])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for g in range(ng):
+            cn = 2 * n[g]
+            rows = stats["rows"][:, g].astype(np.float64)
+            if n[g]:
+                het[:, g] = np.where(rows > 0, stats["obs_het"][:, g].astype(np.float64) / (rows * float(n[g])), np.nan)
+            if cn < 2:
+                continue
+            num = (int(cn) if big else np.uint64(cn)) * sum_ac[:, g] - sum_ac2[:, g]
+            pi[:, g] = 2.0 * num.astype(np.float64) / float(cn * (cn - 1))
+            a1 = math.fsum(1.0 / i for i in range(1, cn))
+            s = stats["seg"][:, g].astype(np.float64)
+            theta[:, g] = s / a1
+            if cn < 4:
+                continue
+            a2 = math.fsum(1.0 / (i * i) for i in range(1, cn))
+            b1 = (cn + 1) / (3.0 * (cn - 1))
+            b2 = 2.0 * (cn * cn + cn + 3) / (9.0 * cn * (cn - 1))
+            c1 = b1 - 1.0 / a1
+            c2 = b2 - (cn + 2) / (a1 * cn) + a2 / (a1 * a1)
+            e1 = c1 / a1
+            e2 = c2 / (a1 * a1 + a2)
+            var = e1 * s + e2 * s * (s - 1.0)
+            taj[:, g] = np.where((s > 0) & (var > 0), (pi[:, g] - theta[:, g]) / np.sqrt(var), np.nan)
+        pair_index = np.array([(g, h) for g in range(ng) for h in range(g + 1, ng)], dtype=np.uint32).reshape(-1, 2)
+        npair = pairs.shape[1] if pairs.ndim == 2 else 0
+        dxy, fst = np.full((q, npair), np.nan), np.full((q, npair), np.nan)
+        if npair:
+            cross = wide(pairs["sum_cross"])
+            for p, (g, h) in enumerate(pair_index.tolist()):
+                ng_, nh_ = 2 * n[g], 2 * n[h]
+                if not ng_ or not nh_:
+                    continue
+                cg, ch = (int(nh_), int(ng_)) if big else (np.uint64(nh_), np.uint64(ng_))
+                num = cg * sum_ac[:, g] + ch * sum_ac[:, h] - (2 if big else np.uint64(2)) * cross[:, p]
+                dxy[:, p] = num.astype(np.float64) / float(ng_ * nh_)
+                fst[:, p] = np.where(dxy[:, p] > 0, 1.0 - ((pi[:, g] + pi[:, h]) / 2.0) / dxy[:, p], np.nan)
+    out = {"pi": pi, "theta_w": theta, "tajima_d": taj, "het_obs": het, "dxy": dxy, "fst_hudson": fst,
+           "pair_index": pair_index if npair else np.zeros((0, 2), np.uint32)}
+    if lengths is not None:
+        ln = np.asarray(lengths, dtype=np.float64).reshape(-1)
+        if ln.shape[0] != q:
+            raise ValueError(f"{ln.shape[0]} window lengths for {q} regions")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["pi_per_bp"] = pi / ln[:, None]
+    return out
+
+
 def _regions_array(regions):
     if isinstance(regions, DeviceArray):
         return regions, C.cast(C.c_void_p(regions.ptr), C.POINTER(Region)), regions.n
@@ -324,6 +405,59 @@ class QueryResult:
         p = C.c_void_p()
         _check(self._lib.vs_result_group_counts_device(self._h, C.byref(n), C.byref(g), C.byref(p)), "vs_result_group_counts_device")
         return int(p.value or 0), int(n.value), int(g.value)
+
+    WINDOW_DTYPE = np.dtype([("rows", "<u4"), ("seg", "<u4"), ("singletons", "<u4"), ("doubletons", "<u4"), ("private", "<u4"),
+                             ("fixed", "<u4"), ("sum_ac", "<u8"), ("sum_ac2", "<u8"), ("obs_het", "<u8")])   # vs_window_stats
+    WINDOW_PAIR_DTYPE = np.dtype([("sum_cross", "<u8"), ("seg_union", "<u4"), ("fixed_diff", "<u4")])     # vs_window_pair_stats
+
+    def window_stats(self, lengths=None):
+        """A window-statistics result (VariantStore.window_stats) as numpy arrays: `stats` (structured WINDOW_DTYPE, shape (Q, G):
+        stats[q, g] is region q over group g -- rows, seg, singletons, doubletons, private, fixed, sum_ac, sum_ac2, obs_het),
+        `pairs` (structured WINDOW_PAIR_DTYPE, shape (Q, P): sum_cross, seg_union, fixed_diff; P = 0 without pair records),
+        `pair_index` ((P, 2): the groups g < h of pair p), `group_sizes` (uint32[G], samples), `group_names` (list of G strings),
+        the regions' `flags`, `row_begin` and `row_count`, and the quantities window_stats_derived forms from the exact integers in
+        float64 -- `pi`, `theta_w`, `tajima_d`, `het_obs` (each (Q, G)), `dxy`, `fst_hudson` (each (Q, P)) and, with `lengths` (Q
+        window lengths in bp), `pi_per_bp`: the formulas are written out there.  Copies, valid after the result is closed."""
+        nq, g, p = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        sizes = C.POINTER(C.c_uint32)()
+        names = C.POINTER(C.c_char_p)()
+        ps, pp = C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_get_window_stats(self._h, C.byref(nq), C.byref(g), C.byref(p), C.byref(sizes), C.byref(names), C.byref(ps),
+                                                    C.byref(pp)), "vs_result_get_window_stats")
+        q, ng, npair = int(nq.value), int(g.value), int(p.value)
+        stats = np.ctypeslib.as_array(C.cast(ps, C.POINTER(C.c_uint8)), shape=(q * ng * 48,)).view(self.WINDOW_DTYPE).copy().reshape(q, ng)
+        pairs = (np.ctypeslib.as_array(C.cast(pp, C.POINTER(C.c_uint8)), shape=(q * npair * 16,)).view(self.WINDOW_PAIR_DTYPE).copy()
+                 if npair else np.zeros(0, self.WINDOW_PAIR_DTYPE)).reshape(q, npair)
+        group_sizes = np.ctypeslib.as_array(sizes, shape=(ng,)).copy()
+        raw = self.raw(with_carriers=False)
+        out = {"stats": stats, "pairs": pairs, "group_sizes": group_sizes,
+               "group_names": [names[i].decode() for i in range(ng)] if names else [str(i) for i in range(ng)],
+               "flags": raw["region_flags"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy()}
+        out.update(window_stats_derived(stats, pairs, group_sizes, lengths))
+        return out
+
+    def region_window_stats(self, q, stats=None):
+        """Region q of a window-statistics result: a dict of views into `stats` (window_stats() of this result; taken now when
+        None) -- `stats` (G records), `pairs` (P records) and the region's row of every derived quantity."""
+        got = self.window_stats() if stats is None else stats
+        q = int(q)
+        if not 0 <= q < got["stats"].shape[0]:
+            raise IndexError(f"region {q} of {got['stats'].shape[0]}")
+        keys = ("stats", "pairs", "pi", "pi_per_bp", "theta_w", "tajima_d", "het_obs", "dxy", "fst_hudson")
+        out = {k: got[k][q] for k in keys if k in got}
+        out["pair_index"], out["group_sizes"], out["group_names"] = got["pair_index"], got["group_sizes"], got["group_names"]
+        return out
+
+    def window_stats_device(self):
+        """A window-statistics result as it lies in this GPU's memory: a dict of the addresses `stats` (n_regions x n_groups records
+        of 48 bytes) and `pairs` (n_regions x n_pairs records of 16 bytes; 0 without), with `n_regions`, `n_groups` and `n_pairs`;
+        complete when this returns and valid until the result is closed."""
+        nq, g, p = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        ps, pp = C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_window_stats_device(self._h, C.byref(nq), C.byref(g), C.byref(p), C.byref(ps), C.byref(pp)),
+               "vs_result_window_stats_device")
+        return {"stats": int(ps.value or 0), "pairs": int(pp.value or 0), "n_regions": int(nq.value), "n_groups": int(g.value),
+                "n_pairs": int(p.value)}
 
     ASSOC_STATS = {"dot": 0, "chi2": 1}   # VS_ASSOC_DOT, VS_ASSOC_CHI2
 
@@ -1197,6 +1331,19 @@ class VariantStore:
         group.  `groups`: a dict name -> iterable of samples (names or ids; dict order is group order), or a sequence of such
         iterables, named "0", "1", ...  A sample that is listed nowhere belongs to no group; a group may be empty.  `regions` as
         for allele_counts.  Read the result with QueryResult.group_counts / region_group_counts / group_counts_device / region_text."""
+        names, members, ids, gof = self._groups_arg(groups)
+        arr, ptr, n = _regions_array(regions)
+        name_arr = (C.c_char_p * len(names))(*[s.encode() for s in names]) if names is not None else None
+        h = C.c_void_p()
+        _check(self._lib.vs_query_group_counts(self._h, ptr, n, ids.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                               gof.ctypes.data_as(C.POINTER(C.c_uint32)), ids.shape[0], len(members), name_arr,
+                                               C.byref(h)), "vs_query_group_counts")
+        res = QueryResult(self, h)
+        res.group_names = names if names is not None else [str(i) for i in range(len(members))]
+        return res
+
+    def _groups_arg(self, groups):
+        """(names or None, members, ids, group_of) of a grouped query's `groups`: a dict name -> samples or a sequence of sample lists."""
         if isinstance(groups, dict):
             names, members = [str(k) for k in groups], list(groups.values())
         else:
@@ -1211,14 +1358,29 @@ class VariantStore:
                 gof.append(g)
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         gof = np.ascontiguousarray(gof, dtype=np.uint32)
+        return names, members, ids, gof
+
+    def window_stats(self, regions, groups=None, pairs=True) -> QueryResult:
+        """Windowed diversity statistics over regions (vs_query_window_stats): per region and group the exact integers nucleotide
+        diversity pi, segregating sites, Watterson's theta, Tajima's D, private alleles and fixed sites are formed from, and with
+        `pairs` per pair of groups those of dxy, Hudson's Fst, shared segregating sites and fixed differences -- the reduction of
+        group_counts' records done on the GPU, a few dozen bytes per window and group instead of 16 bytes per row and group.
+        `groups` as for group_counts, or None: the whole cohort as one group.  `regions` as for allele_counts (a list, an array or
+        a DeviceArray).  Read the result with QueryResult.window_stats (which also forms pi, theta_w, tajima_d, het_obs, dxy and
+        fst_hudson) / region_window_stats / window_stats_device / region_text."""
         arr, ptr, n = _regions_array(regions)
-        name_arr = (C.c_char_p * len(names))(*[s.encode() for s in names]) if names is not None else None
         h = C.c_void_p()
-        _check(self._lib.vs_query_group_counts(self._h, ptr, n, ids.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                               gof.ctypes.data_as(C.POINTER(C.c_uint32)), ids.shape[0], len(members), name_arr,
-                                               C.byref(h)), "vs_query_group_counts")
+        if groups is None:
+            names, n_groups, ids_ptr, gof_ptr, n_ids, name_arr = None, 1, None, None, 0, None
+        else:
+            names, members, ids, gof = self._groups_arg(groups)
+            n_groups, n_ids = len(members), ids.shape[0]
+            ids_ptr, gof_ptr = ids.ctypes.data_as(C.POINTER(C.c_uint32)), gof.ctypes.data_as(C.POINTER(C.c_uint32))
+            name_arr = (C.c_char_p * len(names))(*[s.encode() for s in names]) if names is not None else None
+        _check(self._lib.vs_query_window_stats(self._h, ptr, n, ids_ptr, gof_ptr, n_ids, n_groups, name_arr, 1 if pairs else 0, C.byref(h)),
+               "vs_query_window_stats")
         res = QueryResult(self, h)
-        res.group_names = names if names is not None else [str(i) for i in range(len(members))]
+        res.group_names = names if names is not None else [str(i) for i in range(n_groups)]
         return res
 
     def _sample_set(self, samples):

@@ -126,6 +126,7 @@ struct Args {
   bool ibs_have_min = false;
   double ibs_min_kinship = 0.0;
   bool assoc_chi2 = false;   // `assoc`: the score test instead of the dot products
+  bool windows_no_pairs = false, windows_derived = false;   // `windows`: no pair records; pi, theta, Tajima's D, dxy and Fst beside the integers
   uint32_t type = 0, mode = 0;
   uint64_t hops = 0;
   bool have_hops = false;
@@ -746,13 +747,69 @@ int groups_usage() {
   return EXIT_FAILURE;
 }
 
-int groups_main(const Args& a) {
+// `variantstore windows`: the diversity statistics of every region (vs_query_window_stats) per sample group and pair of groups.  The -G
+// file is `groups`'s; without it the whole cohort is one group.  Output as `counts`: "#region <i> <x>:<y>", then the region's text
+// ("Group N Rows Seg Singletons Doubletons Private Fixed SumAC SumAC2 ObsHet", a line per group, then "GroupA GroupB SumCross SegUnion
+// FixedDiff", a line per pair).  --derived: each group line gains Pi ThetaW TajimaD and each pair line Dxy Fst.
+int windows_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore windows -p <output-prefix> -r <region> [-G <sample-group-file>] [--no-pairs] [--derived] [-o <outfile>]\n"
+               "                             [--device <n>]\n\n"
+               "        For every region (window) and every group of samples -- the file holds one `sample group` pair per line as\n"
+               "        for `groups`; without it the whole cohort is one group -- the integers of the windowed diversity statistics:\n"
+               "        sites, segregating sites, singletons, doubletons, private and fixed alleles, the sums of the alternate-allele\n"
+               "        counts and of their squares, heterozygous calls; and for every pair of groups (unless --no-pairs) the sum of\n"
+               "        the products of their counts, sites segregating in either, fixed differences.  --derived adds nucleotide\n"
+               "        diversity pi, Watterson's theta and Tajima's D per group and dxy and Hudson's Fst per pair (nan: undefined).\n";
+  return EXIT_FAILURE;
+}
+
+// pi, theta_w and Tajima's D of a record over a group of n samples (N = 2 n allele copies), and dxy of a pair: the formulas of the
+// Python accessor (window_stats_derived), in double from exact integers.
+struct WindowDerived { double pi, theta, tajima; };
+WindowDerived window_derived(const vs_window_stats& w, uint32_t n) {
+  const double nan = std::nan("");
+  WindowDerived d{nan, nan, nan};
+  const uint64_t N = 2ull * n;
+  if (N < 2) return d;
+  const unsigned __int128 num = (unsigned __int128)N * w.sum_ac - w.sum_ac2;
+  d.pi = 2.0 * (double)num / (double)(N * (N - 1));
+  double a1 = 0.0, a2 = 0.0;
+  for (uint64_t i = 1; i < N; ++i) { a1 += 1.0 / (double)i; a2 += 1.0 / ((double)i * (double)i); }
+  const double S = (double)w.seg;
+  d.theta = S / a1;
+  if (N < 4 || w.seg == 0) return d;
+  const double dn = (double)N;
+  const double b1 = (dn + 1) / (3.0 * (dn - 1)), b2 = 2.0 * (dn * dn + dn + 3) / (9.0 * dn * (dn - 1));
+  const double c1 = b1 - 1.0 / a1, c2 = b2 - (dn + 2) / (a1 * dn) + a2 / (a1 * a1);
+  const double e1 = c1 / a1, e2 = c2 / (a1 * a1 + a2);
+  const double var = e1 * S + e2 * S * (S - 1.0);
+  if (var > 0) d.tajima = (d.pi - d.theta) / std::sqrt(var);
+  return d;
+}
+double window_dxy(const vs_window_stats& g, const vs_window_stats& h, const vs_window_pair_stats& p, uint32_t n_g, uint32_t n_h) {
+  const uint64_t Ng = 2ull * n_g, Nh = 2ull * n_h;
+  if (!Ng || !Nh) return std::nan("");
+  const unsigned __int128 num = (unsigned __int128)Nh * g.sum_ac + (unsigned __int128)Ng * h.sum_ac - 2 * (unsigned __int128)p.sum_cross;
+  return (double)num / (double)(Ng * Nh);
+}
+std::string g10(double v) {
+  if (std::isnan(v)) return "nan";
+  char buf[48];
+  snprintf(buf, sizeof buf, "%.10g", v);
+  return buf;
+}
+
+int groups_main(const Args& a, bool windows = false) {
   vs_index* idx = nullptr;
   int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
   if (rc != VS_OK) die(rc, "load");
   auto fail_with = [&](const std::string& msg) { error(msg); vs_index_close(idx); return EXIT_FAILURE; };
-  std::ifstream in(a.groups_file);
-  if (!in) return fail_with("cannot open group file " + a.groups_file);
+  std::ifstream in;
+  if (!windows || !a.groups_file.empty()) {
+    in.open(a.groups_file);
+    if (!in) return fail_with("cannot open group file " + a.groups_file);
+  }
   std::vector<uint32_t> ids, group_of;
   std::vector<std::string> names;
   std::map<uint32_t, uint32_t> seen;   // sample id -> its group
@@ -779,14 +836,24 @@ int groups_main(const Args& a) {
     ids.push_back(sid);
     group_of.push_back(g);
   }
-  if (ids.empty()) return fail_with("no sample-group pairs in " + a.groups_file);
+  if (ids.empty() && (!windows || !a.groups_file.empty())) return fail_with("no sample-group pairs in " + a.groups_file);
   std::vector<const char*> name_ptrs;
   for (auto& n : names) name_ptrs.push_back(n.c_str());
   std::vector<vs_region> batch;
   for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
   vs_result* res = nullptr;
-  rc = vs_query_group_counts(idx, batch.data(), batch.size(), ids.data(), group_of.data(), ids.size(), (uint32_t)names.size(), name_ptrs.data(), &res);
-  if (rc != VS_OK) die(rc, "groups");
+  if (!windows) rc = vs_query_group_counts(idx, batch.data(), batch.size(), ids.data(), group_of.data(), ids.size(), (uint32_t)names.size(), name_ptrs.data(), &res);
+  else if (ids.empty()) rc = vs_query_window_stats(idx, batch.data(), batch.size(), nullptr, nullptr, 0, 1, nullptr, a.windows_no_pairs ? 0 : 1, &res);
+  else rc = vs_query_window_stats(idx, batch.data(), batch.size(), ids.data(), group_of.data(), ids.size(), (uint32_t)names.size(), name_ptrs.data(), a.windows_no_pairs ? 0 : 1, &res);
+  if (rc != VS_OK) die(rc, windows ? "windows" : "groups");
+  uint32_t G = 0, P = 0;
+  const uint32_t* sizes = nullptr;
+  const vs_window_stats* ws = nullptr;
+  const vs_window_pair_stats* wp = nullptr;
+  if (windows && a.windows_derived) {
+    rc = vs_result_get_window_stats(res, nullptr, &G, &P, &sizes, nullptr, &ws, &wp);
+    if (rc != VS_OK) die(rc, "result");
+  }
   std::ofstream file;
   if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
   std::ostream& out = a.outfile.empty() ? std::cout : file;
@@ -796,7 +863,30 @@ int groups_main(const Args& a) {
     rc = vs_result_format_region(res, i, &text, &len);
     if (rc != VS_OK) die(rc, "result");
     out << "#region " << i << " " << batch[i].x << ":" << batch[i].y << "\n";
-    out.write(text, len);
+    if (!ws) { out.write(text, len); continue; }
+    // --derived: the same lines, each with its columns appended (line 0: the group header, then G groups, the pair header, P pairs)
+    const std::string body(text, len);
+    std::vector<WindowDerived> d(G);
+    for (uint32_t g = 0; g < G; ++g) d[g] = window_derived(ws[i * G + g], sizes[g]);
+    std::vector<std::pair<uint32_t, uint32_t>> gh;
+    for (uint32_t g = 0; g < G; ++g)
+      for (uint32_t h = g + 1; h < G; ++h) gh.emplace_back(g, h);
+    size_t at = 0;
+    for (uint32_t ln = 0; at < body.size(); ++ln) {
+      const size_t nl = body.find('\n', at);
+      out.write(body.data() + at, nl - at);
+      if (ln == 0) out << "\tPi\tThetaW\tTajimaD";
+      else if (ln <= G) out << '\t' << g10(d[ln - 1].pi) << '\t' << g10(d[ln - 1].theta) << '\t' << g10(d[ln - 1].tajima);
+      else if (ln == G + 1) out << "\tDxy\tFst";
+      else {
+        const uint32_t p = ln - G - 2, g = gh[p].first, h = gh[p].second;
+        const double dxy = window_dxy(ws[i * G + g], ws[i * G + h], wp[i * P + p], sizes[g], sizes[h]);
+        const double fst = dxy > 0 ? 1.0 - ((d[g].pi + d[h].pi) / 2.0) / dxy : std::nan("");
+        out << '\t' << g10(dxy) << '\t' << g10(fst);
+      }
+      out << '\n';
+      at = nl + 1;
+    }
   }
   out.flush();
   vs_result_free(res);
@@ -1387,7 +1477,7 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "prune" || a.cmd == "clump" || a.cmd == "ldscore" || a.cmd == "groups" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "prune" || a.cmd == "clump" || a.cmd == "ldscore" || a.cmd == "groups" || a.cmd == "windows" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if ((a.cmd == "burden" || a.cmd == "prune" || a.cmd == "ldscore") && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if ((a.cmd == "burden" || a.cmd == "prune" || a.cmd == "ldscore") && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
@@ -1419,11 +1509,13 @@ int main(int argc, char** argv) {
         a.ibs_have_min = true;
       }
       else if (f == "-r" || f == "--region") a.region = need(i);
-      else if (a.cmd == "groups" && (f == "-G" || f == "--groups")) a.groups_file = need(i);
+      else if ((a.cmd == "groups" || a.cmd == "windows") && (f == "-G" || f == "--groups")) a.groups_file = need(i);
+      else if (a.cmd == "windows" && f == "--no-pairs") a.windows_no_pairs = true;
+      else if (a.cmd == "windows" && f == "--derived") a.windows_derived = true;
       else if ((a.cmd == "assoc" || a.cmd == "assocmatrix") && (f == "-P" || f == "--phenotypes")) a.pheno_file = need(i);
       else if ((a.cmd == "assoc" || a.cmd == "assocmatrix") && f == "--chi2") a.assoc_chi2 = true;
       else if ((a.cmd == "score" || a.cmd == "scorematrix") && (f == "-W" || f == "--weights")) a.weights_file = need(i);
-      else if (a.cmd != "groups" && a.cmd != "assoc" && a.cmd != "assocmatrix" && (f == "-S" || f == "--samples")) a.samples_file = need(i);
+      else if (a.cmd != "groups" && a.cmd != "windows" && a.cmd != "assoc" && a.cmd != "assocmatrix" && (f == "-S" || f == "--samples")) a.samples_file = need(i);
       else if (f == "-o" || f == "--output_file") a.outfile = need(i);
       else if (f == "--device") a.device = atoi(need(i).c_str());
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
@@ -1436,6 +1528,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "groups") {
     if (a.prefix.empty() || a.region.empty() || a.groups_file.empty()) return groups_usage();
     return groups_main(a);
+  }
+  if (a.cmd == "windows") {
+    if (a.prefix.empty() || a.region.empty()) return windows_usage();
+    return groups_main(a, /*windows=*/true);
   }
   if (a.cmd == "assocmatrix") {
     if (a.prefix.empty() || a.region.empty() || a.pheno_file.empty()) return assocmatrix_usage();

@@ -88,6 +88,7 @@ struct EngineOpts {
   bool fill_fused = true;       // shared batches: the expansion writes the shared rows as well (k_fill_sites2); false: k_share_rows2 + k_fill_sites
   uint32_t fill_chunk = 0;      // rows per task of the expansion: 0 = by the batch's shape, else 8 / 16 / 32 / 64
   uint32_t burden_chunk = 0;    // rows one workgroup of the burden kernel walks before a region is split: 0 = kBurdenChunkRows
+  uint32_t window_chunk = 0;    // rows one wave of the window-statistics kernel walks before a region is split: 0 = kWinChunkRows
   uint32_t matrix_max_mib = 0;  // largest genotype matrix a batch may ask for, MiB: 0 = 32 GiB
   uint32_t assoc_lds_max_kib = 0;   // largest phenotype table k_assoc_scan stages in LDS, KiB: 0 = 32; a larger one is read through global memory
   uint32_t score_chunk = 0;     // table rows one workgroup of k_sample_scores walks: 0 = kScoreChunkRows, else 64..65536
@@ -248,7 +249,8 @@ struct vs_result {
                  // kKindBurden: per-sample burden; kKindMatrix: genotype matrix; kKindLd: banded LD; kKindGroups: grouped allele counts; kKindAssoc: association scan;
                  // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM; kKindIbs: pairwise IBS counts / KING kinship;
                  // kKindLdMatrix: the full LD block of every region; kKindAssocMatrix: trait-matrix association scan;
-                 // kKindScoreMatrix: score matrix; kKindPrune: LD pruning verdicts; kKindClump: p-value clumping verdicts; kKindLdScore: LD scores
+                 // kKindScoreMatrix: score matrix; kKindPrune: LD pruning verdicts; kKindClump: p-value clumping verdicts; kKindLdScore: LD scores;
+                 // kKindWindowStats: windowed diversity statistics
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -322,6 +324,13 @@ struct vs_result {
   // prune_min_ac and prune_max_ac as for a pruning result; ldscore_wgs: the score kernel's workgroups
   uint8_t* d_ldscore = nullptr;
   uint64_t ldscore_wgs = 0;
+  // window-statistics results (vs_query_window_stats): one buffer in HBM (d_wstats) -- Q x n_groups records of 48 bytes, then
+  // Q x ws_pairs pair records of 16 bytes (ws_pairs: n_groups (n_groups - 1) / 2, or 0 without pairs) --, copied to cells_pin in one
+  // piece; n_groups, group_sizes and group_names as for a grouped-count result; the chunks of the split regions in d_cell_total's
+  // second word.  The grouped counts the records are reduced from are a temporary of the call
+  uint8_t* d_wstats = nullptr;
+  uint32_t ws_pairs = 0;
+  std::vector<const char*> ws_name_ptrs;   // group_names as the array of C strings vs_result_get_window_stats hands out
   // clumping results (vs_query_ld_clump): d_state, d_prune_meta, prune_states, ld_window, prune_max_bp and prune_T as for a pruning
   // result -- the words are keep_begin [Q + 1], n_index [Q + 1, the last unused], the scan's summary, d_cell_total, then the rounds
   // every region took [Q + 1, the last unused] --, an owner per verdict beside the state (d_owner, its page-locked copy owner_pin),
@@ -369,9 +378,10 @@ constexpr int kKindAssocMatrix = 18;   // ... of a trait-matrix association resu
 constexpr int kKindScoreMatrix = 19;   // ... of a score-matrix result: the rows of type 6, a columns x scores matrix of weighted dosage sums (up to VS_SCORE_MATRIX_MAX scores) instead of carrier lists
 constexpr int kKindPrune = 20;   // ... of a pruning result: the rows of type 6, a verdict byte per reported row instead of carrier lists
 constexpr int kKindLdScore = 22;   // ... of an LD-score result: the rows of type 6, a sum, a pair count and a state byte per reported row instead of carrier lists
+constexpr int kKindWindowStats = 23;   // ... of a window-statistics result: the rows of type 6, a record per region and sample group (and pair of groups) instead of carrier lists
 constexpr int kKindClump = 21;   // ... of a clumping result: the rows of type 6, a verdict byte and an owner per reported row instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindLdScore || r->kind == kKindClump || r->kind == kKindPrune || r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
+  return r->kind == kKindWindowStats || r->kind == kKindLdScore || r->kind == kKindClump || r->kind == kKindPrune || r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
          r->kind == kKindScores;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
@@ -394,6 +404,8 @@ static int refuse_no_lists(const vs_result* r, const char* what) {
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD-matrix result holds a square block of pair statistics per region, no carrier lists (vs_result_get_ld_matrix)", what);
   if (r->kind == kKindClump)
     return fail(VS_ERR_UNSUPPORTED, "%s: a clumping result holds a verdict and an owner per reported row, no carrier lists (vs_result_get_ld_clump)", what);
+  if (r->kind == kKindWindowStats)
+    return fail(VS_ERR_UNSUPPORTED, "%s: a window-statistics result holds a record per region and group, no carrier lists (vs_result_get_window_stats)", what);
   if (r->kind == kKindLdScore)
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD-score result holds a sum of r2 per reported row, no carrier lists (vs_result_get_ld_scores)", what);
   if (r->kind == kKindPrune)
@@ -1267,7 +1279,8 @@ static int capture_totals(vs_result* r) {
 // Clump: as Prune without the allele-count window; `clump_keys` (host memory, owned by the result), n_pvalues of them, held against
 // the number of table rows once the plan has given it; clump_key: the keys of p1 and p2.
 // LdScore: as Prune without the threshold; ld_window = 0 stands for no row limit.
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix, Prune, Clump, LdScore };
+// WindowStats: mask and n_cols as for Groups; ws_sizes: the groups' sizes (n_cols of them), ws_pairs: the pair records (0: none).
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix, Prune, Clump, LdScore, WindowStats };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1287,6 +1300,8 @@ struct SharedReq {
   uint32_t n_scores = 0, score_max_bits[kScoresMax] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool weights_on_device = false;
   const std::vector<int32_t>* sm_shift = nullptr;
+  const uint32_t* ws_sizes = nullptr;
+  uint32_t ws_pairs = 0;
   bool window() const { return min_ac != 0 || max_ac != UINT32_MAX; }
 };
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
@@ -1704,6 +1719,7 @@ struct SharedCtx {
   bool async_fill = false, fused = false, lean = false;
   uint32_t* u_site = nullptr;   // shared_rows: the site of every shared row (a column request: of every row)
   uint8_t* ld_matrix = nullptr; // shared_tables: the temporary genotype matrix of an LD batch (ld_tmp); an LD-matrix batch: ld_matrix_tables
+  uint4* ws_counts = nullptr;   // shared_tables: a window-statistics batch's temporary grouped counts (ld_tmp)
   uint32_t* prune_hits = nullptr;   // prune_tables: a pruning batch's hit masks (ld_tmp)
   uint64_t* clump_keys = nullptr;   // clump_tables: a clumping batch's keys, classes and blocker masks (ld_tmp)
   uint8_t* clump_cls = nullptr;
@@ -1711,7 +1727,7 @@ struct SharedCtx {
   uint64_t* am_dev = nullptr;   // shared_tables: a trait-matrix batch's Sy, vy, shifts and limb panel on the device (ld_tmp)
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix || q.kind == ReqKind::Prune || q.kind == ReqKind::Clump || q.kind == ReqKind::LdScore) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix || q.kind == ReqKind::Prune || q.kind == ReqKind::Clump || q.kind == ReqKind::LdScore || q.kind == ReqKind::WindowStats) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -1909,6 +1925,20 @@ static int group_counts_fit(SharedCtx& c) {
   return fail(VS_ERR_ARG, "grouped counts of %llu rows x %u groups take %llu bytes, more than the limit of %llu MiB (option matrix_max_mib): split the batch",
               (unsigned long long)r->d.A, c.req.n_cols, (unsigned long long)(r->d.A * row_bytes), (unsigned long long)(cap >> 20));
 }
+// A window-statistics batch: the temporary grouped counts (rows x groups x 16 bytes) and the answer (regions x (48 groups + 16 pairs)
+// bytes) together, under the same limit, before either or the table is allocated.
+static int window_stats_fit(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  const uint64_t row_bytes = 16ull * c.req.n_cols, region_bytes = 48ull * c.req.n_cols + 16ull * c.req.ws_pairs;   // (at most 1 KiB and 35 KiB)
+  if (r->d.Q <= cap / region_bytes && r->d.A <= (cap - r->d.Q * region_bytes) / row_bytes) return VS_OK;
+  (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+  (void)hipStreamSynchronize(idx->stream);
+  return fail(VS_ERR_ARG, "the window statistics of %llu regions over %llu rows x %u groups take %llu bytes (%llu of the grouped counts they are reduced from, "
+              "%llu of the records), more than the limit of %llu MiB (option matrix_max_mib): split the batch", (unsigned long long)r->d.Q, (unsigned long long)r->d.A,
+              c.req.n_cols, (unsigned long long)(r->d.A * row_bytes + r->d.Q * region_bytes), (unsigned long long)(r->d.A * row_bytes),
+              (unsigned long long)(r->d.Q * region_bytes), (unsigned long long)(cap >> 20));
+}
 // The plan's rows are known: an association scan beyond the limit (rows x traits cells of 8 bytes and the rows' count records) is
 // refused here, before they or the table are allocated.
 static int assoc_fits(SharedCtx& c) {
@@ -2072,6 +2102,14 @@ static int shared_tables(SharedCtx& c) {
       VS_TRY(group_counts_fit(c));
       VS_TRY(ralloc(r, d.A, &d.rows));
       VS_TRY(ralloc(r, (size_t)(d.A * q.n_cols), &r->d_counts));
+      break;
+    case ReqKind::WindowStats:   // (the grouped counts are a temporary like an LD batch's matrix: the reduction alone reads them)
+      VS_TRY(window_stats_fit(c));
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(dev_alloc(idx, (size_t)(d.A * q.n_cols) * sizeof(uint4), (void**)&c.ws_counts, &c.ld_tmp.bufs));
+      VS_TRY(ralloc(r, (size_t)d.Q * (48 * (size_t)q.n_cols + 16 * (size_t)q.ws_pairs), &r->d_wstats));
+      VS_TRY(ralloc(r, 2, &r->d_cell_total));   // (the second word: the number of chunks of the split regions)
+      r->ws_pairs = q.ws_pairs;
       break;
     case ReqKind::Assoc:
       VS_TRY(assoc_fits(c));
@@ -2303,6 +2341,7 @@ static int clump_tables(SharedCtx& c);
 static int launch_clump(SharedCtx& c);
 static int ldscore_tables(SharedCtx& c);
 static int launch_ldscore(SharedCtx& c);
+static int launch_window_stats(SharedCtx& c);
 static int shared_columns(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
   if (!c.behind_perm && !r->d.A) return VS_OK;
@@ -2314,7 +2353,10 @@ static int shared_columns(SharedCtx& c) {
   VS_TRY(result_events(r));
   HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
   if (c.req.kind == ReqKind::Groups) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, r->d_counts);
-  else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD, Gram, Ibs, ScoreMatrix; Burden only under a window: shared_tables gives it counts)
+  else if (c.req.kind == ReqKind::WindowStats) {   // (a table without rows: no group kernel, the records are zeros all the same)
+    if (r->d.A) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, c.ws_counts);
+    VS_TRY(launch_window_stats(c));
+  } else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD, Gram, Ibs, ScoreMatrix; Burden only under a window: shared_tables gives it counts)
     launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
   HIP_TRY(hipGetLastError());
   if (c.req.kind == ReqKind::Assoc) VS_TRY(launch_assoc(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.d_pheno, c.req));
@@ -2349,6 +2391,52 @@ static int shared_columns(SharedCtx& c) {
   HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
   r->pending = true;
   c.fill_launches = 1;
+  return VS_OK;
+}
+
+// The records of a window-statistics batch behind the permutation (the per-region arrays are in the caller's order) from the temporary
+// grouped counts: k_window_stats, a wave per region, and -- only when the rows all regions report could hold a region longer than a
+// chunk -- the device-built list of such regions' chunks (k_burden_split_plan) and the SPLIT launch that adds them.
+template <uint32_t NPB>
+static void launch_window_kernels(vs_index* idx, const WindowArgs& a, uint32_t cap, size_t lds) {
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_window_stats<NPB, false>), dim3((unsigned)((a.Q + 3) / 4)), dim3(256), lds, idx->stream, a);
+  if (cap) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_window_stats<NPB, true>), dim3(cap), dim3(256), lds, idx->stream, a);
+}
+static int launch_window_stats(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  const SharedReq& q = c.req;
+  WindowArgs a{};
+  a.gc = c.ws_counts; a.rows = (const VariantRow*)d.rows; a.U = c.U; a.var_begin = d.var_begin; a.q_nvar = d.q_nvar; a.Q = d.Q;
+  a.G = q.n_cols; a.P = q.ws_pairs;
+  a.chunk_rows = idx->opts.window_chunk ? idx->opts.window_chunk : kWinChunkRows;
+  a.rec = reinterpret_cast<uint32_t*>(r->d_wstats);
+  a.pair = reinterpret_cast<uint4*>(r->d_wstats + (size_t)d.Q * 48 * q.n_cols);
+  for (uint32_t g = 0; g < q.n_cols; ++g) a.gsize[g] = (uint16_t)q.ws_sizes[g];   // (at most 32,767 samples in all)
+  uint32_t* n_work = reinterpret_cast<uint32_t*>(r->d_cell_total + 1);
+  a.n_work = n_work;
+  if (d.Q > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu regions)", (unsigned long long)d.Q);
+  HIP_TRY(hipMemsetAsync(r->d_cell_total, 0, 16, idx->stream));
+  // every split region has more than chunk_rows rows, so its chunks number less than twice its rows / chunk_rows
+  const uint64_t cap64 = r->n_rows_reported > a.chunk_rows ? 2 * r->n_rows_reported / a.chunk_rows : 0;
+  if (cap64 > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu row chunks)", (unsigned long long)cap64);
+  const uint32_t cap = (uint32_t)cap64;
+  if (cap) {
+    uint2* work = nullptr;
+    VS_TRY(dev_alloc(idx, (size_t)cap * sizeof(uint2), (void**)&work, &c.scratch.bufs));
+    a.work = work;
+    hipLaunchKernelGGL(k_burden_split_plan, dim3((unsigned)((d.Q + 255) / 256)), dim3(256), 0, idx->stream, (const uint64_t*)d.q_nvar, d.Q, a.chunk_rows, work, n_work, cap);
+  }
+  const size_t lds = 4 * sizeof(uint32_t) * (size_t)window_cells(a.G);
+  const uint32_t batches = (a.P + 63) / 64;   // pairs a lane owns
+  if (batches == 0) launch_window_kernels<0>(idx, a, cap, lds);
+  else if (batches <= 1) launch_window_kernels<1>(idx, a, cap, lds);
+  else if (batches <= 2) launch_window_kernels<2>(idx, a, cap, lds);
+  else if (batches <= 4) launch_window_kernels<4>(idx, a, cap, lds);
+  else if (batches <= 8) launch_window_kernels<8>(idx, a, cap, lds);
+  else if (batches <= 16) launch_window_kernels<16>(idx, a, cap, lds);
+  else launch_window_kernels<32>(idx, a, cap, lds);
+  HIP_TRY(hipGetLastError());
   return VS_OK;
 }
 
@@ -4084,6 +4172,10 @@ int vs_index_set_option(vs_index* idx, const char* key, int64_t value) {
   } else if (k == "phase_events") o.phase_events = value != 0;
   else if (k == "force_fallbacks") o.force_fallbacks = value != 0;
   else if (k == "t6_speculate") o.t6_speculate = value != 0;
+  else if (k == "window_chunk") {
+    if (value != 0 && (value < 64 || value > 65536)) return fail(VS_ERR_ARG, "window_chunk takes 0 (default) or 64..65536 rows");
+    o.window_chunk = (uint32_t)value;
+  }
   else if (k == "burden_chunk") {
     if (value != 0 && (value < 64 || value > 65536)) return fail(VS_ERR_ARG, "burden_chunk takes 0 (default) or 64..65536 rows");
     o.burden_chunk = (uint32_t)value;
@@ -4233,28 +4325,40 @@ int vs_query_allele_counts(vs_index* idx, const vs_region* regions, uint64_t n, 
   return make_result(idx, kKindCounts, out, [&](vs_result* r) { return run_column_batch(idx, regions, n, r, req); });
 }
 
-int vs_query_group_counts(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, const uint32_t* group_of, uint64_t n_ids,
-                          uint32_t n_groups, const char* const* group_names, vs_result** out) {
+// The host's checks of a grouped batch, in the documented order, and what they leave: the label table (a byte per sample id), the
+// groups' sizes and names.  `whole` (window statistics): sample_ids == NULL with one group stands for the whole cohort; `pairs`: that
+// query's with_pairs, which may be 0 or 1.
+static int group_query_args(const vs_index* idx, const void* out, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, const uint32_t* group_of,
+                            uint64_t n_ids, uint32_t n_groups, const char* const* group_names, const char* batch, bool whole, uint32_t pairs,
+                            std::vector<uint64_t>& labels, std::vector<uint32_t>& sizes, std::vector<std::string>& names) {
   if (!idx || !out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
-  if (n == 0) return fail(VS_ERR_ARG, "a grouped-count batch needs at least one region");
-  if (!sample_ids || !group_of) return fail(VS_ERR_ARG, "null argument: a grouped-count batch takes sample ids and the group of each");
-  if (n_ids == 0) return fail(VS_ERR_ARG, "an empty list of samples: no group has a member");
-  if (n_groups == 0 || n_groups > VS_GROUPS_MAX) return fail(VS_ERR_ARG, "%u groups (1 .. %u)", n_groups, VS_GROUPS_MAX);
-  for (uint64_t i = 0; i < n_ids; ++i)
-    if (group_of[i] >= n_groups) return fail(VS_ERR_ARG, "group %u of sample id %u is out of range (%u groups)", group_of[i], sample_ids[i], n_groups);
-  const uint32_t ns = idx->g.num_samples;
-  for (uint64_t i = 0; i < n_ids; ++i)
-    if (sample_ids[i] == 0 || sample_ids[i] >= ns)
-      return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u is not a sample of the cohort (1 .. %u)", sample_ids[i], ns - 1);
-  std::vector<uint64_t> labels(((size_t)ns + 7) / 8, ~0ull);   // a byte per sample id: kGroupNone = in no group
-  uint8_t* lab = reinterpret_cast<uint8_t*>(labels.data());
-  std::vector<uint32_t> sizes(n_groups, 0);
-  for (uint64_t i = 0; i < n_ids; ++i) {
-    const uint32_t id = sample_ids[i], g = group_of[i];
-    if (lab[id] == kGroupNone) { lab[id] = (uint8_t)g; sizes[g]++; }
-    else if (lab[id] != g) return fail(VS_ERR_ARG, "sample id %u is listed in group %u and in group %u: a sample belongs to at most one group", id, (uint32_t)lab[id], g);
+  if (n == 0) return fail(VS_ERR_ARG, "%s batch needs at least one region", batch);
+  whole = whole && !sample_ids && n_groups == 1;
+  if (!whole) {
+    if (!sample_ids || !group_of) return fail(VS_ERR_ARG, "null argument: %s batch takes sample ids and the group of each", batch);
+    if (n_ids == 0) return fail(VS_ERR_ARG, "an empty list of samples: no group has a member");
   }
-  std::vector<std::string> names;
+  if (n_groups == 0 || n_groups > VS_GROUPS_MAX) return fail(VS_ERR_ARG, "%u groups (1 .. %u)", n_groups, VS_GROUPS_MAX);
+  if (pairs > 1) return fail(VS_ERR_ARG, "with_pairs is %u: 0 (no pair records) or 1", pairs);
+  const uint32_t ns = idx->g.num_samples;
+  labels.assign(((size_t)ns + 7) / 8, ~0ull);   // a byte per sample id: kGroupNone = in no group
+  uint8_t* lab = reinterpret_cast<uint8_t*>(labels.data());
+  sizes.assign(n_groups, 0);
+  if (whole) {
+    for (uint32_t id = 1; id < ns; ++id) lab[id] = 0;
+    sizes[0] = ns ? ns - 1 : 0;
+  } else {
+    for (uint64_t i = 0; i < n_ids; ++i)
+      if (group_of[i] >= n_groups) return fail(VS_ERR_ARG, "group %u of sample id %u is out of range (%u groups)", group_of[i], sample_ids[i], n_groups);
+    for (uint64_t i = 0; i < n_ids; ++i)
+      if (sample_ids[i] == 0 || sample_ids[i] >= ns)
+        return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u is not a sample of the cohort (1 .. %u)", sample_ids[i], ns - 1);
+    for (uint64_t i = 0; i < n_ids; ++i) {
+      const uint32_t id = sample_ids[i], g = group_of[i];
+      if (lab[id] == kGroupNone) { lab[id] = (uint8_t)g; sizes[g]++; }
+      else if (lab[id] != g) return fail(VS_ERR_ARG, "sample id %u is listed in group %u and in group %u: a sample belongs to at most one group", id, (uint32_t)lab[id], g);
+    }
+  }
   if (group_names)
     for (uint32_t g = 0; g < n_groups; ++g) {
       if (!group_names[g]) return fail(VS_ERR_ARG, "null name of group %u", g);
@@ -4263,8 +4367,34 @@ int vs_query_group_counts(vs_index* idx, const vs_region* regions, uint64_t n, c
     }
   if (labels.size() * 8 > kGroupLabelMaxBytes)
     return fail(VS_ERR_UNSUPPORTED, "the label table of a cohort of %u samples does not fit the group-count kernel's LDS (at most %zu sample ids)", ns, kGroupLabelMaxBytes);
+  return VS_OK;
+}
+
+int vs_query_group_counts(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, const uint32_t* group_of, uint64_t n_ids,
+                          uint32_t n_groups, const char* const* group_names, vs_result** out) {
+  std::vector<uint64_t> labels;
+  std::vector<uint32_t> sizes;
+  std::vector<std::string> names;
+  VS_TRY(group_query_args(idx, out, regions, n, sample_ids, group_of, n_ids, n_groups, group_names, "a grouped-count", false, 0, labels, sizes, names));
   const SharedReq req = column_request(ReqKind::Groups, labels, {}, n_groups);
   return make_result(idx, kKindGroups, out, [&](vs_result* r) {
+    r->n_groups = n_groups;
+    r->group_sizes = sizes;
+    r->group_names = names;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
+int vs_query_window_stats(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, const uint32_t* group_of, uint64_t n_ids,
+                          uint32_t n_groups, const char* const* group_names, uint32_t with_pairs, vs_result** out) {
+  std::vector<uint64_t> labels;
+  std::vector<uint32_t> sizes;
+  std::vector<std::string> names;
+  VS_TRY(group_query_args(idx, out, regions, n, sample_ids, group_of, n_ids, n_groups, group_names, "a window-statistics", true, with_pairs, labels, sizes, names));
+  SharedReq req = column_request(ReqKind::WindowStats, labels, {}, n_groups);
+  req.ws_sizes = sizes.data();
+  req.ws_pairs = with_pairs ? n_groups * (n_groups - 1) / 2 : 0;
+  return make_result(idx, kKindWindowStats, out, [&](vs_result* r) {
     r->n_groups = n_groups;
     r->group_sizes = sizes;
     r->group_names = names;
@@ -4865,6 +4995,8 @@ static int counts_to_host(vs_result* r) {   // (a grouped-count result: n_groups
   const size_t per_row = r->kind == kKindGroups ? r->n_groups : 1;
   return array_to_host(r, r->d_counts, (size_t)r->d.A * per_row * sizeof(uint4), &r->counts_pin, "allele counts");
 }
+// the records and pair records of a window-statistics result, one piece
+static size_t window_stats_bytes(const vs_result* r) { return (size_t)r->d.Q * (48 * (size_t)r->n_groups + 16 * (size_t)r->ws_pairs); }
 // Start (stream) the raw copy of a result: rows and -- on request -- the arena go into one page-locked block.  (The caller has passed
 // the gate.)
 static int raw_copy_begin(vs_result* r, bool with_carriers, hipStream_t stream) {
@@ -5053,6 +5185,13 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
       uint64_t nc = 0;
       for (uint64_t q = 0; q < r->d.Q; ++q)
         for (uint64_t a = r->h_var_begin[q] * G, e = a + r->h_nvar[q] * G; a < e; ++a) nc += c[a].x;
+      r->n_carriers_kept = nc;
+    }
+    if (r->kind == kKindWindowStats) {   // as a grouped-count result's: carriers = (alt_alleles + heterozygotes) / 2, summed over regions and groups
+      VS_TRY(array_to_host(r, r->d_wstats, window_stats_bytes(r), &r->cells_pin, "window statistics"));
+      const vs_window_stats* w = (const vs_window_stats*)r->cells_pin.p;
+      uint64_t nc = 0;
+      for (uint64_t i = 0, e = r->d.Q * r->n_groups; i < e; ++i) nc += (w[i].sum_ac + w[i].obs_het) / 2;
       r->n_carriers_kept = nc;
     }
     if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindPrune || r->kind == kKindClump || r->kind == kKindLdScore || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
@@ -5390,6 +5529,39 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
         out += num;
       }
       out += '\n';
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
+  if (r->kind == kKindWindowStats) {   // the region's records, a line per group, then a line per pair: integers only
+    VS_TRY(array_to_host(r, r->d_wstats, window_stats_bytes(r), &r->cells_pin, "window statistics"));
+    const uint32_t G = r->n_groups, P = r->ws_pairs;
+    const vs_window_stats* w = (const vs_window_stats*)r->cells_pin.p + q * G;
+    const vs_window_pair_stats* wp = (const vs_window_pair_stats*)((const uint8_t*)r->cells_pin.p + (size_t)r->d.Q * 48 * G) + q * P;
+    auto name = [&](uint32_t g) { return r->group_names.empty() ? std::to_string(g) : r->group_names[g]; };
+    std::string& out = r->text;
+    out = "Group\tN\tRows\tSeg\tSingletons\tDoubletons\tPrivate\tFixed\tSumAC\tSumAC2\tObsHet\n";
+    for (uint32_t g = 0; g < G; ++g) {
+      out += name(g);
+      for (uint64_t f : {(uint64_t)r->group_sizes[g], (uint64_t)w[g].rows, (uint64_t)w[g].seg, (uint64_t)w[g].singletons, (uint64_t)w[g].doubletons,
+                         (uint64_t)w[g].private_alleles, (uint64_t)w[g].fixed, w[g].sum_ac, w[g].sum_ac2, w[g].obs_het}) {
+        out += '\t';
+        out += std::to_string(f);
+      }
+      out += '\n';
+    }
+    if (P) {
+      out += "GroupA\tGroupB\tSumCross\tSegUnion\tFixedDiff\n";
+      uint32_t p = 0;
+      for (uint32_t g = 0; g < G; ++g)
+        for (uint32_t h = g + 1; h < G; ++h, ++p) {
+          out += name(g);
+          out += '\t';
+          out += name(h);
+          for (uint64_t f : {wp[p].sum_cross, (uint64_t)wp[p].seg_union, (uint64_t)wp[p].fixed_diff}) { out += '\t'; out += std::to_string(f); }
+          out += '\n';
+        }
     }
     *text = out.c_str();
     if (len) *len = out.size();
@@ -5741,6 +5913,35 @@ int vs_result_group_counts_device(vs_result* r, uint64_t* n_rows, uint32_t* n_gr
   *dev_counts = r->d_counts;
   if (n_rows) *n_rows = r->d.A;
   if (n_groups) *n_groups = r->n_groups;
+  return VS_OK;
+}
+
+int vs_result_get_window_stats(vs_result* r, uint64_t* n_regions, uint32_t* n_groups, uint32_t* n_pairs, const uint32_t** group_sizes, const char* const** group_names,
+                               const vs_window_stats** stats, const vs_window_pair_stats** pair_stats) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!stats) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindWindowStats) return fail(VS_ERR_ARG, "not a window-statistics result (vs_query_window_stats)");
+  static_assert(sizeof(vs_window_stats) == 48 && sizeof(vs_window_pair_stats) == 16, "record layout of the ABI");
+  VS_TRY(array_to_host(r, r->d_wstats, window_stats_bytes(r), &r->cells_pin, "window statistics"));
+  if (r->ws_name_ptrs.empty())
+    for (const std::string& s : r->group_names) r->ws_name_ptrs.push_back(s.c_str());
+  *stats = (const vs_window_stats*)r->cells_pin.p;
+  if (pair_stats) *pair_stats = r->ws_pairs ? (const vs_window_pair_stats*)((const uint8_t*)r->cells_pin.p + (size_t)r->d.Q * 48 * r->n_groups) : nullptr;
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_groups) *n_groups = r->n_groups;
+  if (n_pairs) *n_pairs = r->ws_pairs;
+  if (group_sizes) *group_sizes = r->group_sizes.data();
+  if (group_names) *group_names = r->ws_name_ptrs.empty() ? nullptr : r->ws_name_ptrs.data();
+  return VS_OK;
+}
+
+int vs_result_window_stats_device(vs_result* r, uint64_t* n_regions, uint32_t* n_groups, uint32_t* n_pairs, const void** dev_stats, const void** dev_pair_stats) {
+  VS_TRY(device_matrix_ready(r, dev_stats, kKindWindowStats, "not a window-statistics result (vs_query_window_stats)"));
+  *dev_stats = r->d_wstats;
+  if (dev_pair_stats) *dev_pair_stats = r->ws_pairs ? r->d_wstats + (size_t)r->d.Q * 48 * r->n_groups : nullptr;
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_groups) *n_groups = r->n_groups;
+  if (n_pairs) *n_pairs = r->ws_pairs;
   return VS_OK;
 }
 

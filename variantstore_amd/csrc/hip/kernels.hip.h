@@ -58,6 +58,11 @@
 //  k_count_slow_sites    counterpart; what a caller of type 6 would count on the host from the carrier lists)
 // k_group_counts        the same counts per sample GROUP in one pass over a row's carriers: a label byte per sample in LDS, one packed
 //                       LDS atomic per carrier, rows x groups records stored once (vs_query_group_counts: no reference counterpart)
+// k_window_stats        those records reduced per region and group, and per pair of groups, to the integers of the windowed diversity
+//                       statistics (rows, seg, singletons, private, fixed, sums of ac, ac^2, het, ac_g ac_h): a wave per region, 64-row
+//                       tiles packed into LDS, lanes owning (row slice, group) and (row slice, pair); regions longer than a chunk split
+//                       through k_burden_split_plan and added with integer atomics (vs_query_window_stats: no reference counterpart;
+//                       DESIGN 5q)
 // k_assoc_scan          every row scored against K phenotypes in one pass over its carriers: the carrier's K float32 values from a table
 //                       in LDS or L2, dosage x value summed in float64 in an order the table's layout fixes (segmented lane scans, no
 //                       floating-point atomic), rows x K cells stored once (vs_query_assoc_scan: no reference counterpart)
@@ -127,6 +132,7 @@
 #include "k_assoc.hip.h"
 #include "k_scores.hip.h"
 #include "k_burden.hip.h"
+#include "k_window_stats.hip.h"
 #include "k_matrix.hip.h"
 #include "k_ld.hip.h"
 #include "k_ld_block.hip.h"
