@@ -297,7 +297,10 @@ int vs_result_window_stats_device(vs_result* r, uint64_t* n_regions, uint32_t* n
  *                  Cochran-Armitage trend test): with the row's own count record over S, Sx = alt_alleles, Sxx = alt_alleles +
  *                  2 hom_alt, vx = n Sxx - Sx^2 in 64-bit integers, cov = n Sxy - Sx Sy and vy = n Syy - Sy^2 in double,
  *                  chi2 = ((double)n * cov) * cov / ((double)vx * vy), each operation rounded on its own in this order; 0.0 when
- *                  vx == 0 or vy <= 0 (a monomorphic or dropped row, a constant trait, n = 1).
+ *                  vx == 0 or vy <= 0 (a monomorphic or dropped row, a constant trait, n = 1).  Sxy, Sy and Syy of this formula
+ *                  are taken about a pivot, over y_k(s) - c_k in double: c_k is the value of trait k nearest its mean over S (the
+ *                  first of equally near ones).  The statistic does not change with c_k; the cancellations in cov and vy then
+ *                  happen at the scale of the trait's spread, not of its mean, and integer-valued traits keep integer sums.
  * The order of a row's additions is fixed by the table's layout, not by the run: the same call gives the same bytes every time,
  * whichever form the phenotype table takes on the device (option "assoc_lds_max_kib").  The result also holds the count record of
  * every table row over S (vs_allele_counts, as an LD result does), per trait Sy and Syy as doubles -- summed on the host left to right

@@ -70,9 +70,55 @@ def trait_sums(y):
     return sy, syy
 
 
+def pivots(y):
+    """The pivot of every trait as the engine chooses it: the trait VALUE nearest Sy / n (float64, Sy as trait_sums forms it), of
+    equally near ones the first in column order -- a value of the trait's own grid, so integer-valued traits keep integer sums."""
+    y64 = np.asarray(y, np.float32).astype(np.float64)
+    mean = trait_sums(y)[0] / np.float64(y64.shape[0])
+    return y64[np.argmin(np.abs(y64 - mean[None, :]), axis=0), np.arange(y64.shape[1])]
+
+
+def trait_sums_about(y, c):
+    """(Sy~, Syy~) per trait about the pivots c (K,): y~ = y - c in float64, then left to right in column order as trait_sums."""
+    yt = np.asarray(y, np.float32).astype(np.float64) - np.asarray(c, np.float64)[None, :]
+    sy, syy = np.zeros(yt.shape[1]), np.zeros(yt.shape[1])
+    for r in yt:
+        sy = sy + r
+        syy = syy + r * r
+    return sy, syy
+
+
+def dot_sequential(dosage, y, c=None):
+    """float64 (A, K): sum of dosage x (y - c) over a dense dosage matrix (A, n), the carriers added left to right in column order
+    (c None: 0).  The kernel adds the same terms in a tree fixed by the table's layout; this is the plainest order."""
+    y64 = np.asarray(y, np.float32).astype(np.float64)
+    if c is not None:
+        y64 = y64 - np.asarray(c, np.float64)[None, :]
+    d = np.asarray(dosage, np.float64)
+    out = np.zeros((d.shape[0], y64.shape[1]))
+    for j in range(d.shape[1]):   # (a sample that does not carry the row adds 0.0: the sum stays as it is)
+        out = out + d[:, j, None] * y64[None, j, :]
+    return out
+
+
+def chi2_uncentred(n, alt_alleles, hom_alt, dosage, y):
+    """The score test as the engine formed it before the sums were taken about a pivot: chi2() over the raw Sy, Syy and Sxy.  cov and
+    vy cancel at the scale of the trait's mean; tests/test_assoc_exact_host.py keeps this to show that the exact check rejects it."""
+    sy, syy = trait_sums(y)
+    return chi2(n, alt_alleles, hom_alt, sy, syy, dot_sequential(dosage, y))
+
+
+def chi2_centred(n, alt_alleles, hom_alt, dosage, y):
+    """The score test in the engine's order: the pivots, Sy~ / Syy~ and Sxy~ about them, then chi2() (the statistic does not change
+    when a constant is taken off the trait)."""
+    c = pivots(y)
+    sy, syy = trait_sums_about(y, c)
+    return chi2(n, alt_alleles, hom_alt, sy, syy, dot_sequential(dosage, y, c))
+
+
 def chi2(n, alt_alleles, hom_alt, sy, syy, sxy):
     """The score test in float64, every operation rounded on its own in the stated order: sxy (A, K), alt_alleles / hom_alt (A,)
-    integers, sy / syy (K,).  0.0 where vx == 0 or vy <= 0."""
+    integers, sy / syy (K,) -- for VS_ASSOC_CHI2 the three sums about the traits' pivots.  0.0 where vx == 0 or vy <= 0."""
     sx = np.asarray(alt_alleles).astype(np.int64)
     sxx = sx + 2 * np.asarray(hom_alt).astype(np.int64)
     vx = (np.int64(n) * sxx - sx * sx)[:, None]

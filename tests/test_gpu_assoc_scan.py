@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import assoc_exact_ref
 import assoc_scan_ref as ref
 from helpers import random_regions, write_random_cohort
 from test_gpu_genotype_matrix import _columns, _oracle, _parse, _read_device, _ref_len, _ref_rows, _reported
@@ -94,7 +95,9 @@ def _check_int(vs, regions, parsed, valid, samples, ycol, rng, chi2=True):
 def _check_real(vs, regions, parsed, valid, samples, ycol, rng):
     """Real-valued phenotypes: |got - fsum| <= m 2^-53 sum |d y| per cell, m the row's carriers in S (m - 1 rounded additions of exact
     terms); the sums of the traits within n 2^-53 sum |y| and n 2^-53 sum y^2 of fsum; CHI2 against the formula applied on the host
-    to the engine's own DOT cells, counts and sums within 8 * 2^-53 relative."""
+    to the engine's own DOT cells, counts and sums within 8 * 2^-53 relative -- for the traits taken about their pivots, where
+    the score is formed from exactly those cells (below); the traits as given give the same bytes where y - c is exact, and stay
+    within the bound of the exact statistic that assoc_exact_ref derives from the text and the trait values alone."""
     res = _query(vs, regions, ycol, samples, rng)
     got = res.assoc_scan()
     res.close()
@@ -111,8 +114,26 @@ def _check_real(vs, regions, parsed, valid, samples, ycol, rng):
     c = cres.assoc_scan()
     cres.close()
     mine_c, _rows, _names = _check_rows(vs, c, parsed, valid, samples, ycol)
-    exp = ref.chi2(n, got["counts"]["alt_alleles"][mine], got["counts"]["hom_alt"][mine], got["trait_sum"], got["trait_sumsq"], got["scores"][mine])
-    assert np.all(np.abs(c["scores"][mine_c] - exp) <= 8 * EPS * np.abs(exp))
+    # the formula's order of operations: y2 = float32(y - c) holds 0.0 where y holds its pivot, and 0.0 is y2's own pivot, so the
+    # CHI2 query over y2 adds the numbers its DOT query adds, in the same order, and forms the score from y2's raw sums
+    piv = ref.pivots(ycol)
+    y2 = (y64 - piv[None, :]).astype(np.float32)
+    assert not ref.pivots(y2).any(), "a near-tie of the pivot"
+    dres, c2res = _query(vs, regions, y2, samples, rng), _query(vs, regions, y2, samples, rng, "chi2")
+    about, c2 = dres.assoc_scan(), c2res.assoc_scan()
+    dres.close(); c2res.close()
+    mine_d, mine_2 = _reported(about, valid)[0], _reported(c2, valid)[0]
+    exp = ref.chi2(n, about["counts"]["alt_alleles"][mine_d], about["counts"]["hom_alt"][mine_d], about["trait_sum"], about["trait_sumsq"], about["scores"][mine_d])
+    assert np.all(np.abs(c2["scores"][mine_2] - exp) <= 8 * EPS * np.abs(exp))
+    exact_diff = (y2.astype(np.float64) == y64 - piv[None, :]).all(axis=0)
+    # where every y - c is a float32 as it is, y and y2 are the same numbers to the kernel: the same bytes
+    assert c["scores"][mine_c][:, exact_diff].tobytes() == c2["scores"][mine_2][:, exact_diff].tobytes()
+    dense = np.zeros((parsed.n_rows, n), np.int64)
+    r_, c_, d_, _val = ref.dosages(parsed, names)
+    dense[r_, c_] = d_
+    val, bound = assoc_exact_ref.table(dense, ycol)
+    err = np.abs(c["scores"][mine_c] - val[rows])
+    assert np.all(err <= bound[rows] + EPS * val[rows]), float((err / np.maximum(bound[rows] + EPS * val[rows], 1e-300)).max())
     return got
 
 

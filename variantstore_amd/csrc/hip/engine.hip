@@ -1266,7 +1266,7 @@ static int capture_totals(vs_result* r) {
 // the whole cohort) and its words; for burden and matrix the columns in front of each word of the mask (NULL with the mask) and
 // their number; for burden the window (0 .. UINT32_MAX: every reported row counts, k_allele_counts is not run); for LD the band's
 // window and statistic.  Groups: `mask` is the label table (a byte per sample id, eight to a word), n_cols the number of groups.
-// Assoc: mask, rank and n_cols as for the matrix; `pheno` is the upload that travels with them -- Sy[8], Syy[8] as doubles, then the
+// Assoc: mask, rank and n_cols as for the matrix; `pheno` is the upload that travels with them -- Sy~[8], Syy~[8] and the pivots c[8] as doubles, then the
 // phenotype table in column order, [column][Kp] float32 -- of pheno_words 8-byte words; the traits and the statistic.
 // Scores: mask, rank and n_cols as for the matrix; `weights` (host or device memory, weights_on_device) are n_weights x n_scores
 // float32 in report order; score_max_bits: per column the largest |w| as a float pattern, formed on the host from host weights.
@@ -1407,19 +1407,24 @@ static void launch_group_counts(vs_index* idx, const DevResult& d, const uint32_
 
 // k_assoc_scan over the whole table of an association batch, behind k_allele_counts over the same table (d_pheno: SharedReq::pheno on
 // the device).  The table form: in LDS when it is at most option assoc_lds_max_kib and the workgroup's LDS stays within a CU's.
-template <uint32_t KP, bool SUBSET>
+template <uint32_t KP, bool SUBSET, bool CHI2>
 static int launch_assoc_form(vs_index* idx, const AssocArgs& a, unsigned blocks, bool lds_table, size_t lds) {
-  const void* fn = lds_table ? reinterpret_cast<const void*>(&k_assoc_scan<KP, SUBSET, true>) : reinterpret_cast<const void*>(&k_assoc_scan<KP, SUBSET, false>);
+  const void* fn = lds_table ? reinterpret_cast<const void*>(&k_assoc_scan<KP, SUBSET, true, CHI2>) : reinterpret_cast<const void*>(&k_assoc_scan<KP, SUBSET, false, CHI2>);
   // more than the default LDS of a launch: the limit is raised once per instantiation, to all a CU has beside the static part
-  const uint32_t bit = 1u << (4 * (KP == 1 ? 0 : KP == 2 ? 1 : KP == 4 ? 2 : 3) + 2 * SUBSET + lds_table);
+  const uint32_t bit = 1u << (16 * CHI2 + 4 * (KP == 1 ? 0 : KP == 2 ? 1 : KP == 4 ? 2 : 3) + 2 * SUBSET + lds_table);
   if (lds + assoc_static_lds(KP) > (48 << 10) && !(idx->assoc_lds_raised & bit)) {
     HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kAssocLdsPerCu - assoc_static_lds(KP))));
     idx->assoc_lds_raised |= bit;
   }
-  if (lds_table) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_assoc_scan<KP, SUBSET, true>), dim3(blocks), dim3(256), lds, idx->stream, idx->d, a);
-  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_assoc_scan<KP, SUBSET, false>), dim3(blocks), dim3(256), lds, idx->stream, idx->d, a);
+  if (lds_table) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_assoc_scan<KP, SUBSET, true, CHI2>), dim3(blocks), dim3(256), lds, idx->stream, idx->d, a);
+  else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_assoc_scan<KP, SUBSET, false, CHI2>), dim3(blocks), dim3(256), lds, idx->stream, idx->d, a);
   HIP_TRY(hipGetLastError());
   return VS_OK;
+}
+template <uint32_t KP>
+static int launch_assoc_kp(vs_index* idx, const AssocArgs& a, bool subset, bool chi2, unsigned blocks, bool lds_table, size_t lds) {
+  if (chi2) return subset ? launch_assoc_form<KP, true, true>(idx, a, blocks, lds_table, lds) : launch_assoc_form<KP, false, true>(idx, a, blocks, lds_table, lds);
+  return subset ? launch_assoc_form<KP, true, false>(idx, a, blocks, lds_table, lds) : launch_assoc_form<KP, false, false>(idx, a, blocks, lds_table, lds);
 }
 static int launch_assoc(vs_index* idx, vs_result* r, const uint32_t* u_site, uint64_t U, const uint64_t* d_mask, const uint32_t* d_rank, const uint64_t* d_pheno,
                         const SharedReq& q) {
@@ -1429,8 +1434,9 @@ static int launch_assoc(vs_index* idx, vs_result* r, const uint32_t* u_site, uin
   a.rows = (const VariantRow*)d.rows; a.u_site = u_site; a.A = d.A; a.U = U;
   a.S = d_mask; a.S_rank = d_rank; a.s_words = d_mask ? q.words : 0;
   a.n_cols = q.n_cols; a.K = q.n_traits; a.chi2 = q.assoc_stat == VS_ASSOC_CHI2;
+  const bool chi2 = a.chi2 != 0;
   a.sums = reinterpret_cast<const double*>(d_pheno);
-  a.table = reinterpret_cast<const float*>(d_pheno + 2 * kAssocTraitsMax);
+  a.table = reinterpret_cast<const float*>(d_pheno + kAssocHeadWords);
   a.counts = r->d_counts; a.out = r->d_scores;
   const size_t sub = d_mask ? ((size_t)q.words * 8 + 15) / 16 * 16 + ((size_t)q.words * 4 + 15) / 16 * 16 : 0;
   const size_t table = (size_t)q.n_cols * kp * 4;
@@ -1439,10 +1445,10 @@ static int launch_assoc(vs_index* idx, vs_result* r, const uint32_t* u_site, uin
   const size_t lds = sub + (lds_table ? table : 0);
   const unsigned blocks = (unsigned)((d.A + 4 * kAssocRows - 1) / (4 * kAssocRows));
   switch (kp) {
-    case 1: return d_mask ? launch_assoc_form<1, true>(idx, a, blocks, lds_table, lds) : launch_assoc_form<1, false>(idx, a, blocks, lds_table, lds);
-    case 2: return d_mask ? launch_assoc_form<2, true>(idx, a, blocks, lds_table, lds) : launch_assoc_form<2, false>(idx, a, blocks, lds_table, lds);
-    case 4: return d_mask ? launch_assoc_form<4, true>(idx, a, blocks, lds_table, lds) : launch_assoc_form<4, false>(idx, a, blocks, lds_table, lds);
-    default: return d_mask ? launch_assoc_form<8, true>(idx, a, blocks, lds_table, lds) : launch_assoc_form<8, false>(idx, a, blocks, lds_table, lds);
+    case 1: return launch_assoc_kp<1>(idx, a, d_mask != nullptr, chi2, blocks, lds_table, lds);
+    case 2: return launch_assoc_kp<2>(idx, a, d_mask != nullptr, chi2, blocks, lds_table, lds);
+    case 4: return launch_assoc_kp<4>(idx, a, d_mask != nullptr, chi2, blocks, lds_table, lds);
+    default: return launch_assoc_kp<8>(idx, a, d_mask != nullptr, chi2, blocks, lds_table, lds);
   }
 }
 
@@ -4437,11 +4443,11 @@ int vs_query_assoc_scan(vs_index* idx, const vs_region* regions, uint64_t n, con
     }
   if (mask.size() * 8 > kCountMaskMaxBytes)
     return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the counting kernel's LDS (the whole cohort has no such limit)", ns);
-  // the upload: Sy[8], Syy[8], then the table in column order, [column][Kp] float32 with the padding zero
+  // the upload: Sy~[8], Syy~[8] and the pivots c[8] (below), then the table in column order, [column][Kp] float32 with the padding zero
   const uint32_t kp = assoc_pow2(n_traits);
   const size_t n_cols = cols.size();
-  std::vector<uint64_t> pheno(2 * kAssocTraitsMax + (n_cols * kp * 4 + 7) / 8, 0);
-  float* table = reinterpret_cast<float*>(pheno.data() + 2 * kAssocTraitsMax);
+  std::vector<uint64_t> pheno(kAssocHeadWords + (n_cols * kp * 4 + 7) / 8, 0);
+  float* table = reinterpret_cast<float*>(pheno.data() + kAssocHeadWords);
   for (uint64_t i = 0; i < n_ids; ++i) {
     size_t col = i;
     if (sample_ids) {
@@ -4457,8 +4463,31 @@ int vs_query_assoc_scan(vs_index* idx, const vs_region* regions, uint64_t n, con
       sy[k] += y;
       syy[k] += y * y;   // (the product of two float32 values is exact in double)
     }
+  // CHI2 cancels n Sxy - Sx Sy and n Syy - Sy^2: at the scale of the trait's mean those differences lose what the statistic is made
+  // of (a trait of 1e6 +- 1 keeps 3 digits of it).  The statistic does not change when a constant is taken off the trait, so the
+  // three sums are taken about a pivot c_k instead: the trait VALUE nearest Sy / n (the first of equally near ones), a function of
+  // the columns asked for alone.  A value of the trait's own grid keeps integer-valued traits' sums integers, and y - c, taken in
+  // double, is exact unless the two lie 29 binary places apart.  DOT takes no pivot (the kernel's CHI2 parameter): its cells are
+  // the bytes they were.  trait_sum / trait_sumsq stay the raw sums above.
   double* sums = reinterpret_cast<double*>(pheno.data());
-  for (uint32_t k = 0; k < n_traits; ++k) { sums[k] = sy[k]; sums[kAssocTraitsMax + k] = syy[k]; }
+  for (uint32_t k = 0; k < n_traits; ++k) {
+    double c = 0.0;
+    if (stat == VS_ASSOC_CHI2) {
+      const double mean = sy[k] / (double)n_cols;
+      double best = INFINITY;
+      for (size_t j = 0; j < n_cols; ++j) {
+        const double y = (double)table[j * kp + k], dist = std::fabs(y - mean);
+        if (dist < best) { best = dist; c = y; }
+      }
+    }
+    double st = 0.0, stt = 0.0;
+    for (size_t j = 0; j < n_cols; ++j) {
+      const double y = (double)table[j * kp + k] - c;
+      st += y;
+      stt += y * y;
+    }
+    sums[k] = st; sums[kAssocTraitsMax + k] = stt; sums[2 * kAssocTraitsMax + k] = c;
+  }
   SharedReq req = column_request(ReqKind::Assoc, mask, rank, n_cols);
   req.pheno = pheno.data(); req.pheno_words = pheno.size(); req.n_traits = n_traits; req.assoc_stat = stat;
   return make_result(idx, kKindAssoc, out, [&](vs_result* r) {

@@ -7,7 +7,10 @@
 namespace vsamd {
 
 // out[row * K + k] = Sxy = sum over the samples s of S of d(s) * y_k(s), d = popc(gt & 6) the dosage (VS_ASSOC_DOT), or the score
-// test formed from it, the row's count record over S and the trait's Sy / Syy (VS_ASSOC_CHI2, assoc_chi2 below).
+// test (VS_ASSOC_CHI2, assoc_chi2 below) formed from the row's count record over S and three sums taken about the trait's pivot c_k:
+// Sxy~ = sum d(s) * (y_k(s) - c_k) here, Sy~ and Syy~ by the host.  The pivot is the trait value nearest the trait's mean over S (the
+// host chooses it); the statistic does not change with it, but the cancellations in it then happen at the scale of the trait's
+// spread instead of its mean.  DOT (the kernel's CHI2 parameter false) takes no pivot and no subtraction: the instructions it ran before.
 //
 // The shape is k_group_counts': one wave owns kAssocRows = 64 consecutive rows and 64 x Kp double accumulators in LDS (Kp: K rounded
 // up to 1, 2, 4 or 8; the padding columns of the phenotype table are zero).  The pieces named here are k_carriers.hip.h's.
@@ -26,7 +29,8 @@ namespace vsamd {
 //          the row (6 shuffle steps per double), then ONE plain LDS read-add-write of acc[row][k] by the segment's last lane.  A row
 //          has one segment per step, the steps of a wave are sequential and no other wave owns the row.
 //   dense  lane-private sums, a butterfly over the wave (6 steps, the same tree every time), lane 0 adds.
-// A product d * y is exact in double (d is 0, 1 or 2, y a float32), so a fused multiply-add rounds as multiply-then-add does.
+// y - c is taken in double (exact unless the two lie 29 binary places apart; c sits in scalar registers: a uniform load of the kernel's
+// arguments).  A product d * (y - c) is exact in double (d is 0, 1 or 2), so a fused multiply-add rounds as multiply-then-add does.
 //
 // LDS per workgroup (4 waves), from MI355X_MICROARCH.md (160 KiB per CU, workgroups per CU <= 160 KiB / LDS per workgroup, 64 KiB per
 // workgroup unless the launch asks for more):
@@ -46,14 +50,19 @@ namespace vsamd {
 // memset; nothing of a recycled buffer shows through.
 //
 // Resources (hipcc -O3 --offload-arch=gfx950, -Rpass-analysis=kernel-resource-usage): VGPRs / SGPRs, then waves per SIMD by registers;
-// scratch 0 bytes per lane, no SGPR or VGPR spill in any instantiation; <Kp, SUBSET, LDSTAB>:
+// scratch 0 bytes per lane, no SGPR or VGPR spill in any instantiation; <Kp, SUBSET, LDSTAB> under DOT, then under CHI2:
 //   <1,0,0> 46/76 8   <1,0,1> 48/74 8   <1,1,0> 48/79 8   <1,1,1> 48/78 8      <2,0,0> 48/76 8   <2,0,1> 48/74 8   <2,1,0> 48/79 8   <2,1,1> 48/78 8
 //   <4,0,0> 56/76 7   <4,0,1> 54/74 7   <4,1,0> 56/79 7   <4,1,1> 54/78 7      <8,0,0> 74/76 5   <8,0,1> 68/74 5   <8,1,0> 72/79 5   <8,1,1> 68/78 5
-// At Kp = 8 the registers allow 5 waves per SIMD = 5 workgroups per CU, which is what the static LDS allows as well.
+//   <1,0,0> 46/78 8   <1,0,1> 48/76 8   <1,1,0> 48/81 8   <1,1,1> 48/80 8      <2,0,0> 48/80 8   <2,0,1> 48/78 8   <2,1,0> 48/83 8   <2,1,1> 48/82 8
+//   <4,0,0> 56/84 7   <4,0,1> 54/82 7   <4,1,0> 56/87 7   <4,1,1> 54/86 7      <8,0,0> 74/92 5   <8,0,1> 68/90 5   <8,1,0> 72/95 5   <8,1,1> 68/94 5
+// At Kp = 8 the registers allow 5 waves per SIMD = 5 workgroups per CU, which is what the static LDS allows as well.  CHI2's pivots
+// are the 2 Kp scalar registers it holds more than DOT.  The template parameter CHI2 governs the pivot alone and the epilogue reads the
+// statistic from the arguments, as it did before there was a pivot: a DOT instantiation is that kernel, instruction for instruction.
 constexpr uint32_t kAssocRows = 64;
 constexpr uint32_t kAssocStageWords = 520;        // 4096 carriers of a 64-word chunk = 512 words, + 1 (unaligned start), rounded up
 constexpr uint32_t kAssocTraitsMax = 8;
 constexpr size_t kAssocLdsPerCu = 160 << 10;
+constexpr size_t kAssocHeadWords = 3 * kAssocTraitsMax;   // the doubles in front of the phenotype table in the upload (AssocArgs::sums)
 __host__ __device__ constexpr uint32_t assoc_pow2(uint32_t k) { return k <= 1 ? 1u : k <= 2 ? 2u : k <= 4 ? 4u : 8u; }
 __host__ __device__ constexpr size_t assoc_static_lds(uint32_t kp) { return 4ull * kAssocRows * kp * 8 + 4ull * kAssocStageWords * 4 + 5136 + 128; }
 
@@ -61,7 +70,7 @@ struct AssocArgs {
   const VariantRow* rows; const uint32_t* u_site; uint64_t A, U;
   const uint64_t* S; const uint32_t* S_rank; uint32_t s_words;   // the subset's mask and the columns in front of each word (SUBSET)
   uint32_t n_cols, K, chi2;
-  const double* sums;      // Sy[8], Syy[8]
+  const double* sums;      // Sy~[8], Syy~[8] about the pivots, then the pivots c[8] (read under CHI2 only)
   const float* table;      // [n_cols][Kp]
   const uint4* counts;     // the rows' count records over S (k_allele_counts, the launch before this one)
   double* out;
@@ -82,9 +91,18 @@ __device__ __forceinline__ void pheno_load(const float* __restrict__ tab, uint32
   }
 }
 
-// The score test of a regression of y on the dosage without covariates, from the row's record over S (Sx = alt_alleles,
-// Sxx = alt_alleles + 2 hom_alt), the trait's Sy / Syy and the cell's Sxy -- in exactly this order of operations, each rounded on
-// its own (no contraction: cov and vy cancel, and a fused product would move them by more than the last bit).
+// y~ = y - c in double under CHI2; y under DOT, whose cells are the sums of d * y and cost no subtraction
+template <bool CHI2>
+__device__ __forceinline__ double about(float y, double c) {
+  if constexpr (CHI2) return (double)y - c;
+  else return (double)y;
+}
+
+// The score test of a regression of y on the dosage without covariates, n cov^2 / (vx vy), from the row's record over S
+// (Sx = alt_alleles, Sxx = alt_alleles + 2 hom_alt) and the trait's Sy~ / Syy~ and the cell's Sxy~ about the pivot -- in exactly this
+// order of operations, each rounded on its own (no contraction: cov and vy cancel, and a fused product would move them by more than
+// the last bit).  About the pivot Sy~ is of the order of one standard deviation, so p2 is small beside p1 and q2 beside q1: what
+// cancels is what the data cancel.  A constant trait has every y~ = 0: vy = 0 exactly.
 __device__ __forceinline__ double assoc_chi2(uint32_t n, const uint4 rec, double sy, double syy, double sxy) {
 #pragma clang fp contract(off)
   const long long sx = rec.y, sxx = (long long)rec.y + 2ll * rec.z;
@@ -99,7 +117,7 @@ __device__ __forceinline__ double assoc_chi2(uint32_t n, const uint4 rec, double
   return num / den;
 }
 
-template <uint32_t KP, bool SUBSET, bool LDSTAB>
+template <uint32_t KP, bool SUBSET, bool LDSTAB, bool CHI2>
 __global__ void __launch_bounds__(256) k_assoc_scan(DevImage im, AssocArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t s_assoc[];   // SUBSET: mask, ranks; LDSTAB: the table
   __shared__ FlatRows s_rows;
@@ -127,6 +145,9 @@ __global__ void __launch_bounds__(256) k_assoc_scan(DevImage im, AssocArgs a) {
   if (r0 >= a.A) return;
   const uint64_t row = r0 + lane;
   const bool valid = row < a.A;
+  double piv[KP];            // CHI2 only; uniform: scalar loads, scalar registers
+#pragma unroll
+  for (uint32_t k = 0; k < KP; ++k) piv[k] = CHI2 ? a.sums[2 * kAssocTraitsMax + k] : 0.0;
   const CarrierForm f = carrier_form(im);
   const ColumnTile t{s_mask, s_rank, 0u, a.n_cols, im.num_samples};   // one tile over all columns
   // ---- the row's parameters ----
@@ -160,7 +181,7 @@ __global__ void __launch_bounds__(256) k_assoc_scan(DevImage im, AssocArgs a) {
         pheno_load<KP>(tab, col, y);
         const double d = (double)__popc(gt_of_slot(w, j, f.groups) & 6u);
 #pragma unroll
-        for (uint32_t k = 0; k < KP; ++k) s[k] = __builtin_fma(d, (double)y[k], s[k]);
+        for (uint32_t k = 0; k < KP; ++k) s[k] = __builtin_fma(d, about<CHI2>(y[k], piv[k]), s[k]);
       }
     }
     // the groups of a row are consecutive lanes: inclusive scan within the segments of equal L
@@ -215,7 +236,7 @@ __global__ void __launch_bounds__(256) k_assoc_scan(DevImage im, AssocArgs a) {
           pheno_load<KP>(tab, col, y);
           const double d = (double)__popc(gt_of_record(stage[kc >> 3], kc, f.groups) & 6u);
 #pragma unroll
-          for (uint32_t k = 0; k < KP; ++k) s[k] = __builtin_fma(d, (double)y[k], s[k]);
+          for (uint32_t k = 0; k < KP; ++k) s[k] = __builtin_fma(d, about<CHI2>(y[k], piv[k]), s[k]);
         }
         kc += 1;
       }
