@@ -873,6 +873,60 @@ int vs_result_get_sample_ibs(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, u
 int vs_result_sample_ibs_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint32_t* stat, const void** dev_counts,
                                 const void** dev_matrices, const void** dev_king);
 
+/* Trio scan over regions: Mendelian errors and allele transmissions per table row and per trio -- what `plink --mendel`, `plink --tdt`
+ * and `bcftools +mendelian` start from once parents and children are known -- counted on the GPU without the genotype matrix ever
+ * reaching the host.  The variant table, its rows and which of them the duplicate rule dropped are those of
+ * vs_query_genotype_matrix over the same regions.  `trios`: 3 * n_trios sample ids, per trio child, father, mother -- pairwise
+ * distinct, none of them 0.  A sample may appear in any number of trios and in any role; the same triple given twice counts twice.
+ * The columns S are the distinct ids over all trios, ascending.
+ * For a table row v and a trio t let f, m, c be the dosages popcount(cell & 6) of father, mother and child (0, 1 or 2; a dropped
+ * row is all zeros), and g(0) = {0}, g(1) = {0, 1}, g(2) = {1} the gametes a parent of that dosage can give:
+ *   error         c is no sum a + b with a in g(f), b in g(m)
+ *   denovo        f == 0 && m == 0 && c > 0, a subset of the errors
+ *   transmitted   T = c - [f == 2] - [m == 2]            consistent cells only: an error cell adds nothing to T or U
+ *   untransmitted U = [f == 1] + [m == 1] - T            a cell with no heterozygous parent has T = U = 0; both parents and the
+ *                                                        child heterozygous: T = U = 1
+ * Only the dosage takes part: the query is meant for diploid calls, a haploid `1` counts as dosage 1.  A `1|2` call shows dosage 1
+ * on both of its ALT rows, as everywhere here: the rule per row is then a necessary condition per allele.
+ *   rows[v]   the four sums over all trios
+ *   trios[t]  the four sums over every table row once (rows that several regions report count once, as for vs_query_sample_ibs)
+ *   n_used    the table's rows minus those the duplicate rule dropped
+ *   counts[v] the count record of table row v over S
+ * All sums are integers formed with integer adds: the same call gives the same bytes.
+ * `regions` as for vs_query_genotype_matrix.  Checked on the host, in this order, before the handle's device is asked for (a handle
+ * opened without a device reports them first and VS_ERR_NO_DEVICE otherwise): n == 0, trios == NULL, n_trios == 0 or n_trios >
+ * VS_TRIOS_MAX -> VS_ERR_ARG; then trio by trio: two equal ids inside the triple -> VS_ERR_ARG (the message names the trio's index),
+ * id 0 or id >= num_samples -> VS_ERR_UNKNOWN_SAMPLE; more than 65,536 distinct members -> VS_ERR_UNSUPPORTED (a staged row must
+ * fit the kernel's LDS tile).  Once the plan has given the rows and before anything is allocated: a table of 2^31 rows or more ->
+ * VS_ERR_ARG (a per-trio sum must fit uint32); the temporary genotype matrix (rows x row_pitch bytes, not part of the result), the
+ * count records, both record arrays and the trio table together may not exceed option "matrix_max_mib" MiB (default 32 GiB):
+ * beyond it VS_ERR_ARG, and the message names rows, columns, trios and bytes.
+ * Option "trio_chunk": the trios one workgroup of the scan takes, a multiple of 64 in 64 .. 16384; 0 (default): by the batch's
+ * shape -- all of them unless the table's row blocks alone give fewer than 2048 workgroups.  The sums are the same integers under
+ * every setting.
+ * Every batch size takes the batch pipeline; a trio batch is never speculative and leaves the handle's type-6 state as it was.  The
+ * result holds the type-6 per-region arrays and variant table, no carrier arena, the counts and the records: vs_result_get_raw /
+ * vs_result_get_view with with_carriers = 0, vs_result_layout (arena and lists 0), vs_result_fill_ms (the batch's own kernels) and
+ * vs_result_totals (n_carriers = the nonzero cells of the temporary matrix) work; vs_result_format_region returns per reported row
+ * "Pos Ref Alt AC Errors DeNovo T U" (tab-separated, under that header; AC over S; dropped rows left out); with_carriers = 1,
+ * vs_result_digest, vs_result_pack_headers / _pack_regions and vs_comm_allgather_regions* fail with VS_ERR_UNSUPPORTED; the other
+ * vs_result_get_* accessors fail with VS_ERR_ARG. */
+#define VS_TRIOS_MAX (1u << 20)
+typedef struct { uint32_t errors, denovo, transmitted, untransmitted; } vs_trio_counts;
+int vs_query_trio_scan(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* trios /* 3 * n_trios: child, father, mother */,
+                       uint64_t n_trios, vs_result** out);
+/* A trio result copied into page-locked memory owned by the result: rows[v], trios[t], n_used, counts[v], col_ids[c] the sample id
+ * of column c, trio_cols three column indices per trio (child, father, mother: col_ids[trio_cols[3 t]] is trio t's child).
+ * Every out-pointer but `rows` may be NULL.  VS_ERR_ARG on any other result. */
+int vs_result_get_trio_scan(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint64_t* n_trios, uint64_t* n_used, const uint32_t** col_ids,
+                            const uint32_t** trio_cols /* 3 per trio: column indices */, const vs_allele_counts** counts,
+                            const vs_trio_counts** rows, const vs_trio_counts** trios);
+/* The same as it lies in HBM, valid until vs_result_free: dev_rows n_rows records of 16 bytes, dev_trios n_trios records right behind
+ * them, dev_n_used one uint64 right behind those; n_rows count records of 16 bytes.  The engine has synchronised its stream when
+ * this returns: the caller needs no event. */
+int vs_result_trio_scan_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint64_t* n_trios, const void** dev_counts,
+                               const void** dev_rows, const void** dev_trios, const void** dev_n_used);
+
 /* host view of a sequence result: region i is chars[seq_begin[i] .. seq_begin[i+1]) */
 int vs_result_get_sequences(vs_result* r, uint64_t* n_regions, const uint8_t** region_flags, const uint64_t** seq_begin,
                             const char** chars);
@@ -1087,6 +1141,9 @@ void vs_comm_destroy(vs_comm* c);
  *                     under every setting
  *   "ibs_chunk"       table rows one workgroup of the IBS kernel sums (vs_query_sample_ibs).  0 (default): by the batch's shape,
  *                     about 128 workgroups; else 64..65536.  The sums are the same integers under every setting
+ *   "trio_chunk"      trios one workgroup of the trio kernel takes (vs_query_trio_scan).  0 (default): by the batch's shape, all of
+ *                     them unless the row blocks give fewer than 2048 workgroups; else a multiple of 64 in 64..16384.  The sums are
+ *                     the same integers under every setting
  *   "score_tile_cols" columns of a workgroup's tile of the score kernel: 0 (default): all that 64 KiB of int64 cells hold,
  *                     65536 / (8 Kp); else a multiple of 16 in 16..65536, held to that (small cohorts reach tile boundaries with it).
  *                     The sums are the same integers under every setting of the two

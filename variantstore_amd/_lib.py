@@ -158,6 +158,12 @@ SYMBOLS = {
                                            C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]),
     "vs_result_sample_ibs_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "vs_query_trio_scan": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(_P)]),
+    "vs_result_get_trio_scan": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(AlleleCounts)),
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "vs_result_trio_scan_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "vs_query_ld_matrix": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.POINTER(_P)]),
     "vs_result_get_ld_matrix": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                           C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(AlleleCounts)),

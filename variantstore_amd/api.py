@@ -100,6 +100,23 @@ def pvalue_keys(p):
     return keys
 
 
+def trio_tdt_chi2(row_stats):
+    """The transmission disequilibrium statistic of every row of a trio result: (T - U)**2 / (T + U) as float64 from the row's exact
+    transmitted and untransmitted counts -- each integer (T - U and T + U, formed in int64) converted once, one multiplication, one
+    division.  NaN where T + U == 0."""
+    t, u = row_stats["transmitted"].astype(np.int64), row_stats["untransmitted"].astype(np.int64)
+    diff, total = (t - u).astype(np.float64), (t + u).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(total > 0.0, diff * diff / total, np.nan)
+
+
+def trio_error_rate(trio_stats, n_used):
+    """The Mendelian error rate of every trio of a trio result: errors / n_used as float64, NaN at n_used == 0."""
+    if not n_used:
+        return np.full(trio_stats.shape[0], np.nan)
+    return trio_stats["errors"].astype(np.float64) / float(n_used)
+
+
 def window_stats_derived(stats, pairs, group_sizes, lengths=None):
     """The diversity statistics of a window-statistics result, formed in float64 from its exact integers (QueryResult.window_stats
     calls this; `stats` (Q, G) and `pairs` (Q, P) are its structured arrays, `group_sizes` the G sizes in samples).  With n a
@@ -1091,6 +1108,60 @@ class QueryResult:
         return (int(pm.value or 0), int(pk.value or 0), int(pc.value or 0), int(a.value), int(c.value),
                 "king" if st.value == self.IBS_STATS["king"] else "counts")
 
+    TRIO_DTYPE = np.dtype([("errors", "<u4"), ("denovo", "<u4"), ("transmitted", "<u4"), ("untransmitted", "<u4")])   # vs_trio_counts
+
+    def trio_scan(self):
+        """A trio result (VariantStore.trio_scan) as numpy arrays.  `row_stats` (structured: errors, denovo, transmitted,
+        untransmitted, uint32; row_stats[i] belongs to rows[i] and sums over all trios), `trio_stats` (the same per trio, summed
+        over every table row once), `n_used` (a Python int: the table's rows minus those the duplicate rule dropped), `tdt_chi2`
+        (float64 per row, (T - U)**2 / (T + U) of the row's transmitted and untransmitted counts: each integer converted once, one
+        multiplication, one division; NaN where T + U == 0), `error_rate` (float64 per trio, errors / n_used; NaN at n_used == 0),
+        `columns` (uint32[n], the distinct member ids, ascending), `trio_cols` ((n_trios, 3) uint32: the columns of child, father,
+        mother), `trio_ids` (the same as sample ids), `counts` (structured as for allele_counts: the count record of every table row
+        over the members), the table's `rows` and per region `row_begin` and `row_count`.  Copies, valid after the result is
+        closed."""
+        a, c, t, nu = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        cols, tc = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
+        cnt = C.POINTER(_lib.AlleleCounts)()
+        pr, pt = C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_get_trio_scan(self._h, C.byref(a), C.byref(c), C.byref(t), C.byref(nu), C.byref(cols), C.byref(tc),
+                                                 C.byref(cnt), C.byref(pr), C.byref(pt)), "vs_result_get_trio_scan")
+        na, nc, nt, n_used = int(a.value), int(c.value), int(t.value), int(nu.value)
+
+        def records(p, n):
+            if not n:
+                return np.zeros(0, self.TRIO_DTYPE)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n * 16,)).view(self.TRIO_DTYPE).copy()
+        row_stats, trio_stats = records(pr, na), records(pt, nt)
+        counts = records(cnt, na).view(self.COUNT_DTYPE)
+        columns = np.ctypeslib.as_array(cols, shape=(nc,)).copy()
+        trio_cols = np.ctypeslib.as_array(tc, shape=(nt, 3)).copy()
+        raw = self.raw(with_carriers=False)
+        return {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+                "columns": columns, "trio_cols": trio_cols, "trio_ids": columns[trio_cols], "counts": counts, "row_stats": row_stats,
+                "trio_stats": trio_stats, "n_used": n_used, "tdt_chi2": trio_tdt_chi2(row_stats), "error_rate": trio_error_rate(trio_stats, n_used)}
+
+    def region_trio_stats(self, q, scan=None):
+        """Region q of a trio result: a dict of views into `scan` (trio_scan() of this result; taken now when None) -- `row_stats`,
+        `tdt_chi2`, `rows` and `counts` of the region's table rows."""
+        got = self.trio_scan() if scan is None else scan
+        q = int(q)
+        if not 0 <= q < got["row_begin"].shape[0]:
+            raise IndexError(f"region {q} of {got['row_begin'].shape[0]}")
+        a0, m = int(got["row_begin"][q]), int(got["row_count"][q])
+        return {k: got[k][a0:a0 + m] for k in ("row_stats", "tdt_chi2", "rows", "counts")}
+
+    def trio_scan_device(self):
+        """A trio result as it lies in this GPU's memory: a dict of the addresses `rows` (n_rows records of four uint32), `trios`
+        (n_trios records, right behind them), `n_used` (one uint64) and `counts` (n_rows records of four uint32), with `n_rows`,
+        `n_cols` and `n_trios`; complete when this returns and valid until the result is closed."""
+        a, c, t = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        pc, pr, pt, pu = (C.c_void_p() for _ in range(4))
+        _check(self._lib.vs_result_trio_scan_device(self._h, C.byref(a), C.byref(c), C.byref(t), C.byref(pc), C.byref(pr), C.byref(pt),
+                                                    C.byref(pu)), "vs_result_trio_scan_device")
+        return {"rows": int(pr.value or 0), "trios": int(pt.value or 0), "n_used": int(pu.value or 0), "counts": int(pc.value or 0),
+                "n_rows": int(a.value), "n_cols": int(c.value), "n_trios": int(t.value)}
+
     def region_variants(self, q) -> List[Variant]:
         out = []
         for line in self.region_text(q).split("\n")[1:]:
@@ -1519,6 +1590,33 @@ class VariantStore:
             stat = QueryResult.IBS_STATS[stat.lower()]
         ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
         _check(self._lib.vs_query_sample_ibs(self._h, ptr, n, ids_ptr, n_ids, int(stat) & 0xFFFFFFFF, C.byref(h)), "vs_query_sample_ibs")
+        return QueryResult(self, h)
+
+    def trio_ids(self, trios):
+        """`trios` -- a sequence of (child, father, mother), each a name or an id, or an (n, 3) integer array -- as the contiguous
+        (n, 3) uint32 array of sample ids the C ABI takes."""
+        if isinstance(trios, np.ndarray) and trios.dtype.kind in "ui":
+            ids = np.ascontiguousarray(trios, dtype=np.uint32)
+        else:
+            ids = np.ascontiguousarray([[self.sample_id(x) if isinstance(x, str) else int(x) for x in t] for t in trios], dtype=np.uint32)
+        if ids.size == 0:
+            return ids.reshape(0, 3)
+        if ids.ndim != 2 or ids.shape[1] != 3:
+            raise ValueError("trios: (child, father, mother) triples expected")
+        return ids
+
+    def trio_scan(self, regions, trios) -> QueryResult:
+        """Trio scan over regions (vs_query_trio_scan): for every row of the variant table a type-6 batch over `regions` produces
+        and every trio, whether the three dosages obey Mendel's laws and which alleles heterozygous parents transmitted -- summed
+        per row over the trios and per trio over the rows, exact uint32: errors, de novo calls, transmitted and untransmitted
+        alleles.  `trios`: a sequence of (child, father, mother), each a name or an id, or an (n, 3) integer array; a sample may
+        appear in any number of trios and in any role.  Meant for diploid calls (only the dosage takes part).  `regions` as for
+        allele_counts.  Read the result with QueryResult.trio_scan / region_trio_stats / trio_scan_device."""
+        arr, ptr, n = _regions_array(regions)
+        ids = self.trio_ids(trios)
+        h = C.c_void_p()
+        _check(self._lib.vs_query_trio_scan(self._h, ptr, n, _u32_ptr(ids) if ids.size else None, ids.shape[0], C.byref(h)),
+               "vs_query_trio_scan")
         return QueryResult(self, h)
 
     def assoc_scan(self, regions, traits, samples=None, stat="dot", trait_names=None) -> QueryResult:

@@ -114,7 +114,7 @@ bool dir_exists(const std::string& p) {
 }
 
 struct Args {
-  std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out, samples_file, groups_file, pheno_file, weights_file;
+  std::string cmd, ref, vcf, prefix, region, outfile, sample, alt, refseq, batch_out, samples_file, groups_file, pheno_file, weights_file, trios_file;
   uint32_t min_ac = 0, max_ac = UINT32_MAX;   // `burden`: the alternate-allele-count window of the rows that count
   uint32_t ld_window = 64;   // `ld`: every row against the next ld_window rows; --dot: dot products instead of r^2
   bool ld_dot = false;
@@ -124,6 +124,7 @@ struct Args {
   bool gram_grm = false;      // `gram`: the GRM (float64) instead of the dosage products (int64)
   bool ibs_king = false;      // `ibs`: the kinship column beside the counts; --min-kinship X: only pairs with kinship >= X (implies --king)
   bool ibs_have_min = false;
+  bool trios_per_trio = false;   // `trios`: one table over the batch, a line per trio, instead of the regions' rows
   double ibs_min_kinship = 0.0;
   bool assoc_chi2 = false;   // `assoc`: the score test instead of the dot products
   bool windows_no_pairs = false, windows_derived = false;   // `windows`: no pair records; pi, theta, Tajima's D, dxy and Fst beside the integers
@@ -1277,6 +1278,97 @@ int ibs_main(const Args& a) {
   return EXIT_SUCCESS;
 }
 
+// `variantstore trios`: Mendelian errors and transmission counts of the regions' variant table (vs_query_trio_scan).  Output as
+// `counts`: "#region <i> <x>:<y>", then the region's text ("Pos Ref Alt AC Errors DeNovo T U", a line per reported row); with
+// --per-trio instead one table over the whole batch, "Child Father Mother N Errors DeNovo T U", a line per trio in the file's order.
+int trios_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore trios -p <output-prefix> -r <region> -T <trio-file> [--per-trio] [-o <outfile>] [--device <n>]\n\n"
+               "        For every variant query type 6 reports in the regions, over the trios of the file: Errors, the trios whose\n"
+               "        three genotypes break Mendel's laws; DeNovo, those of them whose parents both lack the allele; T and U, the\n"
+               "        alleles heterozygous parents transmitted and did not transmit (the counts of the transmission disequilibrium\n"
+               "        test).  With --per-trio the same four per trio, summed over the variants (each once; N of them).  The file\n"
+               "        has a line per trio: three names, child father mother, or a PED/FAM line of six or more fields (FID IID PAT\n"
+               "        MAT ...), where lines whose PAT or MAT is 0 are skipped.  Meant for diploid calls.\n";
+  return EXIT_FAILURE;
+}
+
+// The trios of a file as sample ids, three per trio: false, with the error reported, when the file cannot be read, a line has
+// neither three nor six or more fields, a name is not a sample of the index, or no trio is left.  `founders`: the PED lines skipped
+// (their number goes to stderr).
+bool read_trios(vs_index* idx, const std::string& path, std::vector<uint32_t>& ids, size_t& founders) {
+  std::ifstream in(path);
+  if (!in) { error("cannot open trio file " + path); return false; }
+  std::string line;
+  size_t lineno = 0;
+  while (std::getline(in, line)) {
+    ++lineno;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    std::istringstream ls(line);
+    std::vector<std::string> f;
+    for (std::string w; ls >> w;) f.push_back(w);
+    if (f.empty() || f[0][0] == '#') continue;
+    if (f.size() != 3 && f.size() < 6) {
+      error("trio file line " + std::to_string(lineno) + ": expected \"child father mother\" or a PED line \"FID IID PAT MAT ...\" of six or more fields");
+      return false;
+    }
+    const bool ped = f.size() >= 6;
+    if (ped && (f[2] == "0" || f[3] == "0")) { ++founders; continue; }
+    for (const std::string& name : {f[ped ? 1 : 0], f[ped ? 2 : 1], f[ped ? 3 : 2]}) {
+      uint32_t sid = 0;
+      if (vs_index_sample_id(idx, name.c_str(), &sid) != VS_OK || sid == 0) { error("Sample not found: " + name); return false; }
+      ids.push_back(sid);
+    }
+  }
+  if (founders) std::cerr << "skipped " << founders << " line(s) of " << path << " without both parents\n";
+  if (ids.empty()) { error("no trios in " + path); return false; }
+  return true;
+}
+
+int trios_main(const Args& a) {
+  vs_index* idx = nullptr;
+  int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
+  if (rc != VS_OK) die(rc, "load");
+  std::vector<uint32_t> ids;
+  size_t founders = 0;
+  if (!read_trios(idx, a.trios_file, ids, founders)) { vs_index_close(idx); return EXIT_FAILURE; }
+  std::vector<vs_region> batch;
+  for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
+  vs_result* res = nullptr;
+  rc = vs_query_trio_scan(idx, batch.data(), batch.size(), ids.data(), ids.size() / 3, &res);
+  if (rc != VS_OK) die(rc, "trios");
+  std::ofstream file;
+  if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
+  std::ostream& out = a.outfile.empty() ? std::cout : file;
+  if (a.trios_per_trio) {
+    uint64_t n_trios = 0, n_used = 0;
+    const vs_trio_counts *rows = nullptr, *trios = nullptr;
+    rc = vs_result_get_trio_scan(res, nullptr, nullptr, &n_trios, &n_used, nullptr, nullptr, nullptr, &rows, &trios);
+    if (rc != VS_OK) die(rc, "trios");
+    out << "Child\tFather\tMother\tN\tErrors\tDeNovo\tT\tU\n";
+    for (uint64_t t = 0; t < n_trios; ++t) {
+      for (int k = 0; k < 3; ++k) {
+        const char* nm = vs_index_sample_name(idx, ids[3 * t + k]);
+        out << (nm ? nm : "?") << '\t';
+      }
+      out << n_used << '\t' << trios[t].errors << '\t' << trios[t].denovo << '\t' << trios[t].transmitted << '\t' << trios[t].untransmitted << '\n';
+    }
+  } else {
+    for (size_t i = 0; i < batch.size(); ++i) {
+      const char* text = nullptr;
+      uint64_t len = 0;
+      rc = vs_result_format_region(res, i, &text, &len);
+      if (rc != VS_OK) die(rc, "result");
+      out << "#region " << i << " " << batch[i].x << ":" << batch[i].y << "\n";
+      out.write(text, len);
+    }
+  }
+  out.flush();
+  vs_result_free(res);
+  vs_index_close(idx);
+  return EXIT_SUCCESS;
+}
+
 // `variantstore ldmatrix`: the full LD block of every region (vs_query_ld_matrix) over the same samples.  Output as `counts`:
 // "#region <i> <x>:<y>", then the region's text (a header of the reported rows' <Pos>:<Ref>:<Alt>, then one line per row with its
 // r^2 -- or with --dot its dot product -- against every one of them).
@@ -1477,7 +1569,7 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "prune" || a.cmd == "clump" || a.cmd == "ldscore" || a.cmd == "groups" || a.cmd == "windows" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "prune" || a.cmd == "clump" || a.cmd == "ldscore" || a.cmd == "groups" || a.cmd == "windows" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs" || a.cmd == "trios") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
       else if ((a.cmd == "burden" || a.cmd == "prune" || a.cmd == "ldscore") && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if ((a.cmd == "burden" || a.cmd == "prune" || a.cmd == "ldscore") && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
@@ -1500,6 +1592,8 @@ int main(int argc, char** argv) {
         a.prune_threshold = (uint32_t)std::floor(r2 * 1048576.0 + 0.5);
       }
       else if (a.cmd == "gram" && f == "--grm") a.gram_grm = true;
+      else if (a.cmd == "trios" && (f == "-T" || f == "--trios")) a.trios_file = need(i);
+      else if (a.cmd == "trios" && f == "--per-trio") a.trios_per_trio = true;
       else if (a.cmd == "ibs" && f == "--king") a.ibs_king = true;
       else if (a.cmd == "ibs" && f == "--min-kinship") {
         const std::string v = need(i);
@@ -1515,7 +1609,7 @@ int main(int argc, char** argv) {
       else if ((a.cmd == "assoc" || a.cmd == "assocmatrix") && (f == "-P" || f == "--phenotypes")) a.pheno_file = need(i);
       else if ((a.cmd == "assoc" || a.cmd == "assocmatrix") && f == "--chi2") a.assoc_chi2 = true;
       else if ((a.cmd == "score" || a.cmd == "scorematrix") && (f == "-W" || f == "--weights")) a.weights_file = need(i);
-      else if (a.cmd != "groups" && a.cmd != "windows" && a.cmd != "assoc" && a.cmd != "assocmatrix" && (f == "-S" || f == "--samples")) a.samples_file = need(i);
+      else if (a.cmd != "groups" && a.cmd != "windows" && a.cmd != "assoc" && a.cmd != "assocmatrix" && a.cmd != "trios" && (f == "-S" || f == "--samples")) a.samples_file = need(i);
       else if (f == "-o" || f == "--output_file") a.outfile = need(i);
       else if (f == "--device") a.device = atoi(need(i).c_str());
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
@@ -1584,6 +1678,10 @@ int main(int argc, char** argv) {
   if (a.cmd == "ibs") {
     if (a.prefix.empty() || a.region.empty()) return ibs_usage();
     return ibs_main(a);
+  }
+  if (a.cmd == "trios") {
+    if (a.prefix.empty() || a.region.empty() || a.trios_file.empty()) return trios_usage();
+    return trios_main(a);
   }
   if (a.cmd == "construct") {
     if (a.ref.empty() || a.vcf.empty() || a.prefix.empty()) return usage();

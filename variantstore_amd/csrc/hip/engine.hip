@@ -96,6 +96,7 @@ struct EngineOpts {
   uint32_t gram_chunk = 0;      // table rows one workgroup of k_sample_gram sums: 0 = by the batch's shape (gram_chunk_rows), else 64..65536
   uint32_t score_matrix_chunk = 0;   // table rows one workgroup of k_score_matrix sums: 0 = by the batch's shape (score_matrix_chunk_rows), else a multiple of 128 in 128..65536
   uint32_t ibs_chunk = 0;       // table rows one workgroup of k_sample_ibs sums: 0 = by the batch's shape (ibs_chunk_rows), else 64..65536
+  uint32_t trio_chunk = 0;      // trios one workgroup of k_trio_scan takes: 0 = by the batch's shape (trio_chunk_trios), else a multiple of 64 in 64..16384
   uint32_t matrix_tile_cols = 0;   // column tile of the matrix kernel: 0 = kMatrixTileCols, else a multiple of 16 in 16..65536
   int fill_mode = 0;            // shared expansion: 0 one launch, 2 split (lists + rows, then the dense sites: what a profiler wants to see apart)
   uint32_t fill_dense_k = 16;   // dense sites per wave of k_fill_dense: 8 / 16 / 32 / 64
@@ -250,7 +251,7 @@ struct vs_result {
                  // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM; kKindIbs: pairwise IBS counts / KING kinship;
                  // kKindLdMatrix: the full LD block of every region; kKindAssocMatrix: trait-matrix association scan;
                  // kKindScoreMatrix: score matrix; kKindPrune: LD pruning verdicts; kKindClump: p-value clumping verdicts; kKindLdScore: LD scores;
-                 // kKindWindowStats: windowed diversity statistics
+                 // kKindWindowStats: windowed diversity statistics; kKindTrio: Mendelian errors and transmission counts per row and trio
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -353,6 +354,14 @@ struct vs_result {
   long long* d_ibs = nullptr;
   size_t ibs_king_off = 0, ibs_words = 0;
   uint32_t ibs_stat = 0;
+  // trio results (vs_query_trio_scan): one buffer in HBM (d_trio) -- a record of 16 bytes per table row, one per trio, n_used (8 bytes),
+  // the nonzero cells of the (temporary) genotype matrix (d_cell_total, two words), then from trio_table_off on the trio table, three
+  // column indices of four bytes per trio -- copied to cells_pin in one piece (trio_bytes); the count record of every table row in
+  // d_counts / counts_pin, the member ids h_cols
+  uint8_t* d_trio = nullptr;
+  uint64_t n_trios = 0;
+  size_t trio_table_off = 0, trio_bytes = 0;
+  std::vector<uint32_t> h_trio_cols;   // the table as the batch uploads it
   // sequence results (query types 2 and 3)
   DevSeqResult sq{};
   uint64_t seq_bytes = 0;
@@ -379,9 +388,10 @@ constexpr int kKindScoreMatrix = 19;   // ... of a score-matrix result: the rows
 constexpr int kKindPrune = 20;   // ... of a pruning result: the rows of type 6, a verdict byte per reported row instead of carrier lists
 constexpr int kKindLdScore = 22;   // ... of an LD-score result: the rows of type 6, a sum, a pair count and a state byte per reported row instead of carrier lists
 constexpr int kKindWindowStats = 23;   // ... of a window-statistics result: the rows of type 6, a record per region and sample group (and pair of groups) instead of carrier lists
+constexpr int kKindTrio = 24;    // ... of a trio result: the rows of type 6, a record of Mendelian errors and transmission counts per row and per trio instead of carrier lists
 constexpr int kKindClump = 21;   // ... of a clumping result: the rows of type 6, a verdict byte and an owner per reported row instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindWindowStats || r->kind == kKindLdScore || r->kind == kKindClump || r->kind == kKindPrune || r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
+  return r->kind == kKindTrio || r->kind == kKindWindowStats || r->kind == kKindLdScore || r->kind == kKindClump || r->kind == kKindPrune || r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
          r->kind == kKindScores;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
@@ -400,6 +410,8 @@ static int refuse_no_lists(const vs_result* r, const char* what) {
     return fail(VS_ERR_UNSUPPORTED, "%s: a Gram result holds a samples x samples matrix of dosage products, no carrier lists (vs_result_get_sample_gram)", what);
   if (r->kind == kKindIbs)
     return fail(VS_ERR_UNSUPPORTED, "%s: an IBS result holds samples x samples matrices of genotype-state counts, no carrier lists (vs_result_get_sample_ibs)", what);
+  if (r->kind == kKindTrio)
+    return fail(VS_ERR_UNSUPPORTED, "%s: a trio result holds a record of Mendelian errors and transmission counts per row and per trio, no carrier lists (vs_result_get_trio_scan)", what);
   if (r->kind == kKindLdMatrix)
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD-matrix result holds a square block of pair statistics per region, no carrier lists (vs_result_get_ld_matrix)", what);
   if (r->kind == kKindClump)
@@ -1280,7 +1292,9 @@ static int capture_totals(vs_result* r) {
 // the number of table rows once the plan has given it; clump_key: the keys of p1 and p2.
 // LdScore: as Prune without the threshold; ld_window = 0 stands for no row limit.
 // WindowStats: mask and n_cols as for Groups; ws_sizes: the groups' sizes (n_cols of them), ws_pairs: the pair records (0: none).
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix, Prune, Clump, LdScore, WindowStats };
+// Trio: mask, rank and n_cols as for the matrix (the members); trio_cols (host memory, owned by the result): three column indices
+// per trio -- child, father, mother --, n_trios of them.
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix, Prune, Clump, LdScore, WindowStats, Trio };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1302,6 +1316,8 @@ struct SharedReq {
   const std::vector<int32_t>* sm_shift = nullptr;
   const uint32_t* ws_sizes = nullptr;
   uint32_t ws_pairs = 0;
+  const uint32_t* trio_cols = nullptr;
+  uint64_t n_trios = 0;
   bool window() const { return min_ac != 0 || max_ac != UINT32_MAX; }
 };
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
@@ -1652,6 +1668,59 @@ static int launch_ibs(vs_index* idx, vs_result* r, const uint8_t* cells, uint64_
   return VS_OK;
 }
 
+// Trios one workgroup of k_trio_scan takes.  Option trio_chunk, or by the batch's shape: all of them -- every chunk stages the block's
+// rows again -- unless the row blocks alone give fewer than kTrioBlocksWanted workgroups; then as many chunks as reach that number,
+// of at least four slabs of 64 (one per wave).  At most kTrioChunkMax, a multiple of 64.
+static uint32_t trio_chunk_trios(const vs_index* idx, uint64_t row_blocks, uint64_t n_trios) {
+  if (idx->opts.trio_chunk) return idx->opts.trio_chunk;
+  const uint64_t slabs = (n_trios + 63) / 64;
+  const uint64_t want = std::max<uint64_t>(1, (kTrioBlocksWanted + row_blocks - 1) / std::max<uint64_t>(row_blocks, 1));
+  const uint64_t per = std::min<uint64_t>(kTrioChunkMax / 64, std::max<uint64_t>(4, (slabs + want - 1) / want));
+  return (uint32_t)(std::min(per, slabs) * 64);
+}
+template <uint32_t R>
+static int launch_trio_r(vs_index* idx, const TrioArgs& a, unsigned blocks) {
+  const size_t lds = (size_t)R * a.pitch;
+  if (lds > (48 << 10)) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_trio_scan<R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trio_scan<R>), dim3(blocks), dim3(256), lds, idx->stream, a);
+  HIP_TRY(hipGetLastError());
+  return VS_OK;
+}
+// The records of a trio batch from its temporary genotype matrix and the table's counts: both record arrays and n_used cleared, the
+// trio table uploaded (trio_upload, in front of the pair of events), k_ibs_n_used over the table's rows, k_trio_scan over (row block,
+// trio chunk).  (launch_matrix, in front of this, has cleared and filled d_cell_total.)
+static int launch_trio(vs_index* idx, vs_result* r, const uint8_t* cells, uint64_t U, const SharedReq& tq) {
+  const DevResult& d = r->d;
+  HIP_TRY(hipMemsetAsync(r->d_trio, 0, (size_t)(d.A + tq.n_trios) * 16 + 8, idx->stream));
+  if (!d.A) return VS_OK;   // an empty table: all-zero records, n_used = 0
+  IbsArgs u{};
+  u.m.A = d.A; u.rows = (const VariantRow*)d.rows; u.U = U;
+  u.n_used = reinterpret_cast<unsigned long long*>(r->d_trio + (size_t)(d.A + tq.n_trios) * 16);
+  hipLaunchKernelGGL(k_ibs_n_used, dim3((unsigned)std::min<uint64_t>((d.A + 1023) / 1024, 1024)), dim3(256), 0, idx->stream, u);
+  TrioArgs a{};
+  a.cells = cells; a.A = d.A; a.pitch = (uint32_t)r->mx_pitch; a.n_cols = tq.n_cols;
+  a.counts = r->d_counts;
+  a.trio_cols = reinterpret_cast<const uint32_t*>(r->d_trio + r->trio_table_off);
+  a.n_trios = (uint32_t)tq.n_trios;
+  a.rows = reinterpret_cast<uint32_t*>(r->d_trio);
+  a.trios = a.rows + 4 * d.A;
+  uint32_t R = kTrioRowsMax;   // the largest power of two up to min(kTrioRowsMax, kTrioTileBytes / pitch), at least 1
+  while (R > 1 && (uint64_t)R * a.pitch > kTrioTileBytes) R >>= 1;
+  const uint64_t row_blocks = (d.A + R - 1) / R;
+  a.chunk = trio_chunk_trios(idx, row_blocks, tq.n_trios);
+  a.n_chunks = (uint32_t)((tq.n_trios + a.chunk - 1) / a.chunk);
+  const uint64_t blocks = row_blocks * a.n_chunks;
+  if (blocks > 0x7FFFFFFFull)
+    return fail(VS_ERR_ARG, "batch too large for one launch (%llu row blocks x %u trio chunks)", (unsigned long long)row_blocks, a.n_chunks);
+  switch (R) {
+    case 16: return launch_trio_r<16>(idx, a, (unsigned)blocks);
+    case 8: return launch_trio_r<8>(idx, a, (unsigned)blocks);
+    case 4: return launch_trio_r<4>(idx, a, (unsigned)blocks);
+    case 2: return launch_trio_r<2>(idx, a, (unsigned)blocks);
+    default: return launch_trio_r<1>(idx, a, (unsigned)blocks);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Query type 6 over a batch whose regions SHARE rows and carrier lists (every batch of more than 64 regions unless option
 // share_lists is 0), and every count, grouped-count, burden, genotype-matrix, LD, Gram and IBS batch: the same plan and rows, another consumer (SharedReq).
@@ -1677,6 +1746,7 @@ static int launch_ibs(vs_index* idx, vs_result* r, const uint8_t* cells, uint64_
 //                      LD: k_allele_counts over the table, k_genotype_matrix into the temporary, k_ld_band over blocks of table rows |
 //                      Gram: the same two, then k_sample_gram, k_gram_moments and (GRM) k_gram_finish (launch_gram) |
 //                      Ibs: the same two, then k_ibs_n_used, k_sample_ibs and k_ibs_finish (launch_ibs) |
+//                      Trio: the same two, then k_ibs_n_used and k_trio_scan (launch_trio); the trio table goes up in front of them |
 //                      LdMatrix: in front of them k_ld_block_scan over the per-region row counts and one host wait for its totals
 //                      (ld_matrix_tables: the size limit, the temporary matrix, the cells); behind them k_ld_block (launch_ld_block)
 //                      Prune: in front of them k_prune_scan over the per-region row counts and one host wait for its total
@@ -1733,7 +1803,7 @@ struct SharedCtx {
   uint64_t* am_dev = nullptr;   // shared_tables: a trait-matrix batch's Sy, vy, shifts and limb panel on the device (ld_tmp)
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix || q.kind == ReqKind::Prune || q.kind == ReqKind::Clump || q.kind == ReqKind::LdScore || q.kind == ReqKind::WindowStats) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix || q.kind == ReqKind::Prune || q.kind == ReqKind::Clump || q.kind == ReqKind::LdScore || q.kind == ReqKind::WindowStats || q.kind == ReqKind::Trio) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -2075,6 +2145,25 @@ static int ldscore_fits(SharedCtx& c, uint64_t slots) {
               (unsigned long long)r->d.Q, (unsigned long long)r->d.A, c.req.n_cols, (unsigned long long)(r->d.A * r->mx_pitch + slots * 13 + region_bytes),
               (unsigned long long)(r->d.A * r->mx_pitch), (unsigned long long)(slots * 13), (unsigned long long)region_bytes, (unsigned long long)(cap >> 20));
 }
+// A trio batch: the temporary matrix, the count records, both record arrays and the trio table together, under the same limit; and
+// a table of 2^31 rows or more is refused, because a per-trio sum (at most 2 a row) must fit uint32.
+static int trio_fits(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  r->mx_pitch = ((uint64_t)c.req.n_cols + 15) & ~15ull;
+  const uint64_t trio_part = c.req.n_trios * 28, row_bytes = r->mx_pitch + 32;   // (at most 2^20 trios)
+  const bool rows_fit = r->d.A < (1ull << 31);
+  if (rows_fit && trio_part <= cap && r->d.A <= (cap - trio_part) / row_bytes) return VS_OK;
+  (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+  (void)hipStreamSynchronize(idx->stream);
+  if (!rows_fit)
+    return fail(VS_ERR_ARG, "a trio scan over %llu rows: a trio's sums are 32-bit, the table may have at most 2^31 - 1 rows: split the batch", (unsigned long long)r->d.A);
+  return fail(VS_ERR_ARG, "a trio scan of %llu rows x %u columns x %llu trios takes %llu bytes (%llu of the genotype matrix it is formed from, %llu of the count "
+              "records, %llu of the records per row, %llu of the records per trio, %llu of the trio table), more than the limit of %llu MiB (option matrix_max_mib): "
+              "split the batch or the trios", (unsigned long long)r->d.A, c.req.n_cols, (unsigned long long)c.req.n_trios,
+              (unsigned long long)(r->d.A * row_bytes + trio_part), (unsigned long long)(r->d.A * r->mx_pitch), (unsigned long long)(r->d.A * 16),
+              (unsigned long long)(r->d.A * 16), (unsigned long long)(c.req.n_trios * 16), (unsigned long long)(c.req.n_trios * 12), (unsigned long long)(cap >> 20));
+}
 // Reads the totals (*pt) or the speculation.  Leaves U / n_slow / n_runs, the result's sizes and bookkeeping, a speculative batch
 // registered with its slot, what the request's kind allocates, and the form of the rows and the expansion (n_fill .. lean).
 static int shared_tables(SharedCtx& c) {
@@ -2174,6 +2263,19 @@ static int shared_tables(SharedCtx& c) {
       VS_TRY(ralloc(r, r->ibs_words, &r->d_ibs));
       r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_ibs + head);
       r->ibs_stat = q.ibs_stat;
+      break;
+    }
+    case ReqKind::Trio: {   // (n_used and the matrix kernel's count of nonzero cells live behind the records, the trio table behind them)
+      VS_TRY(trio_fits(c));
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(dev_alloc(idx, (size_t)(d.A * r->mx_pitch), (void**)&c.ld_matrix, &c.ld_tmp.bufs));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      const size_t head = (size_t)(d.A + q.n_trios) * 16 + 8;
+      r->trio_table_off = (head + 16 + 15) & ~(size_t)15;
+      r->trio_bytes = r->trio_table_off + (size_t)q.n_trios * 12;
+      VS_TRY(ralloc(r, r->trio_bytes, &r->d_trio));
+      r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_trio + head);
+      r->n_trios = q.n_trios;
       break;
     }
     case ReqKind::AssocMatrix: {   // (the traits' words and the limb panel are temporaries like the matrix: the kernel alone reads them)
@@ -2356,13 +2458,15 @@ static int shared_columns(SharedCtx& c) {
   if (c.req.kind == ReqKind::Prune) VS_TRY(prune_tables(c));   // (its one host wait in front of the pair of events as well)
   if (c.req.kind == ReqKind::Clump) VS_TRY(clump_tables(c));   // (the same wait, and the upload of the keys)
   if (c.req.kind == ReqKind::LdScore) VS_TRY(ldscore_tables(c));   // (the same wait)
+  if (c.req.kind == ReqKind::Trio)   // (the trio table's upload in front of the pair of events as well)
+    HIP_TRY(hipMemcpyAsync(r->d_trio + r->trio_table_off, c.req.trio_cols, (size_t)c.req.n_trios * 12, hipMemcpyHostToDevice, idx->stream));
   VS_TRY(result_events(r));
   HIP_TRY(hipEventRecord(r->ev_fill[0], idx->stream));
   if (c.req.kind == ReqKind::Groups) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, r->d_counts);
   else if (c.req.kind == ReqKind::WindowStats) {   // (a table without rows: no group kernel, the records are zeros all the same)
     if (r->d.A) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, c.ws_counts);
     VS_TRY(launch_window_stats(c));
-  } else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD, Gram, Ibs, ScoreMatrix; Burden only under a window: shared_tables gives it counts)
+  } else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD, Gram, Ibs, Trio, ScoreMatrix; Burden only under a window: shared_tables gives it counts)
     launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
   HIP_TRY(hipGetLastError());
   if (c.req.kind == ReqKind::Assoc) VS_TRY(launch_assoc(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.d_pheno, c.req));
@@ -2393,6 +2497,9 @@ static int shared_columns(SharedCtx& c) {
   } else if (c.req.kind == ReqKind::Ibs) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_ibs(idx, r, c.ld_matrix, c.U, c.req));
+  } else if (c.req.kind == ReqKind::Trio) {
+    VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+    VS_TRY(launch_trio(idx, r, c.ld_matrix, c.U, c.req));
   } else if (c.req.kind == ReqKind::Matrix) VS_TRY(launch_matrix(idx, r, r->d_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
   HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
   r->pending = true;
@@ -4204,6 +4311,10 @@ int vs_index_set_option(vs_index* idx, const char* key, int64_t value) {
   } else if (k == "ibs_chunk") {
     if (value != 0 && (value < 64 || value > kIbsChunkMax)) return fail(VS_ERR_ARG, "ibs_chunk takes 0 (default: by the batch's shape) or 64..%u rows", kIbsChunkMax);
     o.ibs_chunk = (uint32_t)value;
+  } else if (k == "trio_chunk") {
+    if (value != 0 && (value < 64 || value > kTrioChunkMax || value % 64))
+      return fail(VS_ERR_ARG, "trio_chunk takes 0 (default: by the batch's shape) or a multiple of 64 in 64..%u trios", kTrioChunkMax);
+    o.trio_chunk = (uint32_t)value;
   } else if (k == "score_tile_cols") {
     if (value != 0 && (value < 16 || value > 65536 || value % 16)) return fail(VS_ERR_ARG, "score_tile_cols takes 0 (default) or a multiple of 16 in 16..65536");
     o.score_tile_cols = (uint32_t)value;
@@ -4870,6 +4981,40 @@ int vs_query_sample_ibs(vs_index* idx, const vs_region* regions, uint64_t n, con
   });
 }
 
+int vs_query_trio_scan(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* trios, uint64_t n_trios, vs_result** out) {
+  VS_TRY(column_query_args(idx, out, regions, n, nullptr, 0, "a trio"));
+  if (!trios) return fail(VS_ERR_ARG, "null argument: a trio batch takes three sample ids per trio (trios)");
+  if (n_trios == 0 || n_trios > VS_TRIOS_MAX) return fail(VS_ERR_ARG, "a trio batch of %llu trios (1 .. %u)", (unsigned long long)n_trios, VS_TRIOS_MAX);
+  const uint32_t ns = idx->g.num_samples;
+  for (uint64_t t = 0; t < n_trios; ++t) {
+    const uint32_t c = trios[3 * t], f = trios[3 * t + 1], m = trios[3 * t + 2];
+    if (c == f || c == m || f == m)
+      return fail(VS_ERR_ARG, "trio %llu names a sample twice (child %u, father %u, mother %u): its three members are distinct", (unsigned long long)t, c, f, m);
+    for (uint32_t id : {c, f, m})
+      if (id == 0 || id >= ns) return fail(VS_ERR_UNKNOWN_SAMPLE, "sample id %u of trio %llu is not a sample of the cohort (1 .. %u)", id, (unsigned long long)t, ns - 1);
+  }
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, trios, 3 * n_trios, mask, rank, cols));
+  if (cols.size() > kTrioTileBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a trio scan over %llu distinct members: a staged row must fit the kernel's LDS tile, at most %u", (unsigned long long)cols.size(), kTrioTileBytes);
+  if (mask.size() * 8 > kMatrixMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", idx->g.num_samples);
+  std::vector<uint32_t> tcols((size_t)(3 * n_trios));   // id -> column: the members in front of the id's mask word and inside it
+  for (size_t i = 0; i < tcols.size(); ++i) {
+    const uint32_t id = trios[i];
+    tcols[i] = rank[id >> 6] + (uint32_t)__builtin_popcountll(mask[id >> 6] & ((1ull << (id & 63)) - 1));
+  }
+  SharedReq req = column_request(ReqKind::Trio, mask, rank, cols.size());
+  req.n_trios = n_trios;
+  return make_result(idx, kKindTrio, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    r->h_trio_cols = std::move(tcols);
+    req.trio_cols = r->h_trio_cols.data();
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
 int vs_query_sample_var_in_ref(vs_index* idx, const vs_region* regions, uint64_t n, uint32_t sample_id, vs_result** out) {
   if (!out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
   VS_TRY(query_handle(idx));
@@ -5223,7 +5368,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
       for (uint64_t i = 0, e = r->d.Q * r->n_groups; i < e; ++i) nc += (w[i].sum_ac + w[i].obs_het) / 2;
       r->n_carriers_kept = nc;
     }
-    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindPrune || r->kind == kKindClump || r->kind == kKindLdScore || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
+    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindPrune || r->kind == kKindClump || r->kind == kKindLdScore || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindTrio || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS, trio: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
       VS_TRY(result_ready(r));
       uint64_t nc = 0;
       HIP_TRY(hipMemcpyAsync(&nc, r->d_cell_total, 8, hipMemcpyDeviceToHost, idx->stream));
@@ -5376,6 +5521,37 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
         } else snprintf(num, sizeof num, "%d\n", (int)cell);
         out += num;
       }
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
+  if (r->kind == kKindTrio) {   // the region's reported rows with their alternate-allele count over the members and their four sums over the trios
+    const VariantRow* rows;
+    if (r->have_headers) rows = r->h_rows.data() + a0;
+    else if (r->raw_rows) rows = r->raw_rows + a0;
+    else {
+      VS_TRY(fetch(idx, r->sl_rows, (const VariantRow*)r->d.rows + a0, (size_t)(a1 - a0)));
+      rows = r->sl_rows.data();
+    }
+    VS_TRY(array_to_host(r, r->d_trio, r->trio_bytes, &r->cells_pin, "trio records"));
+    VS_TRY(counts_to_host(r));
+    HIP_TRY(hipStreamSynchronize(idx->stream));
+    const vs_trio_counts* rec = (const vs_trio_counts*)r->cells_pin.p + a0;
+    const uint4* cnt = (const uint4*)r->counts_pin.p + a0;
+    std::string& out = r->text;
+    out = "Pos\tRef\tAlt\tAC\tErrors\tDeNovo\tT\tU\n";
+    for (uint64_t a = a0; a < a1; ++a) {
+      const VariantRow& v = rows[a - a0];
+      if (v.count_flags & kRowDropped) continue;
+      out += std::to_string(v.pos);
+      out += '\t';
+      out.append(idx->seq_chars, v.ref_off, v.ref_len);
+      out += '\t';
+      out.append(idx->seq_chars, v.alt_off, v.alt_len);
+      const vs_trio_counts& t = rec[a - a0];
+      for (uint32_t f : {cnt[a - a0].y, t.errors, t.denovo, t.transmitted, t.untransmitted}) { out += '\t'; out += std::to_string(f); }
+      out += '\n';
     }
     *text = out.c_str();
     if (len) *len = out.size();
@@ -6240,6 +6416,40 @@ int vs_result_sample_ibs_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols
   if (n_rows) *n_rows = r->d.A;
   if (n_cols) *n_cols = r->h_cols.size();
   if (stat) *stat = r->ibs_stat;
+  return VS_OK;
+}
+
+int vs_result_get_trio_scan(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint64_t* n_trios, uint64_t* n_used, const uint32_t** col_ids,
+                            const uint32_t** trio_cols, const vs_allele_counts** counts, const vs_trio_counts** rows, const vs_trio_counts** trios) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!rows) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindTrio) return fail(VS_ERR_ARG, "not a trio result (vs_query_trio_scan)");
+  static_assert(sizeof(vs_trio_counts) == 16, "record layout of the ABI");
+  VS_TRY(array_to_host(r, r->d_trio, r->trio_bytes, &r->cells_pin, "trio records"));
+  VS_TRY(counts_to_host(r));
+  const uint8_t* base = (const uint8_t*)r->cells_pin.p;
+  *rows = (const vs_trio_counts*)base;
+  if (trios) *trios = (const vs_trio_counts*)base + r->d.A;
+  if (n_used) memcpy(n_used, base + (size_t)(r->d.A + r->n_trios) * 16, 8);
+  if (trio_cols) *trio_cols = r->h_trio_cols.data();
+  if (counts) *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_trios) *n_trios = r->n_trios;
+  if (col_ids) *col_ids = r->h_cols.data();
+  return VS_OK;
+}
+
+int vs_result_trio_scan_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint64_t* n_trios, const void** dev_counts, const void** dev_rows,
+                               const void** dev_trios, const void** dev_n_used) {
+  VS_TRY(device_matrix_ready(r, dev_rows, kKindTrio, "not a trio result (vs_query_trio_scan)"));
+  *dev_rows = r->d_trio;
+  if (dev_trios) *dev_trios = r->d_trio + (size_t)r->d.A * 16;
+  if (dev_n_used) *dev_n_used = r->d_trio + (size_t)(r->d.A + r->n_trios) * 16;
+  if (dev_counts) *dev_counts = r->d_counts;
+  if (n_rows) *n_rows = r->d.A;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_trios) *n_trios = r->n_trios;
   return VS_OK;
 }
 

@@ -109,6 +109,11 @@
 //  k_ibs_n_used         int32 accumulators: the pairwise genotype-state counts D^T D cannot give; the rows the duplicate rule kept;
 //  k_ibs_finish         IBS0 / IBS2 and the KING-robust kinship from exact integers (vs_query_sample_ibs: no reference counterpart;
 //                       DESIGN 5j)
+// k_trio_scan           Mendel's laws over the same dosages: per (child, father, mother) column triple and table row a 27-state look-up
+//                       -- error, de novo, transmitted, untransmitted -- from three LDS byte reads, a block of rows staged per
+//                       workgroup, a lane per trio; per-trio sums in the lane, per-row sums by one halving butterfly a wave,
+//                       32-bit integer atomics: exact and order-free; n_used is k_ibs_n_used's (vs_query_trio_scan: no reference
+//                       counterpart)
 // k_score_matrix        D^T W over the same dosages: samples x K weighted sums (K up to 65,536) over the rows a batch reports, the
 //  k_score_matrix_weights  wide form of k_sample_scores.  The report-keyed weights become per-row totals of fixed-point integers
 //  k_score_matrix_limbs    (64-bit atomics), the totals a panel of four or five int8 limbs; 128 columns x 16 or 32 scores x a chunk
@@ -143,4 +148,5 @@
 #include "k_gram.hip.h"
 #include "k_assoc_matrix.hip.h"
 #include "k_ibs.hip.h"
+#include "k_trio.hip.h"
 #include "k_score_matrix.hip.h"
