@@ -51,6 +51,8 @@ namespace vsamd {
 constexpr uint32_t kTrioRowsMax = 16;          // table rows a workgroup stages at most
 constexpr uint32_t kTrioTileBytes = 64 << 10;  // ... and the bytes of its tile
 constexpr uint32_t kTrioChunkMax = 16384;      // trios a workgroup takes at most: 64 slabs a wave, a lane's per-row field stays below 256
+                                               // (tests/test_gpu_trio_scan_wide.py runs 16,384 trios that all add 2 to one field of one row:
+                                               // 128 a lane, 8,192 a wave, 32,768 a workgroup, and holds that a larger trio_chunk is refused)
 constexpr uint32_t kTrioBlocksWanted = 2048;   // the default chunk splits the trios only while the launch has fewer workgroups than this
 
 struct TrioEntry { uint32_t err, denovo, t, u; };
