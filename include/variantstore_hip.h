@@ -927,6 +927,77 @@ int vs_result_get_trio_scan(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, ui
 int vs_result_trio_scan_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols, uint64_t* n_trios, const void** dev_counts,
                                const void** dev_rows, const void** dev_trios, const void** dev_n_used);
 
+/* Runs of homozygosity over regions: per region and per sample the autozygous stretches, their number and their total length --
+ * what `plink --homozyg` reports and F_ROH is formed from -- found on the GPU by walking every column of the batch's genotype matrix
+ * in row order, without that matrix ever reaching the host.  Everything is an integer.
+ * The variant table, its rows, which of them the duplicate rule dropped and the columns are those of vs_query_genotype_matrix over
+ * the same regions and sample ids: the columns S are the distinct ids ascending, or every sample when sample_ids == NULL.
+ * Site: a table row is a site when the duplicate rule did not drop it, it is polymorphic over the columns -- 0 < ac < 2 n, ac the
+ * row's alt_alleles over S, n the number of columns -- and min_ac <= ac <= max_ac (0 and UINT32_MAX admit every count): the rows
+ * vs_query_ld_prune calls eligible, and a row on which EVERY column is heterozygous besides (its variance is 0, it is a site
+ * here).  Any other row is invisible: it neither extends nor breaks a run.
+ * State: at a site column c is het when its dosage popcount(cell & 6) is 1 and hom when it is 0 or 2.  Only the dosage takes part:
+ * a `1|2` call is dosage 1 on both of its ALT rows, as everywhere here, so it is het on both.
+ * Walk: for region q and column c the sites of q in table order, site i at position p_i, with the run's first, last, n_sites,
+ * n_het and pend:
+ *   gap rule             before site i is looked at: a run is open, max_gap > 0 and p_i - p_(i-1) > max_gap -> close.  p_(i-1) is the
+ *                        previous SITE whatever its state; a difference that would be negative counts as 0
+ *   hom, no run open     open: first = last = i, n_sites = 1, n_het = 0, pend = 0
+ *   hom, run open        n_sites += pend + 1, n_het += pend, pend = 0, last = i
+ *   het, run open        n_het + pend < max_het: pend += 1; otherwise close -- the next run opens at the next hom site, the hets the
+ *                        closed run had absorbed are not looked at again
+ *   het, no run open     nothing
+ *   end of the region    close
+ *   close                pending hets behind `last` are not part of the run.  With bp = max(p_last - p_first, 0) + 1 the run is a
+ *                        SEGMENT when n_sites >= min_sites and bp >= min_bp; otherwise it is discarded
+ * Answer: per (region, column), region-major, a vs_roh_summary -- n_segments; seg_sites, total_bp and seg_hets, the sums of the
+ * segments' n_sites, bp and n_het; longest_bp (saturating at 2^32 - 1) and longest_sites, of the segment of largest bp, the EARLIEST
+ * such on a tie; n_het, the column's het sites in the region, inside segments or not.  Per region n_sites[q].  With segments != 0
+ * also seg_begin [Q S + 1] and the segments: cell (q, c) owns segments[seg_begin[q S + c] .. seg_begin[q S + c + 1]), in order of
+ * occurrence -- so the segments are ordered by region, then column, then occurrence; row_first and row_last are offsets into the
+ * region's row_count rows.  No floating-point value anywhere: the same call gives the same bytes.
+ * `regions` as for vs_query_genotype_matrix.  Checked on the host, in this order, before the handle's device is asked for (a handle
+ * opened without a device reports them first and VS_ERR_NO_DEVICE otherwise): n == 0 -> VS_ERR_ARG; an empty subset -> VS_ERR_ARG;
+ * params == NULL, min_sites == 0, max_het > 255, min_ac > max_ac -> VS_ERR_ARG; then the sample ids as for vs_query_ld_prune (id 0
+ * or id >= num_samples -> VS_ERR_UNKNOWN_SAMPLE).  Once the plan has given the rows and before anything is allocated: a table of
+ * 2^31 rows or more -> VS_ERR_ARG; the temporary genotype matrix (rows x row_pitch bytes, not part of the result), the count records,
+ * the walk's site words, the summaries, the per-cell words and n_sites together may not exceed option "matrix_max_mib" MiB (default
+ * 32 GiB); once the first pass has counted the segments, their 32 bytes each are held to it too.  Beyond it VS_ERR_ARG, and the
+ * message names regions, columns, segments and bytes.
+ * Every batch size takes the batch pipeline; a ROH batch is never speculative and leaves the handle's type-6 state as it was.  The
+ * result holds the type-6 per-region arrays and variant table, no carrier arena, the counts, the summaries and the segments:
+ * vs_result_get_raw / vs_result_get_view with with_carriers = 0, vs_result_layout (arena and lists 0), vs_result_fill_ms (the batch's
+ * own kernels, its one host wait between the passes included) and vs_result_totals (n_carriers = the nonzero cells of the temporary
+ * matrix) work; vs_result_format_region returns region q's segments, a line each, "Sample Pos1 Pos2 KB NSites NHet" (tab-separated,
+ * under that header; KB = bp / 1000 printed from the integer with three decimals) and fails with VS_ERR_ARG when segments == 0;
+ * with_carriers = 1, vs_result_digest, vs_result_pack_headers / _pack_regions and vs_comm_allgather_regions* fail with
+ * VS_ERR_UNSUPPORTED; the other vs_result_get_* accessors fail with VS_ERR_ARG. */
+typedef struct {
+  uint32_t min_sites;   /* a segment has at least this many sites (>= 1) */
+  uint32_t min_bp;      /* ... and spans at least this many bases (0: any) */
+  uint32_t max_gap;     /* two consecutive sites further apart than this close the run (0: no gap rule) */
+  uint32_t max_het;     /* het sites a run may absorb (0 .. 255) */
+  uint32_t min_ac, max_ac;   /* the site window over ac (0 and UINT32_MAX: every count) */
+  uint32_t segments;    /* nonzero: the answer also holds seg_begin and the segments */
+} vs_roh_params;
+typedef struct { uint32_t n_segments, seg_sites; uint64_t total_bp; uint32_t longest_bp, longest_sites, seg_hets, n_het; } vs_roh_summary;
+typedef struct { uint32_t region, column, pos_first, pos_last, row_first, row_last, n_sites, n_het; } vs_roh_segment;
+int vs_query_roh(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, const vs_roh_params* params,
+                 vs_result** out);
+/* A ROH result copied into page-locked memory owned by the result: summary[q * n_cols + c], n_sites[q], col_ids[c] the sample id of
+ * column c, counts[v] the count record of table row v over S, params the batch's own; with segments seg_begin [n_regions * n_cols + 1]
+ * and segments [n_segments], else both NULL and n_segments 0.  Every out-pointer but `summary` may be NULL.  VS_ERR_ARG on any other
+ * result. */
+int vs_result_get_roh(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, uint64_t* n_rows, uint64_t* n_segments, vs_roh_params* params,
+                      const uint32_t** col_ids, const vs_allele_counts** counts, const vs_roh_summary** summary, const uint32_t** n_sites,
+                      const uint64_t** seg_begin, const vs_roh_segment** segments);
+/* The same as it lies in HBM, valid until vs_result_free: dev_summary n_regions * n_cols records of 32 bytes, dev_n_sites n_regions
+ * uint32 behind them, dev_seg_begin n_regions * n_cols + 1 uint64 and dev_segments n_segments records of 32 bytes (both NULL without
+ * segments), dev_counts n_rows count records of 16 bytes.  The engine has synchronised its stream when this returns: the caller
+ * needs no event. */
+int vs_result_roh_device(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, uint64_t* n_rows, uint64_t* n_segments, const void** dev_counts,
+                         const void** dev_summary, const void** dev_n_sites, const void** dev_seg_begin, const void** dev_segments);
+
 /* host view of a sequence result: region i is chars[seq_begin[i] .. seq_begin[i+1]) */
 int vs_result_get_sequences(vs_result* r, uint64_t* n_regions, const uint8_t** region_flags, const uint64_t** seq_begin,
                             const char** chars);

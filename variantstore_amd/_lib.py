@@ -42,6 +42,11 @@ class AlleleCounts(C.Structure):   # vs_allele_counts
     _fields_ = [("carriers", C.c_uint32), ("alt_alleles", C.c_uint32), ("hom_alt", C.c_uint32), ("phased", C.c_uint32)]
 
 
+class RohParams(C.Structure):   # vs_roh_params
+    _fields_ = [("min_sites", C.c_uint32), ("min_bp", C.c_uint32), ("max_gap", C.c_uint32), ("max_het", C.c_uint32),
+                ("min_ac", C.c_uint32), ("max_ac", C.c_uint32), ("segments", C.c_uint32)]
+
+
 class SampleBurden(C.Structure):   # vs_sample_burden
     _fields_ = [("variants", C.c_uint32), ("alt_alleles", C.c_uint32), ("hom_alt", C.c_uint32), ("phased", C.c_uint32)]
 
@@ -164,6 +169,12 @@ SYMBOLS = {
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "vs_result_trio_scan_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "vs_query_roh": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(RohParams), C.POINTER(_P)]),
+    "vs_result_get_roh": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(RohParams),
+                                    C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(AlleleCounts)), C.POINTER(C.c_void_p),
+                                    C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.c_void_p)]),
+    "vs_result_roh_device": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "vs_query_ld_matrix": (C.c_int, [_P, C.POINTER(Region), C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.POINTER(_P)]),
     "vs_result_get_ld_matrix": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                           C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(AlleleCounts)),

@@ -117,6 +117,24 @@ def trio_error_rate(trio_stats, n_used):
     return trio_stats["errors"].astype(np.float64) / float(n_used)
 
 
+def roh_derived(summary, lengths=None):
+    """The derived figures of a ROH result, formed in float64 from its exact integers alone (QueryResult.roh calls this; `summary`
+    is its (Q, S) structured array): `kb` = total_bp / 1000, `kb_avg` = total_bp / (1000 n_segments), NaN in a cell without
+    segments, and -- with `lengths`, one length in bases per region -- `froh` = total_bp / lengths[q] (NaN where the length is 0).
+    Each integer is converted once and each figure is one division."""
+    total = summary["total_bp"].astype(np.float64)
+    nseg = summary["n_segments"].astype(np.float64)
+    out = {"kb": total / 1000.0}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["kb_avg"] = np.where(nseg > 0.0, total / (1000.0 * nseg), np.nan)
+        if lengths is not None:
+            ln = np.asarray(lengths, dtype=np.float64).reshape(-1)
+            if ln.shape[0] != summary.shape[0]:
+                raise ValueError(f"{ln.shape[0]} lengths for {summary.shape[0]} regions")
+            out["froh"] = np.where(ln[:, None] > 0.0, total / ln[:, None], np.nan)
+    return out
+
+
 def window_stats_derived(stats, pairs, group_sizes, lengths=None):
     """The diversity statistics of a window-statistics result, formed in float64 from its exact integers (QueryResult.window_stats
     calls this; `stats` (Q, G) and `pairs` (Q, P) are its structured arrays, `group_sizes` the G sizes in samples).  With n a
@@ -1162,6 +1180,72 @@ class QueryResult:
         return {"rows": int(pr.value or 0), "trios": int(pt.value or 0), "n_used": int(pu.value or 0), "counts": int(pc.value or 0),
                 "n_rows": int(a.value), "n_cols": int(c.value), "n_trios": int(t.value)}
 
+    ROH_SUMMARY_DTYPE = np.dtype([("n_segments", "<u4"), ("seg_sites", "<u4"), ("total_bp", "<u8"), ("longest_bp", "<u4"),
+                                  ("longest_sites", "<u4"), ("seg_hets", "<u4"), ("n_het", "<u4")])   # vs_roh_summary
+    ROH_SEGMENT_DTYPE = np.dtype([("region", "<u4"), ("column", "<u4"), ("pos_first", "<u4"), ("pos_last", "<u4"), ("row_first", "<u4"),
+                                  ("row_last", "<u4"), ("n_sites", "<u4"), ("n_het", "<u4")])   # vs_roh_segment
+
+    def roh(self, lengths=None):
+        """A ROH result (VariantStore.roh) as numpy arrays.  `summary` (structured, shape (Q, S): n_segments, seg_sites, total_bp,
+        longest_bp, longest_sites, seg_hets, n_het -- summary[q, c] belongs to region q and columns[c]), `n_sites` (uint32[Q]: the
+        sites of every region), `segments` (structured: region, column, pos_first, pos_last, row_first, row_last, n_sites, n_het;
+        ordered by region, column, occurrence) and `seg_begin` (uint64[Q S + 1]: cell (q, c) owns segments[seg_begin[q S + c] ..
+        seg_begin[q S + c + 1])) -- both None when the batch ran with segments=False --, `columns` (uint32[S], the sample ids,
+        ascending), `params` (the batch's own, a dict), `counts` (structured as for allele_counts: the count record of every
+        table row over the columns), the table's `rows` and per region `row_begin` and `row_count`; and, in float64 from the
+        integers only (roh_derived), `kb` = total_bp / 1000, `kb_avg` (NaN without segments) and -- with `lengths`, one per
+        region -- `froh` = total_bp / lengths[q].  Copies, valid after the result is closed."""
+        nq, nc, na, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        prm = _lib.RohParams()
+        cols, nsites, sb = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint64)()
+        cnt = C.POINTER(_lib.AlleleCounts)()
+        psum, pseg = C.c_void_p(), C.c_void_p()
+        _check(self._lib.vs_result_get_roh(self._h, C.byref(nq), C.byref(nc), C.byref(na), C.byref(ns), C.byref(prm), C.byref(cols), C.byref(cnt),
+                                           C.byref(psum), C.byref(nsites), C.byref(sb), C.byref(pseg)), "vs_result_get_roh")
+        Q, S, A, N = int(nq.value), int(nc.value), int(na.value), int(ns.value)
+
+        def records(p, n, dtype):
+            if not n:
+                return np.zeros(0, dtype)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n * dtype.itemsize,)).view(dtype).copy()
+        summary = records(psum, Q * S, self.ROH_SUMMARY_DTYPE).reshape(Q, S)
+        counts = records(cnt, A, self.COUNT_DTYPE)
+        has_segments = bool(prm.segments)
+        segments = records(pseg, N, self.ROH_SEGMENT_DTYPE) if has_segments else None
+        seg_begin = np.ctypeslib.as_array(sb, shape=(Q * S + 1,)).copy() if has_segments else None
+        raw = self.raw(with_carriers=False)
+        out = {"rows": raw["rows"].copy(), "row_begin": raw["row_begin"].copy(), "row_count": raw["row_count"].copy(),
+               "columns": np.ctypeslib.as_array(cols, shape=(S,)).copy(), "counts": counts, "summary": summary,
+               "n_sites": np.ctypeslib.as_array(nsites, shape=(Q,)).copy(), "segments": segments, "seg_begin": seg_begin,
+               "params": {k: int(getattr(prm, k)) for k, _ in _lib.RohParams._fields_}}
+        out.update(roh_derived(summary, lengths))
+        return out
+
+    def region_roh(self, q, roh=None):
+        """Region q of a ROH result: a dict of views into `roh` (roh() of this result; taken now when None) -- `summary` (the
+        region's row, one record per column), `segments` (the region's, None without segments), `n_sites`, `kb`, `kb_avg`."""
+        got = self.roh() if roh is None else roh
+        q = int(q)
+        Q, S = got["summary"].shape
+        if not 0 <= q < Q:
+            raise IndexError(f"region {q} of {Q}")
+        seg = None
+        if got["segments"] is not None:
+            seg = got["segments"][int(got["seg_begin"][q * S]):int(got["seg_begin"][(q + 1) * S])]
+        return {"summary": got["summary"][q], "segments": seg, "n_sites": int(got["n_sites"][q]), "kb": got["kb"][q], "kb_avg": got["kb_avg"][q]}
+
+    def roh_device(self):
+        """A ROH result as it lies in this GPU's memory: a dict of the addresses `summary` (n_regions x n_cols records of 32
+        bytes), `n_sites` (n_regions uint32), `seg_begin` (n_regions x n_cols + 1 uint64) and `segments` (n_segments records of 32
+        bytes; both 0 without segments) and `counts` (n_rows records of four uint32), with `n_regions`, `n_cols`, `n_rows` and
+        `n_segments`; complete when this returns and valid until the result is closed."""
+        nq, nc, na, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        pc, psum, pn, pb, pseg = (C.c_void_p() for _ in range(5))
+        _check(self._lib.vs_result_roh_device(self._h, C.byref(nq), C.byref(nc), C.byref(na), C.byref(ns), C.byref(pc), C.byref(psum), C.byref(pn),
+                                              C.byref(pb), C.byref(pseg)), "vs_result_roh_device")
+        return {"summary": int(psum.value or 0), "n_sites": int(pn.value or 0), "seg_begin": int(pb.value or 0), "segments": int(pseg.value or 0),
+                "counts": int(pc.value or 0), "n_regions": int(nq.value), "n_cols": int(nc.value), "n_rows": int(na.value), "n_segments": int(ns.value)}
+
     def region_variants(self, q) -> List[Variant]:
         out = []
         for line in self.region_text(q).split("\n")[1:]:
@@ -1617,6 +1701,27 @@ class VariantStore:
         h = C.c_void_p()
         _check(self._lib.vs_query_trio_scan(self._h, ptr, n, _u32_ptr(ids) if ids.size else None, ids.shape[0], C.byref(h)),
                "vs_query_trio_scan")
+        return QueryResult(self, h)
+
+    def roh(self, regions, samples=None, min_sites=50, min_bp=0, max_gap=0, max_het=0, min_ac=0, max_ac=None, segments=True) -> QueryResult:
+        """Runs of homozygosity over regions (vs_query_roh): for every region and every column of `samples` (names or ids, taken
+        as a set; None: the whole cohort) the stretches of consecutive sites at which the sample is homozygous.  A site is a
+        table row that is polymorphic over the columns with its alternate-allele count in [min_ac, max_ac] (max_ac None: no upper
+        limit); other rows are invisible.  A run may absorb up to `max_het` (0 .. 255) heterozygous sites between homozygous
+        ones, is cut where two consecutive sites lie more than `max_gap` bases apart (0: never), and is a segment when it has at
+        least `min_sites` sites and spans at least `min_bp` bases.  Integers throughout: the same call gives the same bytes.
+        segments=False leaves the segment list out (summaries only, one pass).  Regions are independent.  `regions` as for
+        allele_counts.  Read the result with QueryResult.roh / region_roh / roh_device / region_text."""
+        arr, ptr, n = _regions_array(regions)
+        h = C.c_void_p()
+        ids, ids_ptr, n_ids = self._sample_set(samples)   # (ids keeps the array alive over the call)
+        vals = {"min_sites": min_sites, "min_bp": min_bp, "max_gap": max_gap, "max_het": max_het, "min_ac": min_ac,
+                "max_ac": 0xFFFFFFFF if max_ac is None else max_ac}
+        for k, v in vals.items():
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{k} {v}: 0 .. 2**32 - 1")
+        prm = _lib.RohParams(**{k: int(v) for k, v in vals.items()}, segments=1 if segments else 0)
+        _check(self._lib.vs_query_roh(self._h, ptr, n, ids_ptr, n_ids, C.byref(prm), C.byref(h)), "vs_query_roh")
         return QueryResult(self, h)
 
     def assoc_scan(self, regions, traits, samples=None, stat="dot", trait_names=None) -> QueryResult:

@@ -125,6 +125,8 @@ struct Args {
   bool ibs_king = false;      // `ibs`: the kinship column beside the counts; --min-kinship X: only pairs with kinship >= X (implies --king)
   bool ibs_have_min = false;
   bool trios_per_trio = false;   // `trios`: one table over the batch, a line per trio, instead of the regions' rows
+  uint32_t roh_min_sites = 50, roh_min_bp = 0, roh_max_gap = 0, roh_max_het = 0;   // `roh`: the walk's parameters (--min-ac / --max-ac: the site window)
+  bool roh_summary = false;      // `roh`: a line per sample and region instead of a line per segment
   double ibs_min_kinship = 0.0;
   bool assoc_chi2 = false;   // `assoc`: the score test instead of the dot products
   bool windows_no_pairs = false, windows_derived = false;   // `windows`: no pair records; pi, theta, Tajima's D, dxy and Fst beside the integers
@@ -1369,6 +1371,89 @@ int trios_main(const Args& a) {
   return EXIT_SUCCESS;
 }
 
+// `variantstore roh`: runs of homozygosity per sample and region (vs_query_roh).  One table over the batch, tab-separated: by default
+// "Sample Region Pos1 Pos2 KB NSites NHet", a line per segment, ordered by region, then sample column, then occurrence; with
+// --summary "Sample Region NSeg KB KBAvg LongestKB NHet", a line per region and sample.  Region is <x>:<y>; KB figures are printed
+// from the integer base counts with three fixed decimals (KBAvg: floor(total_bp / NSeg) bases; NA without segments).
+int roh_usage() {
+  std::cout << "SYNOPSIS\n"
+               "        variantstore roh -p <output-prefix> -r <region> [-S <sample-file>] [--min-sites <n>] [--min-bp <n>] [--max-gap <n>]\n"
+               "                         [--max-het <n>] [--min-ac <n>] [--max-ac <n>] [--summary] [-o <outfile>] [--device <n>]\n\n"
+               "        Runs of homozygosity of every sample (or of the samples of the file) in every region: stretches of consecutive\n"
+               "        polymorphic sites (alternate-allele count within --min-ac .. --max-ac) at which the sample is homozygous.  A run\n"
+               "        absorbs up to --max-het (0 .. 255, default 0) heterozygous sites, is cut where two consecutive sites lie more\n"
+               "        than --max-gap bases apart (default 0: never) and is reported when it has at least --min-sites sites (default\n"
+               "        50, at least 1) and spans at least --min-bp bases (default 0).  --summary: per sample and region the number of\n"
+               "        segments, their total and mean length, the longest one and the sample's heterozygous sites.\n";
+  return EXIT_FAILURE;
+}
+
+// a decimal uint32 and nothing else
+bool parse_u32(const std::string& v, uint32_t& out) {
+  if (v.empty() || v.size() > 10) return false;
+  uint64_t x = 0;
+  for (char ch : v) {
+    if (ch < '0' || ch > '9') return false;
+    x = x * 10 + (uint64_t)(ch - '0');
+  }
+  if (x > UINT32_MAX) return false;
+  out = (uint32_t)x;
+  return true;
+}
+
+std::string roh_kb(uint64_t bp) {
+  char buf[40];
+  snprintf(buf, sizeof buf, "%llu.%03u", (unsigned long long)(bp / 1000), (unsigned)(bp % 1000));
+  return buf;
+}
+
+int roh_main(const Args& a) {
+  vs_index* idx = nullptr;
+  int rc = vs_index_open(a.prefix.c_str(), a.device, &idx);
+  if (rc != VS_OK) die(rc, "load");
+  std::vector<uint32_t> ids;
+  if (!a.samples_file.empty() && !read_sample_ids(idx, a.samples_file, ids)) { vs_index_close(idx); return EXIT_FAILURE; }
+  std::vector<vs_region> batch;
+  for (auto& r : read_regions(a.region)) batch.push_back(vs_region{std::get<0>(r), std::get<1>(r)});
+  vs_roh_params prm{};
+  prm.min_sites = a.roh_min_sites; prm.min_bp = a.roh_min_bp; prm.max_gap = a.roh_max_gap; prm.max_het = a.roh_max_het;
+  prm.min_ac = a.min_ac; prm.max_ac = a.max_ac; prm.segments = a.roh_summary ? 0u : 1u;
+  vs_result* res = nullptr;
+  rc = vs_query_roh(idx, batch.data(), batch.size(), ids.empty() ? nullptr : ids.data(), ids.size(), &prm, &res);
+  if (rc != VS_OK) die(rc, "roh");
+  uint64_t n_cols = 0, n_segments = 0;
+  const uint32_t* cols = nullptr;
+  const vs_roh_summary* sum = nullptr;
+  const vs_roh_segment* seg = nullptr;
+  rc = vs_result_get_roh(res, nullptr, &n_cols, nullptr, &n_segments, nullptr, &cols, nullptr, &sum, nullptr, nullptr, &seg);
+  if (rc != VS_OK) die(rc, "roh");
+  std::ofstream file;
+  if (!a.outfile.empty()) file.open(a.outfile, std::ios::binary);
+  std::ostream& out = a.outfile.empty() ? std::cout : file;
+  auto name = [&](uint32_t c) { const char* nm = vs_index_sample_name(idx, cols[c]); return nm ? nm : "?"; };
+  if (a.roh_summary) {
+    out << "Sample\tRegion\tNSeg\tKB\tKBAvg\tLongestKB\tNHet\n";
+    for (size_t q = 0; q < batch.size(); ++q)
+      for (uint64_t c = 0; c < n_cols; ++c) {
+        const vs_roh_summary& s = sum[q * n_cols + c];
+        out << name((uint32_t)c) << '\t' << batch[q].x << ':' << batch[q].y << '\t' << s.n_segments << '\t' << roh_kb(s.total_bp) << '\t'
+            << (s.n_segments ? roh_kb(s.total_bp / s.n_segments) : std::string("NA")) << '\t' << roh_kb(s.longest_bp) << '\t' << s.n_het << '\n';
+      }
+  } else {
+    out << "Sample\tRegion\tPos1\tPos2\tKB\tNSites\tNHet\n";
+    for (uint64_t k = 0; k < n_segments; ++k) {
+      const vs_roh_segment& g = seg[k];
+      const uint64_t bp = (uint64_t)(g.pos_last > g.pos_first ? g.pos_last - g.pos_first : 0u) + 1u;
+      out << name(g.column) << '\t' << batch[g.region].x << ':' << batch[g.region].y << '\t' << g.pos_first << '\t' << g.pos_last << '\t' << roh_kb(bp) << '\t'
+          << g.n_sites << '\t' << g.n_het << '\n';
+    }
+  }
+  out.flush();
+  vs_result_free(res);
+  vs_index_close(idx);
+  return EXIT_SUCCESS;
+}
+
 // `variantstore ldmatrix`: the full LD block of every region (vs_query_ld_matrix) over the same samples.  Output as `counts`:
 // "#region <i> <x>:<y>", then the region's text (a header of the reported rows' <Pos>:<Ref>:<Alt>, then one line per row with its
 // r^2 -- or with --dot its dot product -- against every one of them).
@@ -1569,8 +1654,18 @@ int main(int argc, char** argv) {
       else if (f == "--nprocs-same-device") a.nprocs_same_device = true;
       else if (f == "--resident-lists") a.resident_lists = true;
       else { std::cerr << "unknown option " << f << "\n"; return EXIT_FAILURE; }
-    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "prune" || a.cmd == "clump" || a.cmd == "ldscore" || a.cmd == "groups" || a.cmd == "windows" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs" || a.cmd == "trios") {
+    } else if (a.cmd == "counts" || a.cmd == "burden" || a.cmd == "genotypes" || a.cmd == "ld" || a.cmd == "ldmatrix" || a.cmd == "prune" || a.cmd == "clump" || a.cmd == "ldscore" || a.cmd == "groups" || a.cmd == "windows" || a.cmd == "assoc" || a.cmd == "assocmatrix" || a.cmd == "score" || a.cmd == "scorematrix" || a.cmd == "gram" || a.cmd == "ibs" || a.cmd == "trios" || a.cmd == "roh") {
       if (f == "-p" || f == "--output-prefix") a.prefix = need(i);
+      else if (a.cmd == "roh" && (f == "--min-sites" || f == "--min-bp" || f == "--max-gap" || f == "--max-het" || f == "--min-ac" || f == "--max-ac")) {
+        const std::string v = need(i);
+        uint32_t x = 0;
+        if (!parse_u32(v, x)) { std::cerr << f << " takes a whole number between 0 and 4294967295, not '" << v << "'\n"; return roh_usage(); }
+        if (f == "--min-sites" && x == 0) { std::cerr << "--min-sites takes at least 1\n"; return roh_usage(); }
+        if (f == "--max-het" && x > 255) { std::cerr << "--max-het takes at most 255, not " << x << "\n"; return roh_usage(); }
+        (f == "--min-sites" ? a.roh_min_sites : f == "--min-bp" ? a.roh_min_bp : f == "--max-gap" ? a.roh_max_gap : f == "--max-het" ? a.roh_max_het
+         : f == "--min-ac" ? a.min_ac : a.max_ac) = x;
+      }
+      else if (a.cmd == "roh" && f == "--summary") a.roh_summary = true;
       else if ((a.cmd == "burden" || a.cmd == "prune" || a.cmd == "ldscore") && f == "--min-ac") a.min_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if ((a.cmd == "burden" || a.cmd == "prune" || a.cmd == "ldscore") && f == "--max-ac") a.max_ac = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
       else if ((a.cmd == "ld" || a.cmd == "prune" || a.cmd == "clump" || a.cmd == "ldscore") && (f == "-w" || f == "--window")) a.ld_window = (uint32_t)strtoul(need(i).c_str(), nullptr, 10);
@@ -1682,6 +1777,11 @@ int main(int argc, char** argv) {
   if (a.cmd == "trios") {
     if (a.prefix.empty() || a.region.empty() || a.trios_file.empty()) return trios_usage();
     return trios_main(a);
+  }
+  if (a.cmd == "roh") {
+    if (a.prefix.empty() || a.region.empty()) return roh_usage();
+    if (a.min_ac > a.max_ac) { std::cerr << "--min-ac " << a.min_ac << " is above --max-ac " << a.max_ac << "\n"; return roh_usage(); }
+    return roh_main(a);
   }
   if (a.cmd == "construct") {
     if (a.ref.empty() || a.vcf.empty() || a.prefix.empty()) return usage();

@@ -251,7 +251,8 @@ struct vs_result {
                  // kKindScores: per-sample scores; kKindGram: sample Gram matrix / GRM; kKindIbs: pairwise IBS counts / KING kinship;
                  // kKindLdMatrix: the full LD block of every region; kKindAssocMatrix: trait-matrix association scan;
                  // kKindScoreMatrix: score matrix; kKindPrune: LD pruning verdicts; kKindClump: p-value clumping verdicts; kKindLdScore: LD scores;
-                 // kKindWindowStats: windowed diversity statistics; kKindTrio: Mendelian errors and transmission counts per row and trio
+                 // kKindWindowStats: windowed diversity statistics; kKindTrio: Mendelian errors and transmission counts per row and trio;
+                 // kKindRoh: runs of homozygosity per region and column
   // allele-count results (vs_query_allele_counts): 16 bytes per table row in HBM, and their page-locked host copy
   uint4* d_counts = nullptr;
   DevBuf counts_pin{nullptr, 0};
@@ -362,6 +363,15 @@ struct vs_result {
   uint64_t n_trios = 0;
   size_t trio_table_off = 0, trio_bytes = 0;
   std::vector<uint32_t> h_trio_cols;   // the table as the batch uploads it
+  // ROH results (vs_query_roh): one buffer in HBM (d_roh) -- Q x n_cols summaries of 32 bytes, n_sites (4 bytes a region, rounded up
+  // to 16), the nonzero cells of the (temporary) genotype matrix (d_cell_total, two words), then from roh_begin_off on seg_begin
+  // (Q x n_cols + 1 words of 8 bytes; with segments only) -- copied to cells_pin in one piece (roh_bytes); the segments (32 bytes
+  // each, roh_segs of them) in d_roh_seg / owner_pin; the count record of every table row in d_counts / counts_pin, the column ids h_cols
+  uint8_t* d_roh = nullptr;
+  uint4* d_roh_seg = nullptr;
+  size_t roh_sites_off = 0, roh_begin_off = 0, roh_bytes = 0;
+  uint64_t roh_segs = 0;
+  vs_roh_params roh{};
   // sequence results (query types 2 and 3)
   DevSeqResult sq{};
   uint64_t seq_bytes = 0;
@@ -389,9 +399,10 @@ constexpr int kKindPrune = 20;   // ... of a pruning result: the rows of type 6,
 constexpr int kKindLdScore = 22;   // ... of an LD-score result: the rows of type 6, a sum, a pair count and a state byte per reported row instead of carrier lists
 constexpr int kKindWindowStats = 23;   // ... of a window-statistics result: the rows of type 6, a record per region and sample group (and pair of groups) instead of carrier lists
 constexpr int kKindTrio = 24;    // ... of a trio result: the rows of type 6, a record of Mendelian errors and transmission counts per row and per trio instead of carrier lists
+constexpr int kKindRoh = 25;     // ... of a ROH result: the rows of type 6, a summary per region and column and the segments instead of carrier lists
 constexpr int kKindClump = 21;   // ... of a clumping result: the rows of type 6, a verdict byte and an owner per reported row instead of carrier lists
 static bool no_lists(const vs_result* r) {
-  return r->kind == kKindTrio || r->kind == kKindWindowStats || r->kind == kKindLdScore || r->kind == kKindClump || r->kind == kKindPrune || r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
+  return r->kind == kKindRoh || r->kind == kKindTrio || r->kind == kKindWindowStats || r->kind == kKindLdScore || r->kind == kKindClump || r->kind == kKindPrune || r->kind == kKindScoreMatrix || r->kind == kKindAssocMatrix || r->kind == kKindLdMatrix || r->kind == kKindIbs || r->kind == kKindGram || r->kind == kKindCounts || r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindGroups || r->kind == kKindAssoc ||
          r->kind == kKindScores;
 }
 static int refuse_no_lists(const vs_result* r, const char* what) {
@@ -412,6 +423,8 @@ static int refuse_no_lists(const vs_result* r, const char* what) {
     return fail(VS_ERR_UNSUPPORTED, "%s: an IBS result holds samples x samples matrices of genotype-state counts, no carrier lists (vs_result_get_sample_ibs)", what);
   if (r->kind == kKindTrio)
     return fail(VS_ERR_UNSUPPORTED, "%s: a trio result holds a record of Mendelian errors and transmission counts per row and per trio, no carrier lists (vs_result_get_trio_scan)", what);
+  if (r->kind == kKindRoh)
+    return fail(VS_ERR_UNSUPPORTED, "%s: a ROH result holds a summary per region and column and the segments, no carrier lists (vs_result_get_roh)", what);
   if (r->kind == kKindLdMatrix)
     return fail(VS_ERR_UNSUPPORTED, "%s: an LD-matrix result holds a square block of pair statistics per region, no carrier lists (vs_result_get_ld_matrix)", what);
   if (r->kind == kKindClump)
@@ -1294,7 +1307,8 @@ static int capture_totals(vs_result* r) {
 // WindowStats: mask and n_cols as for Groups; ws_sizes: the groups' sizes (n_cols of them), ws_pairs: the pair records (0: none).
 // Trio: mask, rank and n_cols as for the matrix (the members); trio_cols (host memory, owned by the result): three column indices
 // per trio -- child, father, mother --, n_trios of them.
-enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix, Prune, Clump, LdScore, WindowStats, Trio };
+// Roh: mask, rank and n_cols as for the matrix; roh: the walk's parameters (min_ac / max_ac: the site window, as Prune's).
+enum class ReqKind { Lists, Counts, Burden, Matrix, LD, Groups, Assoc, Scores, Gram, Ibs, LdMatrix, AssocMatrix, ScoreMatrix, Prune, Clump, LdScore, WindowStats, Trio, Roh };
 struct SharedReq {
   ReqKind kind = ReqKind::Lists;
   const uint64_t* mask = nullptr;
@@ -1318,6 +1332,7 @@ struct SharedReq {
   uint32_t ws_pairs = 0;
   const uint32_t* trio_cols = nullptr;
   uint64_t n_trios = 0;
+  vs_roh_params roh{};
   bool window() const { return min_ac != 0 || max_ac != UINT32_MAX; }
 };
 static int run_type6_shared(vs_index* idx, const vs_region* regions, uint64_t n, vs_result* r, bool regions_on_device, const uint64_t* site_records,
@@ -1747,6 +1762,7 @@ static int launch_trio(vs_index* idx, vs_result* r, const uint8_t* cells, uint64
 //                      Gram: the same two, then k_sample_gram, k_gram_moments and (GRM) k_gram_finish (launch_gram) |
 //                      Ibs: the same two, then k_ibs_n_used, k_sample_ibs and k_ibs_finish (launch_ibs) |
 //                      Trio: the same two, then k_ibs_n_used and k_trio_scan (launch_trio); the trio table goes up in front of them |
+//                      Roh: the same two, then k_roh_sites and k_roh_walk; with segments a scan, one host wait and the walk again (launch_roh) |
 //                      LdMatrix: in front of them k_ld_block_scan over the per-region row counts and one host wait for its totals
 //                      (ld_matrix_tables: the size limit, the temporary matrix, the cells); behind them k_ld_block (launch_ld_block)
 //                      Prune: in front of them k_prune_scan over the per-region row counts and one host wait for its total
@@ -1803,7 +1819,7 @@ struct SharedCtx {
   uint64_t* am_dev = nullptr;   // shared_tables: a trait-matrix batch's Sy, vy, shifts and limb panel on the device (ld_tmp)
   uint32_t fill_launches = 0;   // the consumer's, for the phase times
   SharedCtx(vs_index* i, vs_result* res, uint64_t nn, const SharedReq& q)
-      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix || q.kind == ReqKind::Prune || q.kind == ReqKind::Clump || q.kind == ReqKind::LdScore || q.kind == ReqKind::WindowStats || q.kind == ReqKind::Trio) {}
+      : idx(i), r(res), n(nn), req(q), scratch(i), ld_tmp(i), lists(q.kind == ReqKind::Lists), behind_perm(q.kind == ReqKind::Burden || q.kind == ReqKind::Matrix || q.kind == ReqKind::LD || q.kind == ReqKind::Scores || q.kind == ReqKind::Gram || q.kind == ReqKind::Ibs || q.kind == ReqKind::LdMatrix || q.kind == ReqKind::AssocMatrix || q.kind == ReqKind::ScoreMatrix || q.kind == ReqKind::Prune || q.kind == ReqKind::Clump || q.kind == ReqKind::LdScore || q.kind == ReqKind::WindowStats || q.kind == ReqKind::Trio || q.kind == ReqKind::Roh) {}
 };
 
 // The nine per-region arrays of a shared batch, f(array, elements) for each: shared_setup carves them out of one buffer of the
@@ -2164,6 +2180,28 @@ static int trio_fits(SharedCtx& c) {
               (unsigned long long)(r->d.A * row_bytes + trio_part), (unsigned long long)(r->d.A * r->mx_pitch), (unsigned long long)(r->d.A * 16),
               (unsigned long long)(r->d.A * 16), (unsigned long long)(c.req.n_trios * 16), (unsigned long long)(c.req.n_trios * 12), (unsigned long long)(cap >> 20));
 }
+// A ROH batch: the temporary matrix, the count records and the walk's 8 bytes a row; per (region, column) the summary (32 bytes) and
+// -- with segments -- seg_begin (8) and the scan's input (4); n_sites; the segments (32 bytes each; `segs` is 0 until pass 1 has
+// counted them).  All together under the same limit; and a table of 2^31 rows or more is refused (row offsets and site counts are 32-bit).
+static int roh_fits(SharedCtx& c, uint64_t segs) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const uint64_t cap = idx->opts.matrix_max_mib ? (uint64_t)idx->opts.matrix_max_mib << 20 : 32ull << 30;
+  r->mx_pitch = ((uint64_t)c.req.n_cols + 15) & ~15ull;
+  const bool rows_fit = r->d.A < (1ull << 31);
+  const unsigned __int128 cells = (unsigned __int128)r->d.Q * c.req.n_cols;
+  const unsigned __int128 row_part = (unsigned __int128)r->d.A * (r->mx_pitch + 24), cell_part = cells * (c.req.roh.segments ? 44u : 32u) + (unsigned __int128)r->d.Q * 4 + 64,
+                          seg_part = (unsigned __int128)segs * 32, need = row_part + cell_part + seg_part;
+  if (rows_fit && need <= cap) return VS_OK;
+  (void)hipStreamSynchronize(c.ps);   // (the plan's last kernels still read the call's temporaries: they go back to the pool on return)
+  (void)hipStreamSynchronize(idx->stream);
+  if (!rows_fit)
+    return fail(VS_ERR_ARG, "a ROH batch over %llu rows: row offsets and site counts are 32-bit, the table may have at most 2^31 - 1 rows: split the batch", (unsigned long long)r->d.A);
+  auto sat = [](unsigned __int128 v) { return v > ~0ull ? ~0ull : (unsigned long long)v; };
+  return fail(VS_ERR_ARG, "a ROH batch of %llu regions x %u columns over %llu rows with %llu segments takes %llu bytes (%llu of the genotype matrix it walks, %llu of the "
+              "count records and site words, %llu of the summaries and per-cell words, %llu of the segments), more than the limit of %llu MiB (option matrix_max_mib): "
+              "split the batch or the samples", (unsigned long long)r->d.Q, c.req.n_cols, (unsigned long long)r->d.A, (unsigned long long)segs, sat(need),
+              sat((unsigned __int128)r->d.A * r->mx_pitch), sat((unsigned __int128)r->d.A * 24), sat(cell_part), sat(seg_part), (unsigned long long)(cap >> 20));
+}
 // Reads the totals (*pt) or the speculation.  Leaves U / n_slow / n_runs, the result's sizes and bookkeeping, a speculative batch
 // registered with its slot, what the request's kind allocates, and the form of the rows and the expansion (n_fill .. lean).
 static int shared_tables(SharedCtx& c) {
@@ -2276,6 +2314,21 @@ static int shared_tables(SharedCtx& c) {
       VS_TRY(ralloc(r, r->trio_bytes, &r->d_trio));
       r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_trio + head);
       r->n_trios = q.n_trios;
+      break;
+    }
+    case ReqKind::Roh: {   // (n_sites and the matrix kernel's count of nonzero cells live behind the summaries, seg_begin behind them; the segments wait for pass 1: launch_roh)
+      VS_TRY(roh_fits(c, 0));
+      VS_TRY(ralloc(r, d.A, &d.rows));
+      VS_TRY(dev_alloc(idx, (size_t)(d.A * r->mx_pitch), (void**)&c.ld_matrix, &c.ld_tmp.bufs));
+      VS_TRY(ralloc(r, d.A, &r->d_counts));
+      const size_t cells = (size_t)d.Q * q.n_cols;
+      r->roh_sites_off = cells * 32;
+      const size_t head = r->roh_sites_off + (((size_t)d.Q * 4 + 15) & ~(size_t)15);
+      r->roh_begin_off = head + 16;
+      r->roh_bytes = r->roh_begin_off + (q.roh.segments ? (cells + 1) * 8 : 0);
+      VS_TRY(ralloc(r, r->roh_bytes, &r->d_roh));
+      r->d_cell_total = reinterpret_cast<unsigned long long*>(r->d_roh + head);
+      r->roh = q.roh;
       break;
     }
     case ReqKind::AssocMatrix: {   // (the traits' words and the limb panel are temporaries like the matrix: the kernel alone reads them)
@@ -2450,6 +2503,7 @@ static int launch_clump(SharedCtx& c);
 static int ldscore_tables(SharedCtx& c);
 static int launch_ldscore(SharedCtx& c);
 static int launch_window_stats(SharedCtx& c);
+static int launch_roh(SharedCtx& c);
 static int shared_columns(SharedCtx& c) {
   vs_index* idx = c.idx; vs_result* r = c.r;
   if (!c.behind_perm && !r->d.A) return VS_OK;
@@ -2466,7 +2520,7 @@ static int shared_columns(SharedCtx& c) {
   else if (c.req.kind == ReqKind::WindowStats) {   // (a table without rows: no group kernel, the records are zeros all the same)
     if (r->d.A) launch_group_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, c.req.n_cols, c.ws_counts);
     VS_TRY(launch_window_stats(c));
-  } else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD, Gram, Ibs, Trio, ScoreMatrix; Burden only under a window: shared_tables gives it counts)
+  } else if (c.req.kind != ReqKind::Matrix && r->d_counts && r->d.A)   // (Counts, LD, Gram, Ibs, Trio, Roh, ScoreMatrix; Burden only under a window: shared_tables gives it counts)
     launch_allele_counts(idx, r->d, c.u_site, c.U, c.d_mask, c.req.words, r->d_counts);
   HIP_TRY(hipGetLastError());
   if (c.req.kind == ReqKind::Assoc) VS_TRY(launch_assoc(idx, r, c.u_site, c.U, c.d_mask, c.d_rank, c.d_pheno, c.req));
@@ -2500,10 +2554,57 @@ static int shared_columns(SharedCtx& c) {
   } else if (c.req.kind == ReqKind::Trio) {
     VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
     VS_TRY(launch_trio(idx, r, c.ld_matrix, c.U, c.req));
+  } else if (c.req.kind == ReqKind::Roh) {
+    VS_TRY(launch_matrix(idx, r, c.ld_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
+    VS_TRY(launch_roh(c));
   } else if (c.req.kind == ReqKind::Matrix) VS_TRY(launch_matrix(idx, r, r->d_matrix, c.u_site, c.U, c.d_mask, c.d_rank, c.req));
   HIP_TRY(hipEventRecord(r->ev_fill[1], idx->stream));
   r->pending = true;
   c.fill_launches = 1;
+  return VS_OK;
+}
+
+// The summaries and segments of a ROH batch behind the permutation (the per-region arrays are in the caller's order) from its temporary
+// genotype matrix and the table's counts: k_roh_sites over the table, k_roh_walk<false> over (region, column tile).  With segments:
+// the engine's exclusive scan over the cells' n_segments, ONE host wait for the total (inside the pair of events, as launch_scores'),
+// the segment bytes held against option matrix_max_mib before they are allocated, then k_roh_walk<true>.
+static int launch_roh(SharedCtx& c) {
+  vs_index* idx = c.idx; vs_result* r = c.r;
+  const DevResult& d = r->d;
+  const SharedReq& q = c.req;
+  const uint64_t cells = d.Q * q.n_cols;
+  RohArgs a{};
+  a.cells = c.ld_matrix; a.row_begin = (const uint64_t*)d.var_begin; a.row_count = (const uint64_t*)d.q_nvar; a.Q = d.Q;
+  a.pitch = (uint32_t)r->mx_pitch; a.n_cols = q.n_cols; a.n_tiles = (q.n_cols + kRohTileCols - 1) / kRohTileCols;
+  a.min_sites = q.roh.min_sites; a.min_bp = q.roh.min_bp; a.max_gap = q.roh.max_gap; a.max_het = q.roh.max_het;
+  a.summary = reinterpret_cast<RohSummary*>(r->d_roh);
+  a.n_sites = reinterpret_cast<uint32_t*>(r->d_roh + r->roh_sites_off);
+  if (d.Q * a.n_tiles > 0x7FFFFFFFull) return fail(VS_ERR_ARG, "batch too large for one launch (%llu regions x %u column tiles)", (unsigned long long)d.Q, a.n_tiles);
+  uint2* sites = nullptr;
+  VS_TRY(dev_alloc(idx, (size_t)d.A * 8, (void**)&sites, &c.ld_tmp.bufs));
+  a.sites = sites;
+  if (d.A) {
+    RohSiteArgs s{};
+    s.rows = (const VariantRow*)d.rows; s.counts = r->d_counts; s.A = d.A; s.n_cols = q.n_cols; s.min_ac = q.roh.min_ac; s.max_ac = q.roh.max_ac; s.sites = sites;
+    hipLaunchKernelGGL(k_roh_sites, dim3((unsigned)((d.A + 255) / 256)), dim3(256), 0, idx->stream, s);
+  }
+  uint64_t* seg_begin = reinterpret_cast<uint64_t*>(r->d_roh + r->roh_begin_off);
+  if (q.roh.segments) VS_TRY(dev_alloc(idx, (size_t)cells * 4, (void**)&a.seg_count, &c.ld_tmp.bufs));
+  const unsigned blocks = (unsigned)(d.Q * a.n_tiles);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_roh_walk<false>), dim3(blocks), dim3(256), 0, idx->stream, a);
+  HIP_TRY(hipGetLastError());
+  if (!q.roh.segments) return VS_OK;
+  VS_TRY(exclusive_scan(idx, (const uint32_t*)a.seg_count, cells, seg_begin, &c.ld_tmp.bufs));
+  uint64_t segs = 0;
+  HIP_TRY(hipMemcpyAsync(&segs, seg_begin + cells, 8, hipMemcpyDeviceToHost, idx->stream));
+  HIP_TRY(hipStreamSynchronize(idx->stream));
+  VS_TRY(roh_fits(c, segs));
+  r->roh_segs = segs;
+  VS_TRY(ralloc(r, (size_t)segs * 2, &r->d_roh_seg));
+  if (!segs) return VS_OK;
+  a.seg_begin = seg_begin; a.segments = r->d_roh_seg;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_roh_walk<true>), dim3(blocks), dim3(256), 0, idx->stream, a);
+  HIP_TRY(hipGetLastError());
   return VS_OK;
 }
 
@@ -5015,6 +5116,26 @@ int vs_query_trio_scan(vs_index* idx, const vs_region* regions, uint64_t n, cons
   });
 }
 
+int vs_query_roh(vs_index* idx, const vs_region* regions, uint64_t n, const uint32_t* sample_ids, uint64_t n_ids, const vs_roh_params* params, vs_result** out) {
+  VS_TRY(column_query_args(idx, out, regions, n, sample_ids, n_ids, "a ROH"));
+  if (!params) return fail(VS_ERR_ARG, "null argument: a ROH batch takes its parameters (params)");
+  if (params->min_sites == 0) return fail(VS_ERR_ARG, "a ROH segment of at least 0 sites (min_sites is 1 or more)");
+  if (params->max_het > kRohMaxHet) return fail(VS_ERR_ARG, "a ROH run absorbing %u heterozygous sites (max_het is 0 .. %u)", params->max_het, kRohMaxHet);
+  if (params->min_ac > params->max_ac) return fail(VS_ERR_ARG, "an empty allele-count window [%u, %u]", params->min_ac, params->max_ac);
+  std::vector<uint64_t> mask;
+  std::vector<uint32_t> rank, cols;
+  VS_TRY(sample_columns(idx, sample_ids, n_ids, mask, rank, cols));
+  if (mask.size() * 8 > kMatrixMaskMaxBytes)
+    return fail(VS_ERR_UNSUPPORTED, "a sample subset of a cohort of %u samples does not fit the matrix kernel's LDS", idx->g.num_samples);
+  SharedReq req = column_request(ReqKind::Roh, mask, rank, cols.size());
+  req.roh = *params;
+  req.roh.segments = params->segments ? 1u : 0u;
+  return make_result(idx, kKindRoh, out, [&](vs_result* r) {
+    r->h_cols = cols;
+    return run_column_batch(idx, regions, n, r, req);
+  });
+}
+
 int vs_query_sample_var_in_ref(vs_index* idx, const vs_region* regions, uint64_t n, uint32_t sample_id, vs_result** out) {
   if (!out || (n && !regions)) return fail(VS_ERR_ARG, "null argument");
   VS_TRY(query_handle(idx));
@@ -5368,7 +5489,7 @@ int vs_result_totals(const vs_result* cr, uint64_t* n_regions, uint64_t* n_varia
       for (uint64_t i = 0, e = r->d.Q * r->n_groups; i < e; ++i) nc += (w[i].sum_ac + w[i].obs_het) / 2;
       r->n_carriers_kept = nc;
     }
-    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindPrune || r->kind == kKindClump || r->kind == kKindLdScore || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindTrio || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS, trio: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
+    if (r->kind == kKindBurden || r->kind == kKindMatrix || r->kind == kKindLd || r->kind == kKindLdMatrix || r->kind == kKindPrune || r->kind == kKindClump || r->kind == kKindLdScore || r->kind == kKindGram || r->kind == kKindIbs || r->kind == kKindTrio || r->kind == kKindRoh || r->kind == kKindScoreMatrix) {   // (LD, LD matrix, Gram, IBS, trio, ROH: of the matrix the band / the products were formed from) the sum of `variants` over the burden matrix, the nonzero cells of the genotype matrix: the kernels' own word
       VS_TRY(result_ready(r));
       uint64_t nc = 0;
       HIP_TRY(hipMemcpyAsync(&nc, r->d_cell_total, 8, hipMemcpyDeviceToHost, idx->stream));
@@ -5551,6 +5672,31 @@ int vs_result_format_region(vs_result* r, uint64_t q, const char** text, uint64_
       out.append(idx->seq_chars, v.alt_off, v.alt_len);
       const vs_trio_counts& t = rec[a - a0];
       for (uint32_t f : {cnt[a - a0].y, t.errors, t.denovo, t.transmitted, t.untransmitted}) { out += '\t'; out += std::to_string(f); }
+      out += '\n';
+    }
+    *text = out.c_str();
+    if (len) *len = out.size();
+    return VS_OK;
+  }
+  if (r->kind == kKindRoh) {   // the region's segments, a line each, in column order: integers only (KB from bp with three fixed decimals)
+    if (!r->roh.segments) return fail(VS_ERR_ARG, "the ROH batch was run without segments (vs_roh_params::segments): its summaries are vs_result_get_roh's");
+    VS_TRY(array_to_host(r, r->d_roh, r->roh_bytes, &r->cells_pin, "ROH summaries"));
+    VS_TRY(array_to_host(r, r->d_roh_seg, (size_t)r->roh_segs * 32, &r->owner_pin, "ROH segments"));
+    const size_t nc = r->h_cols.size();
+    const uint64_t* sb = (const uint64_t*)((const uint8_t*)r->cells_pin.p + r->roh_begin_off) + q * nc;
+    const vs_roh_segment* seg = (const vs_roh_segment*)r->owner_pin.p;
+    std::string& out = r->text;
+    out = "Sample\tPos1\tPos2\tKB\tNSites\tNHet\n";
+    char kb[40];
+    for (uint64_t s = sb[0]; s < sb[nc]; ++s) {
+      const vs_roh_segment& g = seg[s];
+      const uint32_t id = r->h_cols[g.column];
+      const uint64_t bp = (uint64_t)(g.pos_last > g.pos_first ? g.pos_last - g.pos_first : 0u) + 1u;
+      snprintf(kb, sizeof kb, "%llu.%03u", (unsigned long long)(bp / 1000), (unsigned)(bp % 1000));
+      out += id < idx->g.sample_names.size() ? idx->g.sample_names[id] : std::string("?");
+      for (uint32_t f : {g.pos_first, g.pos_last}) { out += '\t'; out += std::to_string(f); }
+      out += '\t'; out += kb;
+      for (uint32_t f : {g.n_sites, g.n_het}) { out += '\t'; out += std::to_string(f); }
       out += '\n';
     }
     *text = out.c_str();
@@ -6450,6 +6596,46 @@ int vs_result_trio_scan_device(vs_result* r, uint64_t* n_rows, uint64_t* n_cols,
   if (n_rows) *n_rows = r->d.A;
   if (n_cols) *n_cols = r->h_cols.size();
   if (n_trios) *n_trios = r->n_trios;
+  return VS_OK;
+}
+
+int vs_result_get_roh(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, uint64_t* n_rows, uint64_t* n_segments, vs_roh_params* params,
+                      const uint32_t** col_ids, const vs_allele_counts** counts, const vs_roh_summary** summary, const uint32_t** n_sites,
+                      const uint64_t** seg_begin, const vs_roh_segment** segments) {
+  VS_TRY(result_enter(r, Want::Variants, true));
+  if (!summary) return fail(VS_ERR_ARG, "null argument");
+  if (r->kind != kKindRoh) return fail(VS_ERR_ARG, "not a ROH result (vs_query_roh)");
+  static_assert(sizeof(vs_roh_summary) == 32 && sizeof(vs_roh_segment) == 32, "record layout of the ABI");
+  VS_TRY(array_to_host(r, r->d_roh, r->roh_bytes, &r->cells_pin, "ROH summaries"));
+  if (counts) VS_TRY(counts_to_host(r));
+  if (r->roh.segments && segments) VS_TRY(array_to_host(r, r->d_roh_seg, (size_t)r->roh_segs * 32, &r->owner_pin, "ROH segments"));
+  const uint8_t* base = (const uint8_t*)r->cells_pin.p;
+  *summary = (const vs_roh_summary*)base;
+  if (n_sites) *n_sites = (const uint32_t*)(base + r->roh_sites_off);
+  if (seg_begin) *seg_begin = r->roh.segments ? (const uint64_t*)(base + r->roh_begin_off) : nullptr;
+  if (segments) *segments = r->roh.segments ? (const vs_roh_segment*)r->owner_pin.p : nullptr;
+  if (counts) *counts = (const vs_allele_counts*)r->counts_pin.p;
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_rows) *n_rows = r->d.A;
+  if (n_segments) *n_segments = r->roh_segs;
+  if (params) *params = r->roh;
+  if (col_ids) *col_ids = r->h_cols.data();
+  return VS_OK;
+}
+
+int vs_result_roh_device(vs_result* r, uint64_t* n_regions, uint64_t* n_cols, uint64_t* n_rows, uint64_t* n_segments, const void** dev_counts,
+                         const void** dev_summary, const void** dev_n_sites, const void** dev_seg_begin, const void** dev_segments) {
+  VS_TRY(device_matrix_ready(r, dev_summary, kKindRoh, "not a ROH result (vs_query_roh)"));
+  *dev_summary = r->d_roh;
+  if (dev_n_sites) *dev_n_sites = r->d_roh + r->roh_sites_off;
+  if (dev_seg_begin) *dev_seg_begin = r->roh.segments ? r->d_roh + r->roh_begin_off : nullptr;
+  if (dev_segments) *dev_segments = r->roh.segments ? r->d_roh_seg : nullptr;
+  if (dev_counts) *dev_counts = r->d_counts;
+  if (n_regions) *n_regions = r->d.Q;
+  if (n_cols) *n_cols = r->h_cols.size();
+  if (n_rows) *n_rows = r->d.A;
+  if (n_segments) *n_segments = r->roh_segs;
   return VS_OK;
 }
 

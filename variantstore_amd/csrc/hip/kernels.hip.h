@@ -114,6 +114,12 @@
 //                       workgroup, a lane per trio; per-trio sums in the lane, per-row sums by one halving butterfly a wave,
 //                       32-bit integer atomics: exact and order-free; n_used is k_ibs_n_used's (vs_query_trio_scan: no reference
 //                       counterpart)
+// k_roh_sites           Runs of homozygosity: per table row {pos, site} from the count records (eligible as for pruning: kept,
+//  k_roh_walk           polymorphic, inside the allele-count window); then a COLUMN walk of the temporary matrix -- a workgroup per
+//                       (region, 256 columns), blocks of 64 rows staged in LDS through registers, double-buffered, a block without
+//                       a site skipped, a lane per column, the run machine in registers, selects but for the close; pass 1 the
+//                       32-byte summaries, the engine's scan over n_segments, pass 2 the segments.  Integers only (vs_query_roh:
+//                       no reference counterpart)
 // k_score_matrix        D^T W over the same dosages: samples x K weighted sums (K up to 65,536) over the rows a batch reports, the
 //  k_score_matrix_weights  wide form of k_sample_scores.  The report-keyed weights become per-row totals of fixed-point integers
 //  k_score_matrix_limbs    (64-bit atomics), the totals a panel of four or five int8 limbs; 128 columns x 16 or 32 scores x a chunk
@@ -149,4 +155,5 @@
 #include "k_assoc_matrix.hip.h"
 #include "k_ibs.hip.h"
 #include "k_trio.hip.h"
+#include "k_roh.hip.h"
 #include "k_score_matrix.hip.h"
